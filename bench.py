@@ -7,6 +7,14 @@
                   [--staged]         (ragged: headline = the staged form; default: as delivered, the staged form beside it)
                   [--as-delivered]   (e / f: int64 ids + SparseTensor indices resident on the device, pre-pass there;
                                       default: as the staged Addons>ConcatInputs leaves the request, host cost stated)
+                  [--full]           (everything beyond the headline: see below)
+                  [--dump-outputs DIR]   (DIR/group_<g>.npy: the output the last timed step left in its arena)
+
+A plain run sets up, warms up, times exactly --steps requests once, writes its outputs when --dump-outputs is given and
+prints the line.  Everything else it measures or checks runs only with --full: the closed-form check of the resident
+requests, repeats of the timed region, latency percentiles, the roofline's memory probes, arena reuse, overlapped serving,
+the single caller stream, the as-delivered / staged forms beside the headline, host staging cost, the CPU baseline, the
+PCIe-inclusive pass, the live PMC traffic and the sharded side record of a multi-GPU line.
 
 A *step* is one request: one pass of the fused feature-column path (ids resident
 in HBM -> [batch, sum(dim)] concat output resident in HBM) over one batch of
@@ -23,7 +31,7 @@ Whether tables are replicated or sharded is decided by the placement gate
 (recom_amd/placement.py) from the workload's table bytes and the GPU's HBM.
 
 The timed loop is native (recom_amd/csrc/fcp_harness.hip); rank 0 prints ONE JSON
-line: `value` = exactly --steps requests from one serve worker; `overlapped_serving` =
+line: `value` = exactly --steps requests from one serve worker; with --full, `overlapped_serving` =
 the reference's multi-worker protocol (best of 2 / 3 / 4 workers, >= 400 requests each).  `roofline.achieved` = algorithmic bytes per request (SURVEY.md §8d formula,
 DESIGN.md §5) / average device time per request from HIP events recorded on the
 launch stream around the timed region.  `cpu_baseline` times the CPU oracle
@@ -49,7 +57,7 @@ import numpy as np  # noqa: E402
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 PREWARM_S = 0.25       # untimed pre-warm in front of the timed region, seconds of the same requests (whatever --warmup is)
 PREWARM_CHUNK = 256    # ... issued in calls of this many requests
-REPEATS = 5            # the K timed steps are repeated this many times (9 times when K < 200); the median repeat is the one reported
+REPEATS = 5            # --full: the K timed steps are timed this many times in all (9 times when K < 200) for their spread
 METRIC = "inference QPS + p50 latency, 1000-col synth model, batch 512, 1\u00d7MI355X"  # == BASELINE.json "metric"
 try:
     with open(os.path.join(ROOT, "BASELINE.json")) as _f:
@@ -206,6 +214,31 @@ def host_staging_cost(raw_model, n_requests: int = 8):
 def side_error(e: BaseException) -> str:
     """What a failed SIDE record says in its place (the line's contract fields never depend on a side record)."""
     return f"{type(e).__name__}: {e}"[:400]
+
+
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(h, index: int, out_dir: str) -> dict:
+    """What the timed loop computed for its last request (worker 0, resident request `index`): the concat matrices copied
+    out of the ring arena that request wrote (ServingHarness.last_output), as out_dir/group_<g>.npy (float32).  Beyond
+    DUMP_LIMIT_BYTES in all, the same rows of every group are kept: a sorted sample drawn with a fixed seed."""
+    groups = h.last_output(0)
+    total = sum(g.nbytes for g in groups)
+    rows = None
+    if total > DUMP_LIMIT_BYTES:
+        n = max(g.shape[0] for g in groups)
+        keep = max(1, int(n * DUMP_LIMIT_BYTES // total))
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        groups = [g[rows[rows < g.shape[0]]] for g in groups]
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for g, a in enumerate(groups):
+        np.save(os.path.join(out_dir, f"group_{g}.npy"), a)
+        files[f"group_{g}.npy"] = list(a.shape)
+    return {"dir": out_dir, "request": index, "files": files,
+            "rows": "all" if rows is None else f"{rows.size} sampled with seed 0",
+            "what": "the concat output of the last timed request, read from the arena the timed loop wrote"}
 
 
 def cpu_baseline(model, budget_s: float = 20.0, sample_columns: int = 0):
@@ -448,6 +481,12 @@ def main():
                          "recom_examples.patch:264-465) for this path - grow the batch until the average request latency reaches this "
                          "many milliseconds (--threads = its serve_workers, --steps = its num_iterations); s2 / dlrm / ragged; one JSON line")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) normally; gloo only to exercise the N>1 control flow on a 1-GPU box")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side record and check (the --no-* flags above switch single ones off); a plain run "
+                         "only sets up, warms up, times the --steps requests and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the concat output the last timed request left in its arena as DIR/group_<g>.npy "
+                         "(float32; a fixed, seeded row sample beyond 64 MB in all).  Give a DIR outside the repository")
     args = ap.parse_args()
 
     # `python bench.py --gpus N` without a launcher: start the N ranks here (one process per GPU, torch.distributed.run
@@ -484,8 +523,8 @@ def main():
     if args.sla_ms > 0:
         # the reference's other harness: the pressure test (recom_amd.harness.sla_throughput_search); N = 1 only
         from recom_amd.harness import sla_throughput_search
-        if world != 1 or args.workload not in ("s2", "dlrm", "ragged"):
-            print("bench.py --sla-ms: one GPU; --workload s2 | dlrm | ragged", file=sys.stderr)
+        if world != 1 or args.workload not in ("s2", "dlrm", "ragged") or args.dump_outputs:
+            print("bench.py --sla-ms: one GPU; --workload s2 | dlrm | ragged; no --dump-outputs", file=sys.stderr)
             sys.exit(2)
         make = {"s2": lambda b: synth.model_s2(columns=args.columns or 1000, batch=b, **({'vocab': args.vocab} if args.vocab else {})),
                 "dlrm": lambda b: synth.model_dlrm(batch=b),
@@ -553,6 +592,12 @@ def main():
             dist.destroy_process_group()
         sys.exit(2)
     if placement.mode != REPLICATE:
+        if args.dump_outputs:
+            if rank == 0:
+                print("bench.py: --dump-outputs covers the replicated serving line, not sharded tables", file=sys.stderr)
+            if dist:
+                dist.destroy_process_group()
+            sys.exit(2)
         from recom_amd.shard import bench_sharded
         rec = bench_sharded(args, model, placement, rank, world, local_rank, dist)
         if rank == 0:
@@ -564,11 +609,16 @@ def main():
     h = ServingHarness(model, device=local_rank, n_requests=args.requests, arena_ring=args.arena_ring, n_threads=args.threads,
                        seed0=1000 * rank)
     bytes_alg = h.algorithmic_bytes()
-    # a wrong kernel is not timed: every resident request is served once and compared with the closed-form tables (no
-    # oracle: recom_amd.harness.verify_resident); this also reads every request blob once before the warm-up
-    verified = h.verify_resident() if not args.no_verify else {"checked": 0, "note": "--no-verify"}
+    # --full: every resident request is served once and compared with the closed-form tables before anything is timed (no
+    # oracle: recom_amd.harness.verify_resident; a wrong kernel is refused there).  A plain run skips the check and says so
+    # in `verified`
+    if args.full and not args.no_verify:
+        verified = h.verify_resident()
+    else:
+        verified = {"checked": 0, "note": "--no-verify" if args.no_verify else "checked with --full only"}
 
-    h.run(max(args.warmup, 1))                       # W untimed warm-up steps
+    issued = max(args.warmup, 1)
+    h.run(issued)                                    # W untimed warm-up steps
     # ... and, whatever --warmup says, an untimed pre-warm of >= PREWARM_S of the same requests: the reference's protocol
     # discards >= 10 iterations (recom_examples.patch:110, 186-207) so that clocks, queues and TLBs are those of a serving
     # process; a 5-request warm-up in front of a 0.6-ms region measured the clock ramp (r05: 31.2 us by the driver's
@@ -577,11 +627,10 @@ def main():
     while time.perf_counter() < t_end:
         h.run(PREWARM_CHUNK)
         extra_warmup += PREWARM_CHUNK
-    # exactly K timed steps, REPEATS times, each repeat bracketed by barrier + synchronize on both sides and reduced to the
-    # MAX over ranks; `ms_per_step` / `value` = the MEDIAN repeat, min / max beside it
-    repeats = []
-    # (short regions are noisy — one 20-request region in five came out at 32 us on a fresh box: more of them)
-    for _ in range(REPEATS if args.steps >= 200 else 2 * REPEATS - 1):
+    issued += extra_warmup
+
+    def timed_region():
+        """Exactly K timed steps, bracketed by barrier + synchronize on both sides and reduced to the MAX over ranks."""
         if dist:
             dist.barrier()
         torch.cuda.synchronize()
@@ -595,20 +644,39 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.dist_backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        repeats.append((elapsed, dev_ms, wall_ms))
-    repeats_in_order = list(repeats)
-    repeats.sort()
-    elapsed, _, wall_ms = repeats[len(repeats) // 2]           # ms_per_step / value: the repeat with the median wall time
-    dev_ms = sorted(r[1] for r in repeats)[len(repeats) // 2]   # roofline: the median HIP-event time of the repeats
+        return elapsed, dev_ms, wall_ms
+    # `ms_per_step` / `value` / roofline: ONE region of exactly --steps requests
+    elapsed, dev_ms, wall_ms = timed_region()
+    issued += args.steps
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        # read from the arena before anything else runs; worker 0 serves request k % n_requests as its k-th
+        # (fcp_harness.hip: issue), so the last timed step served this one
+        outputs = dump_outputs(h, (issued - 1) % args.requests, args.dump_outputs)
 
-    # latency percentiles: separate pass with one HIP event pair per request, at least 200 samples
-    # whatever --steps is
-    _, _, it = h.run(min(max(args.steps, 200), 500), per_request=True)
+    repeats = None
+    if args.full:
+        # the same K steps timed again, so that the spread of the region is on record (short regions are noisy — one
+        # 20-request region in five came out at 32 us on a fresh box: more of them); the headline stays the first region
+        regions = [(elapsed, dev_ms, wall_ms)] + [timed_region() for _ in range((REPEATS if args.steps >= 200 else 2 * REPEATS - 1) - 1)]
+        per_step = sorted(r[0] * 1e3 / (args.steps * args.threads) for r in regions)
+        repeats = {"n": len(regions), "reported": "the first (the headline region)", "ms_per_step_min": per_step[0],
+                   "ms_per_step_max": per_step[-1], "ms_per_step_median": per_step[len(per_step) // 2], "ms_per_step_all": per_step,
+                   "kernel_avg_us_all": sorted(r[1] * 1e3 / args.steps for r in regions),
+                   "kernel_avg_us_in_time_order": [r[1] * 1e3 / args.steps for r in regions],
+                   "what": f"exactly --steps requests timed {len(regions)} times (barrier + synchronize on both sides of each, max over "
+                           f"ranks) behind >= {PREWARM_S} s of untimed requests; ms_per_step / value / roofline are the first"}
+
+    it = None
+    if args.full:
+        # latency percentiles: separate pass with one HIP event pair per request, at least 200 samples
+        # whatever --steps is
+        _, _, it = h.run(min(max(args.steps, 200), 500), per_request=True)
     # What the output costs by reuse distance of the arena: the same loop over rings of 1 / 2 / 6 arenas,
     # the library choosing its store policy per request (plain stores into an arena one of the plan's last two requests wrote,
     # nt / sc1 nt otherwise: store_policy_for, fcp_process.hip).  Extra field only; `value` is the ring --arena-ring names.
     arena_reuse = None
-    if args.threads == 1 and not dist and not args.no_overlap:
+    if args.full and args.threads == 1 and not dist and not args.no_overlap:
         arena_reuse = {"what": "stream order, one serve worker, HIP-event us per request by the number of output arenas the loop rotates "
                                "through; 1 = TF's allocate_output handing a one-thread serving loop the block it just freed; the library "
                                "picks the store policy from the arena's reuse (profiles/r06_arena_reuse_store_policy.txt)",
@@ -627,7 +695,7 @@ def main():
     # overlapped serving (the reference harness' serve_workers): independent requests on
     # 3 streams hide each launch's ramp / tail behind its neighbours.  Extra field only.
     overlap = None
-    if args.threads == 1 and not dist and not args.no_overlap:
+    if args.full and args.threads == 1 and not dist and not args.no_overlap:
         # its own floor whatever --steps / --warmup are: the workers need some tens of requests each to reach
         # steady overlap (round 1: the driver's --steps 20 gave 6 requests per worker and no overlap).  The
         # reference sweeps its serve workers too (AE/build_and_run.py:73-80: 2 / 4 / 8); how many streams overlap
@@ -654,7 +722,7 @@ def main():
     # streams (fcp_plan_set_private_streams), the consumer of each request (fcp_result_wait + a reader kernel on the
     # caller's stream, standing for Addons>ConcatOutputs) enqueued `lanes - 1` requests behind it.  Extra field only.
     single_caller = None
-    if args.threads == 1 and not dist and not args.no_overlap:
+    if args.full and args.threads == 1 and not dist and not args.no_overlap:
         try:
             sweep = {}
             sc_warm, sc_steps = max(args.warmup, 100), max(args.steps, 1200)
@@ -758,13 +826,6 @@ def main():
         # hipDeviceSynchronize): host wall time of the region minus the HIP-event time of its K requests; ~30 us, i.e. 5 % of
         # a 20-request region (0.55 ms) and 0.05 % of the default 2000-request one
         "bracket_overhead_us": (elapsed - dev_ms * 1e-3) * 1e6,
-        "repeats": {"n": len(repeats), "reported": "median", "ms_per_step_min": repeats[0][0] * 1e3 / steps_total,
-                    "ms_per_step_max": repeats[-1][0] * 1e3 / steps_total,
-                    "ms_per_step_all": [r[0] * 1e3 / steps_total for r in repeats],
-                    "kernel_avg_us_all": [r[1] * 1e3 / args.steps for r in repeats],
-                    "kernel_avg_us_in_time_order": [r[1] * 1e3 / args.steps for r in repeats_in_order],
-                    "what": f"exactly --steps requests timed {len(repeats)} times (barrier + synchronize on both sides of each, max over "
-                            f"ranks) behind >= {PREWARM_S} s of untimed requests; ms_per_step / value / roofline are the median repeat"},
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": f"{model.name}: {model.description}", "batch": batch,
                    "columns": model.spec.n_columns, "table_bytes": model.table_bytes(),
@@ -773,10 +834,16 @@ def main():
                    "serve_workers": args.threads, "arena_ring": args.arena_ring},
         "requests_per_s": value / batch,
         "verified": verified,
-        "p50_latency_ms": float(np.percentile(it, 50)), "p95_latency_ms": float(np.percentile(it, 95)),
-        "latency_scope": f"device latency of one request (HIP event pair around it on the launch stream, {len(it)} samples), "
-                         "inputs resident in HBM; host packing + H2D are reported separately (profiles/HISTORY.md, PCIe-inclusive rate; DESIGN.md section 5)",
     }
+    if repeats:
+        rec["repeats"] = repeats
+    if it is not None:
+        rec.update({
+            "p50_latency_ms": float(np.percentile(it, 50)), "p95_latency_ms": float(np.percentile(it, 95)),
+            "latency_scope": f"device latency of one request (HIP event pair around it on the launch stream, {len(it)} samples), "
+                             "inputs resident in HBM; host packing + H2D are reported separately (profiles/HISTORY.md, PCIe-inclusive rate; DESIGN.md section 5)"})
+    if outputs:
+        rec["outputs"] = outputs
     if rank == 0:
         achieved = bytes_alg["total"] / (dev_ms_per_req * 1e-3) / 1e9
         # (the PMC record of RAGGED is for the default segment encoding: SparseTensor indices, pre-pass included)
@@ -793,8 +860,9 @@ def main():
             "read_only_frac": bytes_alg["read"] / (dev_ms_per_req * 1e-3) / 1e9 / HBM_PEAK_GBS,
         }
         try:
-            rec["roofline"]["measured_copy_peak_GBs"] = copy_probe() / 1e9
-            rec["roofline"]["access_mix"] = access_mix_floor(model, h, bytes_alg, dev_ms_per_req * 1e3)
+            if args.full:
+                rec["roofline"]["measured_copy_peak_GBs"] = copy_probe() / 1e9
+                rec["roofline"]["access_mix"] = access_mix_floor(model, h, bytes_alg, dev_ms_per_req * 1e3)
         except Exception as e:
             rec["roofline"]["access_mix"] = {"error": side_error(e)}
         if arena_reuse:
@@ -819,7 +887,7 @@ def main():
             single_caller["inputs_ready_back_to_back"]["frac_of_peak"] = (
                 bytes_alg["total"] / (single_caller["inputs_ready_back_to_back"]["us_per_request"] * 1e-6) / 1e9 / HBM_PEAK_GBS)
             rec["single_caller_stream"] = single_caller
-        if args.staged and raw_model is not model:
+        if args.full and args.staged and raw_model is not model:
             # the same requests resident AS DELIVERED (int64 ids, SparseTensor indices; the segment-offset pre-pass runs on the
             # device): the like-for-like figure of rounds 1-2, in the same record
             hd = ServingHarness(raw_model, device=local_rank, n_requests=args.requests, arena_ring=args.arena_ring, n_threads=1, tables=h.tables,
@@ -832,7 +900,7 @@ def main():
                                    "what": "the same requests resident as the graph's tensors are (int64 ids, SparseTensor indices), "
                                            "segment-offset pre-pass on the device; `bench.py --as-delivered` makes this the headline"}
             hd.close()
-        if args.workload == "ragged" and args.seg == "indices" and not args.staged:
+        if args.full and args.workload == "ragged" and args.seg == "indices" and not args.staged:
             # the same requests in the form the rewritten graph's Addons>ConcatInputs leaves in HBM (plan-file stage section: ids
             # int32, SparseTensor indices -> row offsets while packing): no pre-pass, no search — and what that conversion costs
             # the HOST per request, stated right beside it (one thread, like the TF op; pack pool of 4 / 8 / 16 threads)
@@ -851,16 +919,16 @@ def main():
             hs2.close()
             if "FCP_LIB_DIR" not in os.environ:
                 rec["staged"]["staging"] = host_staging_cost(raw_model)
-        if args.staged and "FCP_LIB_DIR" not in os.environ:
+        if args.full and args.staged and "FCP_LIB_DIR" not in os.environ:
             rec["staging"] = host_staging_cost(raw_model)
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
             try:
                 rec["cpu_baseline"] = cpu_baseline(model)
             except Exception as e:                   # (e.g. a host that cannot hold the tables and cannot even sample them)
                 rec["cpu_baseline"] = {"value": None, "unit": "inferences/s", "cores": 0, "kind": "port", "sample": "failed",
                                        "error": side_error(e)}
     h.close()
-    if world > 1 and args.workload == "s2" and not os.environ.get("FCP_BENCH_NO_SHARDED_RECORD"):
+    if args.full and world > 1 and args.workload == "s2" and not os.environ.get("FCP_BENCH_NO_SHARDED_RECORD"):
         # The default multi-GPU line is replicas (S2's 120 GB fit one GPU: no collective); so that a scaling run on a multi-GPU
         # node still measures the one exchange this path has, BASELINE configs[4]'s row-sharded step runs on the same ranks for
         # <= 10 s afterwards and rides along as `sharded` (every rank takes part; rank 0 reports)
@@ -907,7 +975,7 @@ def main():
             os._exit(0)
         h = None
     if rank == 0:
-        if args.workload == "s2" and world == 1 and args.ids == "uniform" and not args.no_pcie and not args.no_cpu_baseline and not args.batch and not args.columns:
+        if args.full and args.workload == "s2" and world == 1 and args.ids == "uniform" and not args.no_pcie and not args.no_cpu_baseline and not args.batch and not args.columns:
             del h
             torch.cuda.empty_cache()
             rec["pcie_inclusive"] = pcie_inclusive()

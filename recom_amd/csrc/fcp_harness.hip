@@ -78,8 +78,16 @@ struct fcp_harness {
   long issued = 0; // requests issued so far per worker (variant rotation)
   int device = 0;  // the device the streams and arenas were created on: a new host thread starts on device 0, so every
                    // worker thread selects it first (rank r of a multi-GPU node serves device r)
+  // per worker: where the last request of the latest fcp_harness_run left its concat matrices (in its ring arena)
+  struct LastOut {
+    std::vector<void *> group_ptrs;
+    std::vector<int32_t> group_shapes;
+    bool valid = false;
+  };
+  std::vector<LastOut> last;
 
-  void issue(int t, long begin, int count) {
+  // request k = record_at (if in range) also reports where its output lies: one result per call, not per request
+  void issue(int t, long begin, int count, long record_at = -1) {
     const int nv = (int)variants.size();
     for (long k = begin; k < begin + count; ++k) {
       fcp_process_args_t a = variants[(size_t)((k + t) % nv)];
@@ -88,12 +96,21 @@ struct fcp_harness {
       a.malloc_buff_ctx = &rings[t];
       a.malloc_temp = nullptr;
       a.malloc_temp_ctx = nullptr;
-      const int rc = fcp_process_feature_columns(plan, &a, nullptr);
+      fcp_process_result_t r = {};
+      if (k == record_at) {
+        r.group_ptrs = last[t].group_ptrs.data();
+        r.group_shapes = last[t].group_shapes.data();
+      }
+      const int rc = fcp_process_feature_columns(plan, &a, k == record_at ? &r : nullptr);
       if (rc) {
         status[t] = rc;
         return;
       }
+      if (k == record_at) last[t].valid = true;
     }
+  }
+  void forget_last() {
+    for (auto &l : last) l.valid = false;
   }
 };
 
@@ -121,6 +138,16 @@ int fcp_harness_create(fcp_plan_t *plan, const fcp_process_args_t *variants, int
   h->rings.resize(n_threads);
   h->streams.resize(n_threads);
   h->status.assign(n_threads, FCP_OK);
+  int32_t n_groups = 0;
+  if (int rc = fcp_plan_counts(plan, nullptr, &n_groups, nullptr, nullptr, nullptr)) {
+    delete h;
+    return rc;
+  }
+  h->last.resize(n_threads);
+  for (auto &l : h->last) {
+    l.group_ptrs.assign((size_t)n_groups, nullptr);
+    l.group_shapes.assign(2 * (size_t)n_groups, 0);
+  }
   for (int t = 0; t < n_threads; ++t) {
     H_TRY(hipStreamCreateWithFlags(&h->streams[t], hipStreamNonBlocking));
     h->rings[t].bytes = (size_t)arena_bytes;
@@ -148,6 +175,8 @@ int fcp_harness_run(fcp_harness *h, int steps, double *wall_ms, float *dev_ms, f
   OnDevice on(h->device);
   const int n_threads = (int)h->streams.size();
   const long begin = h->issued;
+  const long last_k = begin + steps - 1;
+  h->forget_last();
   std::vector<hipEvent_t> ev;
   if (iter_ms) {
     ev.resize(2 * (size_t)steps);
@@ -156,19 +185,19 @@ int fcp_harness_run(fcp_harness *h, int steps, double *wall_ms, float *dev_ms, f
   const auto t0 = std::chrono::steady_clock::now();
   H_TRY(hipEventRecord(h->e0, h->streams[0]));
   std::vector<std::thread> workers;
-  for (int t = 1; t < n_threads; ++t) workers.emplace_back([h, t, begin, steps] {
+  for (int t = 1; t < n_threads; ++t) workers.emplace_back([h, t, begin, steps, last_k] {
       (void)hipSetDevice(h->device);
-      h->issue(t, begin, steps);
+      h->issue(t, begin, steps, last_k);
     });
   hipError_t worker0 = hipSuccess; // no early return while the other workers run: a joinable std::thread must be joined
   if (iter_ms) {
     for (int k = 0; k < steps && worker0 == hipSuccess; ++k) {
       worker0 = hipEventRecord(ev[2 * k], h->streams[0]);
-      h->issue(0, begin + k, 1);
+      h->issue(0, begin + k, 1, last_k);
       if (worker0 == hipSuccess) worker0 = hipEventRecord(ev[2 * k + 1], h->streams[0]);
     }
   } else {
-    h->issue(0, begin, steps);
+    h->issue(0, begin, steps, last_k);
   }
   for (auto &w : workers) w.join();
   H_TRY(worker0);
@@ -197,6 +226,7 @@ int fcp_harness_run(fcp_harness *h, int steps, double *wall_ms, float *dev_ms, f
 int fcp_harness_run_graph(fcp_harness *h, int steps, int group, double *wall_ms, float *dev_ms) {
   if (!h || group < 1 || steps < group || steps % group) return FCP_ERR_INVALID_ARGUMENT;
   OnDevice on(h->device);
+  h->forget_last();
   hipStream_t s = h->streams[0];
   h->issue(0, 0, group); // descriptors of the captured variants are now resident
   H_TRY(hipStreamSynchronize(s));
@@ -248,6 +278,7 @@ int fcp_harness_run_private_threads(fcp_harness *h, int steps, int depth, int th
   if (!h || steps < 1 || depth < 1 || threads < 1 || threads > (int)h->rings.size() || depth > (int)h->rings[0].bufs.size())
     return FCP_ERR_INVALID_ARGUMENT;
   OnDevice on(h->device);
+  h->forget_last();
   hipStream_t caller = h->streams[0];
   static float *sink = nullptr;
   if (!sink) H_TRY(hipMalloc(&sink, sizeof(float)));
@@ -333,6 +364,27 @@ int fcp_harness_run_private(fcp_harness *h, int steps, int depth, double *wall_m
 }
 
 // worker `t`'s stream (what fcp_harness_run_private issues on is worker 0's): for probes that need the caller's stream
+// The concat matrices worker `t` wrote for the LAST request of the latest fcp_harness_run, copied out of the ring arena that
+// request was given — what the timed loop itself computed, not a recomputation.  group_shapes: int32[2 * n_groups] (rows,
+// width per group); host_out: n_groups host float buffers of rows * width elements each, or NULL for the shapes alone.
+// FCP_LAYOUT_CONCAT plans; after fcp_harness_run has returned (its streams are synchronised).
+int fcp_harness_last_output(fcp_harness *h, int t, int32_t n_groups, int32_t *group_shapes, float **host_out) {
+  if (!h || t < 0 || t >= (int)h->last.size() || !group_shapes || n_groups != (int32_t)h->last[t].group_ptrs.size())
+    return FCP_ERR_INVALID_ARGUMENT;
+  const auto &l = h->last[t];
+  if (!l.valid) return FCP_ERR_INVALID_ARGUMENT;
+  for (int32_t g = 0; g < n_groups; ++g)
+    if (!l.group_ptrs[g]) return FCP_ERR_INVALID_ARGUMENT; // not a concat layout
+  std::copy(l.group_shapes.begin(), l.group_shapes.end(), group_shapes);
+  if (!host_out) return FCP_OK;
+  OnDevice on(h->device);
+  for (int32_t g = 0; g < n_groups; ++g) {
+    const size_t bytes = (size_t)l.group_shapes[2 * g] * (size_t)l.group_shapes[2 * g + 1] * sizeof(float);
+    if (bytes) H_TRY(hipMemcpy(host_out[g], l.group_ptrs[g], bytes, hipMemcpyDeviceToHost));
+  }
+  return FCP_OK;
+}
+
 void *fcp_harness_stream(fcp_harness *h, int t) { return (h && t >= 0 && t < (int)h->streams.size()) ? h->streams[t] : nullptr; }
 
 int fcp_harness_destroy(fcp_harness *h) {

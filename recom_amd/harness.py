@@ -46,6 +46,8 @@ def load() -> C.CDLL:
             H.fcp_harness_run_private.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_float)]
         if hasattr(H, "fcp_harness_run_private_threads"):
             H.fcp_harness_run_private_threads.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_float)]
+        if hasattr(H, "fcp_harness_last_output"):
+            H.fcp_harness_last_output.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p)]
         H.fcp_harness_copy_probe.argtypes = [C.c_size_t, C.c_int, C.POINTER(C.c_float)]
         H.fcp_harness_gather_probe.argtypes = [C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
                                                C.POINTER(C.c_double)]
@@ -103,6 +105,17 @@ class ServingHarness:
         _lib.check(self.H.fcp_harness_run(self.handle, steps, C.byref(wall), C.byref(dev),
                                           None if it is None else it.ctypes.data), "fcp_harness_run")
         return wall.value, dev.value, it
+
+    def last_output(self, worker: int = 0) -> List[np.ndarray]:
+        """The concat matrices (float32 [rows, width] per group) that worker ``worker`` wrote for the last request of the
+        latest ``run`` — copied out of the ring arena that request was given, not computed again."""
+        g = self.spec.n_groups
+        shapes = (C.c_int32 * (2 * g))()
+        _lib.check(self.H.fcp_harness_last_output(self.handle, worker, g, shapes, None), "fcp_harness_last_output")
+        out = [np.empty((shapes[2 * k], shapes[2 * k + 1]), np.float32) for k in range(g)]
+        ptrs = (C.c_void_p * g)(*[a.ctypes.data for a in out])
+        _lib.check(self.H.fcp_harness_last_output(self.handle, worker, g, shapes, ptrs), "fcp_harness_last_output")
+        return out
 
     def caller_stream(self, worker: int = 0) -> int:
         """The HIP stream worker ``worker`` issues on (``run_private``: worker 0's is the caller's stream)."""

@@ -3,7 +3,7 @@
 # queues (GPU_MAX_HW_QUEUES), and the sc1-nt store policy across all workloads.
 : "${GRAFT_REPO_ROOT:?run on a gpurun box (or export GRAFT_REPO_ROOT)}"
 cd "$GRAFT_REPO_ROOT" || exit 1
-ov() { python3 bench.py --no-cpu-baseline --steps 600 --warmup 100 "$@" 2>/dev/null | python3 -c "
+ov() { python3 bench.py --full --no-cpu-baseline --steps 600 --warmup 100 "$@" 2>/dev/null | python3 -c "
 import json,sys
 r=json.loads(sys.stdin.readline()); o=r.get('overlapped_serving') or {}
 print('%.2f us single, 3 workers %.2f us' % (r['roofline']['kernel_avg_us'], o.get('us_per_request', float('nan'))))"; }

@@ -11,7 +11,7 @@ for w in s2 dlrm f; do
     FCP_STORE_PLAIN_REUSE=$mode python3 scripts/r06_arena_reuse.py --workload $w --policy "plain_reuse=$mode" 2>>"$O/err.log"
   done
 done | tee "$O/cells2.jsonl"
-python bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver_steps20.json" 2> "$O/bench_driver.err"
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver_steps20.json" 2> "$O/bench_driver.err"
 tail -c 1500 "$O/bench_driver.err"
 python3 - <<'PY'
 import json,os

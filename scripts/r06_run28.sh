@@ -3,7 +3,7 @@
 : "${GRAFT_REPO_ROOT:?}"
 cd "$GRAFT_REPO_ROOT" || exit 1
 O="$GRAFT_REPO_ROOT/gpurun_out/r06_run28"; mkdir -p "$O"
-python bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver.json" 2>"$O/bench_driver.err"; echo "bench rc=$?"
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/bench_driver.json" 2>"$O/bench_driver.err"; echo "bench rc=$?"
 python3 -c "
 import json; r=json.loads(open('$O/bench_driver.json').readline()); ro=r['roofline']
 print('driver:', round(r['ms_per_step']*1e3,2), round(ro['kernel_avg_us'],2), round(ro['frac'],3), ro['traffic'])

@@ -12,7 +12,7 @@ done | tee "$O/cells_after_nt_fix.jsonl" | python3 -c "
 import json,sys
 for l in sys.stdin:
     r=json.loads(l); print(r['workload'], {k:r[k]['plain_us'] for k in r if k.startswith('ring_')})"
-one() { python3 bench.py --no-cpu-baseline --no-pcie --no-overlap "$@" 2>/dev/null | python3 -c "
+one() { python3 bench.py --full --no-cpu-baseline --no-pcie --no-overlap "$@" 2>/dev/null | python3 -c "
 import json,sys
 r=json.loads(sys.stdin.readline())
 print('ms_per_step %.2f us kernel %.2f p50 %.2f repeats %s' % (r['ms_per_step']*1e3, r['roofline']['kernel_avg_us'], r['p50_latency_ms']*1e3, [round(x*1e3,2) for x in r['repeats']['ms_per_step_all']]))"; }

@@ -4,12 +4,12 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 O=$GRAFT_REPO_ROOT/gpurun_out/refresh
 mkdir -p $O
-python bench.py > $O/r01_bench_s2.json 2> $O/bench_s2.err
-python bench.py --ids zipf --no-cpu-baseline > $O/r01_bench_s2_zipf.json 2>/dev/null
-python bench.py --workload ragged > $O/r01_bench_ragged.json 2>/dev/null
-python bench.py --workload dlrm > $O/r01_bench_dlrm.json 2>/dev/null
-python bench.py --workload e > $O/r01_bench_ae_model_e.json 2>/dev/null
-python bench.py --workload f > $O/r01_bench_ae_model_f.json 2>/dev/null
+python bench.py --full > $O/r01_bench_s2.json 2> $O/bench_s2.err
+python bench.py --full --ids zipf --no-cpu-baseline > $O/r01_bench_s2_zipf.json 2>/dev/null
+python bench.py --full --workload ragged > $O/r01_bench_ragged.json 2>/dev/null
+python bench.py --full --workload dlrm > $O/r01_bench_dlrm.json 2>/dev/null
+python bench.py --full --workload e > $O/r01_bench_ae_model_e.json 2>/dev/null
+python bench.py --full --workload f > $O/r01_bench_ae_model_f.json 2>/dev/null
 python scripts/ae_split.py e 1000 > $O/r01_ae_split.txt 2>/dev/null
 python scripts/ae_split.py f 1000 >> $O/r01_ae_split.txt 2>/dev/null
 python scripts/seg_encoding.py > $O/r01_ragged_segment_encodings.txt 2>/dev/null

@@ -11,14 +11,14 @@ bash scripts/pmc_py.sh refresh2_ragged --workload ragged > $O/r02_ragged_pmc.txt
 bash scripts/pmc_py.sh refresh2_e --workload e > $O/r02_ae_model_e_pmc.txt 2>&1
 python3 scripts/traffic_from_pmc.py $O > /dev/null && cp profiles/traffic.json $O/traffic.json
 # the driver's invocation (few steps) and the default one
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r02_bench_s2_driver_steps20.json 2> $O/bench_s2_driver.err
-python bench.py > $O/r02_bench_s2.json 2> $O/bench_s2.err
-python bench.py --ids zipf --no-cpu-baseline > $O/r02_bench_s2_zipf.json 2>/dev/null
-python bench.py --workload ragged > $O/r02_bench_ragged.json 2>/dev/null
-python bench.py --workload ragged --seg csr --no-cpu-baseline > $O/r02_bench_ragged_csr.json 2>/dev/null
-python bench.py --workload dlrm > $O/r02_bench_dlrm.json 2>/dev/null
-python bench.py --workload e > $O/r02_bench_ae_model_e.json 2>/dev/null
-python bench.py --workload f > $O/r02_bench_ae_model_f.json 2>/dev/null
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r02_bench_s2_driver_steps20.json 2> $O/bench_s2_driver.err
+python bench.py --full > $O/r02_bench_s2.json 2> $O/bench_s2.err
+python bench.py --full --ids zipf --no-cpu-baseline > $O/r02_bench_s2_zipf.json 2>/dev/null
+python bench.py --full --workload ragged > $O/r02_bench_ragged.json 2>/dev/null
+python bench.py --full --workload ragged --seg csr --no-cpu-baseline > $O/r02_bench_ragged_csr.json 2>/dev/null
+python bench.py --full --workload dlrm > $O/r02_bench_dlrm.json 2>/dev/null
+python bench.py --full --workload e > $O/r02_bench_ae_model_e.json 2>/dev/null
+python bench.py --full --workload f > $O/r02_bench_ae_model_f.json 2>/dev/null
 ./build/stamps/fcp_bench --steps 200 | tail -24 > $O/stamps_s2.txt
 ./build/stamps/fcp_bench --columns 980 --vocab 101 --bucketize-every 1 --dim 8 --steps 200 | tail -12 > $O/stamps_elike.txt
 ./build/ramp_probe 3776 300 > $O/ramp_probe.txt 2>&1

@@ -12,15 +12,15 @@ bash scripts/pmc_py.sh refresh3_ragged_ad --workload ragged --as-delivered > $O/
 bash scripts/pmc_py.sh refresh3_e --workload e > $O/r03_ae_model_e_pmc.txt 2>&1
 python3 scripts/traffic_from_pmc.py $O r03 > /dev/null && cp profiles/traffic.json $O/traffic.json
 # the driver's invocation (few steps) and the default one
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r03_bench_s2_driver_steps20.json 2> $O/bench_s2_driver.err
-python bench.py > $O/r03_bench_s2.json 2> $O/bench_s2.err
-python bench.py --ids zipf --no-cpu-baseline > $O/r03_bench_s2_zipf.json 2>/dev/null
-python bench.py --workload ragged > $O/r03_bench_ragged.json 2>/dev/null
-python bench.py --workload ragged --as-delivered --no-cpu-baseline > $O/r03_bench_ragged_as_delivered.json 2>/dev/null
-python bench.py --workload ragged --seg csr --no-cpu-baseline > $O/r03_bench_ragged_csr.json 2>/dev/null
-python bench.py --workload dlrm > $O/r03_bench_dlrm.json 2>/dev/null
-python bench.py --workload e > $O/r03_bench_ae_model_e.json 2>/dev/null
-python bench.py --workload f > $O/r03_bench_ae_model_f.json 2>/dev/null
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r03_bench_s2_driver_steps20.json 2> $O/bench_s2_driver.err
+python bench.py --full > $O/r03_bench_s2.json 2> $O/bench_s2.err
+python bench.py --full --ids zipf --no-cpu-baseline > $O/r03_bench_s2_zipf.json 2>/dev/null
+python bench.py --full --workload ragged > $O/r03_bench_ragged.json 2>/dev/null
+python bench.py --full --workload ragged --as-delivered --no-cpu-baseline > $O/r03_bench_ragged_as_delivered.json 2>/dev/null
+python bench.py --full --workload ragged --seg csr --no-cpu-baseline > $O/r03_bench_ragged_csr.json 2>/dev/null
+python bench.py --full --workload dlrm > $O/r03_bench_dlrm.json 2>/dev/null
+python bench.py --full --workload e > $O/r03_bench_ae_model_e.json 2>/dev/null
+python bench.py --full --workload f > $O/r03_bench_ae_model_f.json 2>/dev/null
 # kernel traces (single stream: --no-overlap keeps every traced kernel alone on its stream)
 for w in s2 ragged "ragged --as-delivered" e; do
   tag=$(echo $w | tr -d ' -')

@@ -14,16 +14,16 @@ bash scripts/pmc_py.sh refresh4_e --workload e > $O/r04_ae_model_e_pmc.txt 2>&1
 python3 scripts/traffic_from_pmc.py $O r04 > /dev/null || fail "traffic_from_pmc.py"
 cp profiles/traffic.json $O/traffic.json
 # the driver's invocation (few steps) and the default one
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r04_bench_s2_driver_steps20.json 2> $O/bench_s2_driver.err
-python bench.py > $O/r04_bench_s2.json 2> $O/bench_s2.err
-python bench.py --ids zipf --no-cpu-baseline > $O/r04_bench_s2_zipf.json 2>/dev/null
-python bench.py --workload ragged > $O/r04_bench_ragged.json 2>/dev/null
-python bench.py --workload ragged --as-delivered --no-cpu-baseline > $O/r04_bench_ragged_as_delivered.json 2>/dev/null
-python bench.py --workload ragged --seg csr --no-cpu-baseline > $O/r04_bench_ragged_csr.json 2>/dev/null
-python bench.py --workload dlrm > $O/r04_bench_dlrm.json 2>/dev/null
-python bench.py --workload e > $O/r04_bench_ae_model_e.json 2>/dev/null
-python bench.py --workload f > $O/r04_bench_ae_model_f.json 2>/dev/null
-python bench.py --workload e --requests 64 --no-cpu-baseline --no-overlap > $O/r04_bench_ae_model_e_64_shapes.json 2>/dev/null
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r04_bench_s2_driver_steps20.json 2> $O/bench_s2_driver.err
+python bench.py --full > $O/r04_bench_s2.json 2> $O/bench_s2.err
+python bench.py --full --ids zipf --no-cpu-baseline > $O/r04_bench_s2_zipf.json 2>/dev/null
+python bench.py --full --workload ragged > $O/r04_bench_ragged.json 2>/dev/null
+python bench.py --full --workload ragged --as-delivered --no-cpu-baseline > $O/r04_bench_ragged_as_delivered.json 2>/dev/null
+python bench.py --full --workload ragged --seg csr --no-cpu-baseline > $O/r04_bench_ragged_csr.json 2>/dev/null
+python bench.py --full --workload dlrm > $O/r04_bench_dlrm.json 2>/dev/null
+python bench.py --full --workload e > $O/r04_bench_ae_model_e.json 2>/dev/null
+python bench.py --full --workload f > $O/r04_bench_ae_model_f.json 2>/dev/null
+python bench.py --full --workload e --requests 64 --no-cpu-baseline --no-overlap > $O/r04_bench_ae_model_e_64_shapes.json 2>/dev/null
 # kernel traces (single stream: --no-overlap keeps every traced kernel alone on its stream); tag = file name, explicit
 trace() { # trace <tag> <bench args...>
   local tag=$1; shift

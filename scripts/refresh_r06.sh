@@ -17,16 +17,16 @@ bash scripts/pmc_py.sh refresh6_e --workload e > "$O/r06_ae_model_e_pmc.txt" 2>&
 python3 scripts/traffic_from_pmc.py "$O" r06 > /dev/null || fail "traffic_from_pmc.py"
 cp profiles/traffic.json "$O/traffic.json"
 # the driver's invocation (few steps) and the default one
-python bench.py --gpus 1 --steps 20 --warmup 5 > "$O/r06_bench_s2_driver_steps20.json" 2> "$O/bench_s2_driver.err"
-python bench.py > "$O/r06_bench_s2.json" 2> "$O/bench_s2.err"
-python bench.py --arena-ring 6 --no-cpu-baseline --no-pcie --no-overlap > "$O/r06_bench_s2_ring6.json" 2>/dev/null
-python bench.py --ids zipf --no-cpu-baseline > "$O/r06_bench_s2_zipf.json" 2>/dev/null
-python bench.py --workload ragged > "$O/r06_bench_ragged.json" 2>/dev/null
-python bench.py --workload ragged --staged --no-cpu-baseline > "$O/r06_bench_ragged_staged.json" 2>/dev/null
-python bench.py --workload ragged --seg csr --no-cpu-baseline > "$O/r06_bench_ragged_csr.json" 2>/dev/null
-python bench.py --workload dlrm > "$O/r06_bench_dlrm.json" 2>/dev/null
-python bench.py --workload e > "$O/r06_bench_ae_model_e.json" 2>/dev/null
-python bench.py --workload f > "$O/r06_bench_ae_model_f.json" 2>/dev/null
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/r06_bench_s2_driver_steps20.json" 2> "$O/bench_s2_driver.err"
+python bench.py --full > "$O/r06_bench_s2.json" 2> "$O/bench_s2.err"
+python bench.py --full --arena-ring 6 --no-cpu-baseline --no-pcie --no-overlap > "$O/r06_bench_s2_ring6.json" 2>/dev/null
+python bench.py --full --ids zipf --no-cpu-baseline > "$O/r06_bench_s2_zipf.json" 2>/dev/null
+python bench.py --full --workload ragged > "$O/r06_bench_ragged.json" 2>/dev/null
+python bench.py --full --workload ragged --staged --no-cpu-baseline > "$O/r06_bench_ragged_staged.json" 2>/dev/null
+python bench.py --full --workload ragged --seg csr --no-cpu-baseline > "$O/r06_bench_ragged_csr.json" 2>/dev/null
+python bench.py --full --workload dlrm > "$O/r06_bench_dlrm.json" 2>/dev/null
+python bench.py --full --workload e > "$O/r06_bench_ae_model_e.json" 2>/dev/null
+python bench.py --full --workload f > "$O/r06_bench_ae_model_f.json" 2>/dev/null
 # kernel traces (single stream: --no-overlap keeps every traced kernel alone on its stream)
 trace() { # trace <tag> <bench args...>
   local tag=$1; shift

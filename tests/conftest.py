@@ -22,22 +22,53 @@ def oracle():
     return fcp_oracle.COracle()
 
 
-@pytest.fixture(scope="session")
-def ref_bucketize():
-    """The REFERENCE's own `Bucketize` (cuda_emitter.cc:233-247), compiled from its source where it lies by the recipe
-    oracle/ref_extract.py into oracle/_ref/libref_bucketize.so (built in the container that has /root/reference; the built
-    library travels to the GPU box).  Returns f(boundaries, values) -> int32 bucket ids."""
+def _ref_host_lib():
+    """oracle/_ref/libref_bucketize.so — the REFERENCE's own `Bucketize` and `alignmem`, compiled from its source where it
+    lies by the recipe oracle/ref_extract.py — or None where that source is absent and nothing was built from it."""
     import ctypes as C
     import ref_extract
     if not ref_extract.build():
-        pytest.skip("oracle/_ref/libref_bucketize.so is absent and /root/reference is not here to build it from")
+        return None
     lib = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libref_bucketize.so"))
     lib.ref_bucketize_many.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
     lib.ref_bucketize_max_boundaries.restype = C.c_int
+    lib.ref_alignmem.argtypes = [C.c_int]
+    lib.ref_alignmem.restype = C.c_int
+    return lib
+
+
+@pytest.fixture(scope="session")
+def ref_host_goldens():
+    """tests/golden/ref_host_goldens.npz: what the reference's `Bucketize` and `alignmem` returned for the inputs the tests
+    give them (tests/golden/make_ref_host_goldens.py).  Where the library is built, it must still return exactly that."""
+    z = np.load(os.path.join(ROOT, "tests", "golden", "ref_host_goldens.npz"))
+    g = {"alignmem": z["alignmem"],
+         "bucketize": {(z[k].tobytes(), z[k[:-1] + "x"].tobytes()): z[k[:-1] + "want"] for k in z.files if k.endswith("_b")}}
+    lib = _ref_host_lib()
+    if lib is not None:
+        assert all(lib.ref_alignmem(x) == v for x, v in enumerate(g["alignmem"].tolist())), "stored alignmem differs"
+        for (b, x), want in g["bucketize"].items():
+            b, x = np.frombuffer(b, np.float32), np.frombuffer(x, np.float32)
+            out = np.empty(x.size, np.int32)
+            lib.ref_bucketize_many(b.ctypes.data, int(b.size), x.ctypes.data, int(x.size), out.ctypes.data)
+            assert np.array_equal(out, want), "stored Bucketize vectors differ from the reference's function"
+    return g
+
+
+@pytest.fixture(scope="session")
+def ref_bucketize(ref_host_goldens):
+    """The REFERENCE's own `Bucketize` (cuda_emitter.cc:233-247): the library built from its source where that source lies,
+    else its stored outputs for the inputs the tests use (an input it never saw fails the test).
+    Returns f(boundaries, values) -> int32 bucket ids."""
+    lib = _ref_host_lib()
 
     def run(boundaries, values):
         b = np.ascontiguousarray(boundaries, np.float32)
         v = np.ascontiguousarray(values, np.float32).ravel()
+        if lib is None:
+            want = ref_host_goldens["bucketize"].get((b.tobytes(), v.tobytes()))
+            assert want is not None, "no stored output of the reference's Bucketize for these inputs (make_ref_host_goldens.py)"
+            return want.copy()
         assert 1 <= b.size <= lib.ref_bucketize_max_boundaries()
         out = np.empty(v.size, np.int32)
         lib.ref_bucketize_many(b.ctypes.data, int(b.size), v.ctypes.data, int(v.size), out.ctypes.data)
@@ -46,18 +77,18 @@ def ref_bucketize():
 
 
 @pytest.fixture(scope="session")
-def ref_alignmem():
+def ref_alignmem(ref_host_goldens):
     """The REFERENCE's own `alignmem` (the arena alignment of its generated host code, cuda_emitter.cc:967-969, used by
-    :2151-2179), compiled from its source by oracle/ref_extract.py next to `Bucketize`.  Returns f(bytes) -> bytes."""
-    import ctypes as C
-    import ref_extract
-    if not ref_extract.build():
-        pytest.skip("oracle/_ref/libref_bucketize.so is absent and /root/reference is not here to build it from")
-    lib = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libref_bucketize.so"))
-    if not hasattr(lib, "ref_alignmem"):
-        pytest.skip("oracle/_ref was built before ref_alignmem existed")
-    lib.ref_alignmem.argtypes = [C.c_int]
-    lib.ref_alignmem.restype = C.c_int
+    :2151-2179): the library built from its source next to `Bucketize`, else its stored value table.
+    Returns f(bytes) -> bytes."""
+    lib = _ref_host_lib()
+    if lib is None:
+        table = ref_host_goldens["alignmem"]
+
+        def stored(x):
+            assert 0 <= int(x) < table.size, f"alignmem({x}) is not stored (make_ref_host_goldens.py)"
+            return int(table[int(x)])
+        return stored
     return lambda x: int(lib.ref_alignmem(int(x)))
 
 

@@ -171,7 +171,7 @@ def test_bench_gpus_2_starts_its_ranks_and_prints_one_line(workload):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["FCP_BENCH_DEVICE"] = "0"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "20", "--warmup", "5",
-           "--no-cpu-baseline", "--no-pcie", "--no-overlap", "--columns", "48", "--vocab", "5000", "--batch", "64"]
+           "--full", "--no-cpu-baseline", "--no-pcie", "--no-overlap", "--columns", "48", "--vocab", "5000", "--batch", "64"]
     if workload != "s2":
         cmd += ["--workload", workload]
         env["FCP_BENCH_HBM_BYTES"] = str(24 << 20)              # 48 tables of 160 KB .. 1.3 MB: 29 MB do not fit "one GPU"
@@ -218,7 +218,7 @@ def test_bench_gpus_2_headline_survives_a_sharded_leg_that_never_returns():
     env["FCP_BENCH_SHARD_COLUMNS"], env["FCP_BENCH_SHARD_VOCAB"] = "400", "3000"
     env["FCP_BENCH_SHARDED_WATCHDOG_S"] = "0.05"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "20", "--warmup", "5",
-           "--no-cpu-baseline", "--no-pcie", "--no-overlap", "--columns", "48", "--vocab", "5000", "--batch", "64"]
+           "--full", "--no-cpu-baseline", "--no-pcie", "--no-overlap", "--columns", "48", "--vocab", "5000", "--batch", "64"]
     res = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

@@ -1749,9 +1749,9 @@ def test_random_sparse_reshape_graphs_to_hip_path(torch_cuda, tmp_path, seed):
 
 @pytest.mark.gpu
 def test_bench_refuses_to_time_wrong_results(torch_cuda):
-    """bench.py serves every resident request once and compares it with the closed-form tables before the warm-up
-    (ServingHarness.verify_resident, no oracle): correct kernels pass on one-hot and pooled columns alike, and one
-    flipped table value is caught."""
+    """`bench.py --full` serves every resident request once and compares it with the closed-form tables before the warm-up
+    (ServingHarness.verify_resident, no oracle; a plain run skips it and says so in `verified`): correct kernels pass on
+    one-hot and pooled columns alike, and one flipped table value is caught."""
     from recom_amd import synth
     from recom_amd.harness import ServingHarness
     torch = torch_cuda
@@ -1768,6 +1768,50 @@ def test_bench_refuses_to_time_wrong_results(torch_cuda):
         with pytest.raises(RuntimeError, match="closed-form"):
             h.verify_resident()
         h.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("through_bytes,ring", [(None, 1), ("1", 1), ("1", 6)], ids=["nt", "plain_reused", "sc1nt_fresh"])
+def test_plain_bench_times_the_steps_and_dumps_what_the_last_one_computed(torch_cuda, oracle, tmp_path, through_bytes, ring):
+    """`bench.py` without --full: one JSON line with the headline fields and none of the side records; --dump-outputs writes
+    the concat output the last timed request left in its ring arena, which must be the oracle's output for the request the
+    loop served last (warm-up, pre-warm and the 7 timed steps, cycling 16 resident requests).  All three store policies of
+    the output (store_policy_for, fcp_process.hip): `nt` below FCP_STORE_THROUGH_BYTES (32 MiB by default; this output is
+    0.37 MB), and with the threshold at 1 byte plain stores into the reused arena of a one-arena ring and `sc1 nt` into a
+    six-arena ring."""
+    import json
+    import os
+    import subprocess
+    from recom_amd import synth
+    from recom_amd.ops import concat_inputs
+    out_dir = str(tmp_path / "outputs")
+    cmd = [sys.executable, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"),
+           "--gpus", "1", "--steps", "7", "--warmup", "2", "--columns", "48", "--vocab", "5000", "--batch", "64",
+           "--arena-ring", str(ring), "--dump-outputs", out_dir]
+    env = dict(os.environ)
+    if through_bytes:
+        env["FCP_STORE_THROUGH_BYTES"] = through_bytes
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 7 and rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["unit"] == "inferences/s"
+    assert rec["higher_is_better"] is True and rec["dtype"] == "f32"
+    for side in ("repeats", "p50_latency_ms", "arena_reuse", "overlapped_serving", "single_caller_stream", "cpu_baseline",
+                 "pcie_inclusive", "sharded"):
+        assert side not in rec, side
+    assert "access_mix" not in rec["roofline"] and rec["verified"]["checked"] == 0
+    index = (2 + rec["extra_warmup_requests"] + 7 - 1) % 16
+    assert rec["outputs"]["request"] == index and rec["outputs"]["rows"] == "all" and rec["config"]["arena_ring"] == ring
+    model = synth.model_s2(columns=48, vocab=5000, batch=64)
+    blob, offsets, shapes = concat_inputs(model.make_request(index).inputs)
+    want, bad = oracle.process_feature_columns(model.spec.to_dict(), blob, offsets, shapes, model.numpy_tables(), None)
+    assert bad == 0 and sorted(os.listdir(out_dir)) == [f"group_{g}.npy" for g in range(len(want))]
+    for g, w in enumerate(want):
+        got = np.load(os.path.join(out_dir, f"group_{g}.npy"))
+        assert got.dtype == np.float32 and got.shape == w.shape
+        assert np.abs(got.astype(np.float64) - w).max(initial=0.0) < 1e-5
 
 
 def test_sla_bounded_throughput_search_follows_the_reference_protocol(torch_cuda):
