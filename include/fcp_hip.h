@@ -395,6 +395,27 @@ int fcp_plan_arena_bytes(fcp_plan_t *plan, const int32_t *concated_shapes,
 /* Device error counter (FCP_FLAG_COUNT_BAD_IDS); synchronises `stream`. */
 int fcp_plan_read_bad_ids(fcp_plan_t *plan, void *stream, int64_t *count);
 
+/* ---- diagnostics: what the last request launched (read-only) ------------------------------------------------------------
+ * The kernel variant, block counts and output store policy of the plan's most recent fcp_process_feature_columns (or
+ * the request of fcp_shard_step_run) — so a test can assert which instantiation it reached.  The request path records
+ * it with relaxed stores and no lock: while host threads issue requests on the plan concurrently the fields may come
+ * from different requests.  Before the first request: kernel FCP_LAUNCH_NONE, and zero block counts. */
+enum { FCP_LAUNCH_NONE = 0, FCP_LAUNCH_DENSE = 1, FCP_LAUNCH_RAGGED = 2, FCP_LAUNCH_HYBRID = 3 };
+enum { FCP_LAUNCH_STORE_NT = 0, FCP_LAUNCH_STORE_SC1_NT = 1, FCP_LAUNCH_STORE_PLAIN = 4 };
+enum { FCP_LAUNCH_SEG_NONE = 0, FCP_LAUNCH_SEG_PREPASS = 1, FCP_LAUNCH_SEG_SEARCH = 2 };
+typedef struct fcp_launch_info {
+  int32_t kernel;           /* FCP_LAUNCH_*: no kernel (empty request), dense, ragged, or the hybrid of the two */
+  int32_t vec;              /* floats per slot (V of the instantiation): the gcd of the plan's column dims, 1 | 2 | 4 */
+  int32_t rows_per_wave;    /* dense body (R of the instantiation): 1 | 2 | 4 */
+  int32_t store_policy;     /* FCP_LAUNCH_STORE_*: output stores `nt`, write-through `sc1 nt`, or plain */
+  int32_t wide_rows;        /* 1: 64-bit row arithmetic in the dense body (a table shard of >= 2^32 - 3 slots) */
+  int32_t shard_world;      /* > 1: the SHARDED instantiation (row-sharded plan) */
+  int32_t dense_blocks;     /* blocks of the dense body (0: none) */
+  int32_t ragged_blocks;    /* blocks of the ragged body (0: none) */
+  int32_t segment_offsets;  /* FCP_LAUNCH_SEG_*: segment-id columns took the pre-pass kernel, or the blocks searched */
+} fcp_launch_info_t;
+int fcp_plan_last_launch(const fcp_plan_t *plan, fcp_launch_info_t *out);
+
 /* ---- ProcessFeatureColumns (cuda_emitter.cc:2303-2494) ------------------- */
 /* HIP graphs: a request whose shapes are resident (it ran once on this stream) only
  * enqueues kernels, so the call may be made while `stream` is being captured.  The

@@ -299,6 +299,11 @@ struct fcp_plan {
   int64_t lane_min_work = 0;
   int32_t request_order = FCP_ORDER_STREAM; // fcp_plan_set_request_order
   std::atomic<uintptr_t> recent_arena[2] = {}; // the arenas of the last two requests (store_policy_for)
+  // what the last request enqueued (fcp_plan_last_launch): written with relaxed stores beside the values the request path
+  // computes anyway, read by diagnostics only
+  struct LastLaunch {
+    std::atomic<int32_t> kernel{0}, rows_per_wave{0}, store_policy{0}, dense_blocks{0}, ragged_blocks{0}, segment_offsets{0};
+  } last_launch;
   // Run-time supervision of the lanes (LaneSupervisor below): a verdict is learnt once, a mapping can go bad later (another
   // library of the process creates streams; the runtime re-maps queues): sampled windows of lane requests are timed
   // against the stream-order rate of the same requests and the caller is demoted to its own stream when they lose.

@@ -1350,6 +1350,21 @@ int fcp_plan_read_bad_ids(fcp_plan_t *p, void *stream, int64_t *count) {
   return FCP_OK;
 }
 
+int fcp_plan_last_launch(const fcp_plan_t *p, fcp_launch_info_t *out) {
+  if (!p || !out) return fail(FCP_ERR_INVALID_ARGUMENT, "null argument");
+  const fcp_plan::LastLaunch &ll = p->last_launch;
+  out->kernel = ll.kernel.load(std::memory_order_relaxed);
+  out->vec = p->vec;
+  out->rows_per_wave = ll.rows_per_wave.load(std::memory_order_relaxed);
+  out->store_policy = ll.store_policy.load(std::memory_order_relaxed);
+  out->wide_rows = p->wide_rows ? 1 : 0;
+  out->shard_world = p->desc.shard_world > 1 ? p->desc.shard_world : 1;
+  out->dense_blocks = ll.dense_blocks.load(std::memory_order_relaxed);
+  out->ragged_blocks = ll.ragged_blocks.load(std::memory_order_relaxed);
+  out->segment_offsets = ll.segment_offsets.load(std::memory_order_relaxed);
+  return FCP_OK;
+}
+
 } // extern "C"
 
 #if defined(FCP_STAMPS)

@@ -321,6 +321,15 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
   FcpLaunch L;
   const int store_policy = store_policy_for(p, arena, m.csr_arena_off);
   fill_launch(p, *slot, 1, a->concated_inputs, arena, store_policy, &L);
+  { // fcp_plan_last_launch (diagnostics): the dispatch below, as it will be made
+    fcp_plan::LastLaunch &ll = p->last_launch;
+    ll.kernel.store((int32_t)(m.geo[0].grid_blocks > 0) | (int32_t)(m.geo[1].grid_blocks > 0) << 1, std::memory_order_relaxed);
+    ll.rows_per_wave.store(m.geo[0].rows_per_wave, std::memory_order_relaxed);
+    ll.store_policy.store(store_policy, std::memory_order_relaxed);
+    ll.dense_blocks.store(m.geo[0].grid_blocks, std::memory_order_relaxed);
+    ll.ragged_blocks.store(m.geo[1].grid_blocks, std::memory_order_relaxed);
+    ll.segment_offsets.store(p->seg_cols.empty() ? 0 : (m.seg_search ? 2 : 1), std::memory_order_relaxed);
+  }
   if (!p->seg_cols.empty() && !m.seg_search) {
     FcpSegLaunch S;
     S.seg_cols = p->d_seg_cols;

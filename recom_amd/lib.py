@@ -22,6 +22,10 @@ FCP_ERR_HIP = 4
 FCP_ERR_UNSUPPORTED = 5
 FCP_ERR_NO_DEVICE = 6
 FLAG_HOST_ONLY = 1 << 31  # plan without device resources (layout queries only)
+# fcp_launch_info_t (fcp_plan_last_launch): names of the kernel, store-policy and segment-offset codes
+LAUNCH_KERNELS = {0: "none", 1: "dense", 2: "ragged", 3: "hybrid"}
+LAUNCH_STORES = {0: "nt", 1: "sc1_nt", 4: "plain"}
+LAUNCH_SEGMENT_OFFSETS = {0: "none", 1: "prepass", 2: "search"}
 
 
 class FcpError(RuntimeError):
@@ -103,6 +107,13 @@ class PrivateStreamsStats(C.Structure):
                 ("keep_ratio", C.c_double), ("demoted", C.c_int32), ("evaluation_in_progress", C.c_int32)]
 
 
+class LaunchInfo(C.Structure):
+    """fcp_launch_info_t"""
+    _fields_ = [("kernel", C.c_int32), ("vec", C.c_int32), ("rows_per_wave", C.c_int32), ("store_policy", C.c_int32),
+                ("wide_rows", C.c_int32), ("shard_world", C.c_int32), ("dense_blocks", C.c_int32), ("ragged_blocks", C.c_int32),
+                ("segment_offsets", C.c_int32)]
+
+
 class StagerStats(C.Structure):
     """fcp_stager_stats_t"""
     _fields_ = [("calls", C.c_int64), ("copy_calls", C.c_int64), ("copy_calls_over_1ms", C.c_int64), ("fallback_switches", C.c_int64),
@@ -132,7 +143,7 @@ EXPORTS = [
     "fcp_graph_build", "fcp_graph_free", "fcp_placement_assign", "fcp_concat_outputs_scatter_strided",
     "fcp_plan_set_private_streams", "fcp_result_wait", "fcp_result_synchronize", "fcp_plan_set_request_order",
     "fcp_plan_probe_private_streams", "fcp_plan_private_streams_verdict", "fcp_plan_verify_private_streams",
-    "fcp_plan_private_streams_stats",
+    "fcp_plan_private_streams_stats", "fcp_plan_last_launch",
 ]
 
 _lib = None
@@ -272,6 +283,8 @@ def load() -> C.CDLL:
         L.fcp_plan_private_streams_stats.argtypes = [C.c_void_p, C.POINTER(PrivateStreamsStats)]
     if hasattr(L, "fcp_plan_set_request_order"):
         L.fcp_plan_set_request_order.argtypes = [C.c_void_p, C.c_int32]
+    if hasattr(L, "fcp_plan_last_launch"):
+        L.fcp_plan_last_launch.argtypes = [C.c_void_p, C.POINTER(LaunchInfo)]
     if L.fcp_abi_version() != FCP_ABI_VERSION:
         raise ImportError("libfcp_hip.so ABI version mismatch; rebuild")
     _lib = L

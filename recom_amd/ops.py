@@ -297,6 +297,18 @@ class Plan:
         _lib.check(self._L.fcp_plan_read_bad_ids(self.handle, stream, C.byref(out)), "fcp_plan_read_bad_ids")
         return out.value
 
+    def last_launch(self) -> dict:
+        """``fcp_plan_last_launch``: what the plan's most recent request enqueued — kernel (``none`` / ``dense`` /
+        ``ragged`` / ``hybrid``), ``vec``, dense ``rows_per_wave``, ``store`` (``nt`` / ``sc1_nt`` / ``plain``),
+        ``wide_rows``, ``shard_world``, ``dense_blocks`` / ``ragged_blocks``, ``segment_offsets`` (``none`` /
+        ``prepass`` / ``search``).  Read-only diagnostics: which kernel instantiation a request reached."""
+        li = _lib.LaunchInfo()
+        _lib.check(self._L.fcp_plan_last_launch(self.handle, C.byref(li)), "fcp_plan_last_launch")
+        return dict(kernel=_lib.LAUNCH_KERNELS[li.kernel], vec=li.vec, rows_per_wave=li.rows_per_wave,
+                    store=_lib.LAUNCH_STORES[li.store_policy], wide_rows=bool(li.wide_rows), shard_world=li.shard_world,
+                    dense_blocks=li.dense_blocks, ragged_blocks=li.ragged_blocks,
+                    segment_offsets=_lib.LAUNCH_SEGMENT_OFFSETS[li.segment_offsets])
+
 
 @dataclass
 class ProcessOutputs:
@@ -353,15 +365,24 @@ class FeatureColumnProcess:
         plan = Plan.from_file(dlpath, device)
         return cls(plan.spec, device, plan)
 
-    def _allocators(self):
+    def _allocators(self, arena=None):
         """Per-call allocator callbacks (malloc_buff = the op's allocate_output(2),
-        malloc_temp = allocate_temp): per-call state keeps __call__ re-entrant."""
+        malloc_temp = allocate_temp): per-call state keeps __call__ re-entrant.  ``arena``: a caller-owned
+        torch.uint8 device tensor that malloc_buff hands out instead of a fresh one (it must hold ``nbytes``)."""
         torch, dev = self.torch, self.device
-        state = {"arena": None, "temps": []}
+        state = {"arena": None, "temps": [], "error": None}
 
         def _alloc(_ctx, nbytes):
-            state["arena"] = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-            return state["arena"].data_ptr()
+            if arena is None:
+                state["arena"] = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+                return state["arena"].data_ptr()
+            have = arena.numel() * arena.element_size()
+            if have < int(nbytes):       # (raised after the call: an exception cannot cross the C callback)
+                state["error"] = ValueError(f"FeatureColumnProcess: caller arena of {have} bytes, the request needs {int(nbytes)} "
+                                            "(Plan.arena_bytes)")
+                return None
+            state["arena"] = arena
+            return arena.data_ptr()
 
         def _alloc_temp(_ctx, nbytes):
             t = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
@@ -370,8 +391,10 @@ class FeatureColumnProcess:
 
         return state, _lib.ALLOC_FN(_alloc), _lib.ALLOC_FN(_alloc_temp)
 
-    def _args(self, concated_inputs, concated_offsets, concated_shapes, inputs, symbols, stream):
+    def _args(self, concated_inputs, concated_offsets, concated_shapes, inputs, symbols, stream, arena=None):
         torch = self.torch
+        if arena is not None and (arena.dtype != torch.uint8 or arena.device != self.device or not arena.is_contiguous()):
+            raise ValueError(f"FeatureColumnProcess: arena= must be a contiguous torch.uint8 tensor on {self.device}")
         offs = np.ascontiguousarray(concated_offsets, np.int32)
         shps = np.ascontiguousarray(concated_shapes, np.int32)
         sym = None if symbols is None else np.ascontiguousarray(symbols, np.int32)
@@ -384,7 +407,8 @@ class FeatureColumnProcess:
             self._tab_cache = (inputs, tptrs, tshapes, len(inputs))
         if stream is None:
             stream = torch.cuda.current_stream(self.device).cuda_stream
-        state, alloc_cb, alloc_temp_cb = self._allocators()
+        # (without `arena`, the zero-argument form: callers may replace `_allocators` with their own)
+        state, alloc_cb, alloc_temp_cb = self._allocators(arena) if arena is not None else self._allocators()
         a = _lib.ProcessArgs(
             concated_inputs.data_ptr() if concated_inputs is not None and concated_inputs.numel() else None,
             0 if concated_inputs is None else concated_inputs.numel() * concated_inputs.element_size(),
@@ -394,18 +418,23 @@ class FeatureColumnProcess:
             stream, alloc_temp_cb, None, alloc_cb, None)
         return a, (offs, shps, sym, tptrs, tshapes, state, alloc_cb, alloc_temp_cb)
 
+    def _process(self, a, res, state) -> None:
+        rc = self._L.fcp_process_feature_columns(self.plan.handle, C.byref(a), C.byref(res))
+        if state.get("error") is not None:
+            raise state["error"]
+        _lib.check(rc, "FeatureColumnProcess")
+
     def groups_only(self, concated_inputs, concated_offsets, concated_shapes, inputs, symbols=None,
-                    stream: Optional[int] = None) -> list:
+                    stream: Optional[int] = None, arena=None) -> list:
         """Lean call: returns only the per-group concat matrices (no per-column pointer /
-        shape arrays are materialised in Python).  FCP_LAYOUT_CONCAT plans only."""
+        shape arrays are materialised in Python).  FCP_LAYOUT_CONCAT plans only.  ``arena``: as for ``__call__``."""
         torch = self.torch
-        a, keep = self._args(concated_inputs, concated_offsets, concated_shapes, inputs, symbols, stream)
+        a, keep = self._args(concated_inputs, concated_offsets, concated_shapes, inputs, symbols, stream, arena)
         g = self.spec.n_groups
         _grp_ptrs = (C.c_void_p * g)()
         _grp_shapes = (C.c_int32 * (2 * g))()
         res = _lib.ProcessResult(None, None, None, _grp_ptrs, _grp_shapes, None, 0)
-        _lib.check(self._L.fcp_process_feature_columns(self.plan.handle, C.byref(a), C.byref(res)),
-                   "FeatureColumnProcess")
+        self._process(a, res, keep[5])
         arena = keep[5]["arena"]
         if getattr(self.plan, "private_streams", 0):
             _lib.check(self._L.fcp_result_wait(arena.data_ptr(), a.stream), "fcp_result_wait")
@@ -418,12 +447,15 @@ class FeatureColumnProcess:
         return out
 
     def __call__(self, concated_inputs, concated_offsets, concated_shapes, inputs, symbols=None,
-                 stream: Optional[int] = None, defer_wait: bool = False) -> ProcessOutputs:
+                 stream: Optional[int] = None, defer_wait: bool = False, arena=None) -> ProcessOutputs:
         """``defer_wait`` (plans with private streams only): do not order ``stream`` behind the result here; the reader
         calls ``ProcessOutputs.wait`` — the split between FeatureColumnProcess and ConcatOutputs in the rewritten
-        graph.  Default: the wait is enqueued at once, so torch code on ``stream`` may read the result as always."""
+        graph.  Default: the wait is enqueued at once, so torch code on ``stream`` may read the result as always.
+        ``arena``: a caller-owned contiguous torch.uint8 tensor on the op's device that the request writes its outputs
+        into instead of a fresh allocation (at least ``Plan.arena_bytes(shapes, symbols)`` bytes, else ValueError) — the
+        caller decides whether consecutive requests reuse an arena, which the output store policy depends on."""
         torch = self.torch
-        a, keep = self._args(concated_inputs, concated_offsets, concated_shapes, inputs, symbols, stream)
+        a, keep = self._args(concated_inputs, concated_offsets, concated_shapes, inputs, symbols, stream, arena)
         n, g = self.spec.n_columns, self.spec.n_groups
         _out_ptrs = (C.c_void_p * n)()
         _out_shapes = (C.c_int32 * (2 * n))()
@@ -431,8 +463,7 @@ class FeatureColumnProcess:
         _grp_ptrs = (C.c_void_p * g)()
         _grp_shapes = (C.c_int32 * (2 * g))()
         res = _lib.ProcessResult(_out_ptrs, _out_shapes, _out_strides, _grp_ptrs, _grp_shapes, None, 0)
-        _lib.check(self._L.fcp_process_feature_columns(self.plan.handle, C.byref(a), C.byref(res)),
-                   "FeatureColumnProcess")
+        self._process(a, res, keep[5])
         arena = keep[5]["arena"]
         if getattr(self.plan, "private_streams", 0) and not defer_wait:
             _lib.check(self._L.fcp_result_wait(arena.data_ptr(), a.stream), "fcp_result_wait")

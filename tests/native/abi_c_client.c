@@ -107,6 +107,14 @@ int main(void) {
   /* no device behind this plan: computing fails loudly, there is no CPU fallback */
   memset(&args, 0, sizeof(args));
   CHECK(fcp_process_feature_columns(plan, &args, NULL) == FCP_ERR_NO_DEVICE);
+  { /* the launch report: nothing launched yet; the plan's constants are there already (dims 8 and 4: V = 4) */
+    fcp_launch_info_t li;
+    memset(&li, 0x5a, sizeof(li));
+    CHECK(fcp_plan_last_launch(plan, &li) == FCP_OK && li.kernel == FCP_LAUNCH_NONE && li.vec == 4 && li.wide_rows == 0 &&
+          li.shard_world == 1 && li.dense_blocks == 0 && li.ragged_blocks == 0 && li.store_policy == FCP_LAUNCH_STORE_NT);
+    CHECK(fcp_plan_last_launch(plan, NULL) == FCP_ERR_INVALID_ARGUMENT);
+    CHECK(fcp_plan_last_launch(NULL, &li) == FCP_ERR_INVALID_ARGUMENT);
+  }
   { /* the serving-mode entry points (round 4) from plain C: a plan without a device refuses them, arguments are checked */
     double serial_us = 0.0, lanes_us = 0.0;
     int32_t verdict = 7;

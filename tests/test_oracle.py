@@ -570,3 +570,54 @@ def test_tf_cpu_dataflow_of_the_cpu_baseline_equals_the_fused_layout(oracle):
     for dataflow in (0, 1):
         done, sec = oracle.serve_for(model.spec.to_dict(), packed, model.numpy_tables(), None, 2, 0.05, dataflow)
         assert done >= 2 and sec > 0
+
+
+def _variant_keys():
+    import kernel_variant_cases as K
+    return sorted({c.key for c in K.cells()})
+
+
+@pytest.mark.parametrize("key", _variant_keys(), ids=lambda k: "-".join(map(str, k)))
+def test_kernel_variant_cells_oracle_within_rounding_of_float64(oracle, key):
+    """The plans and requests of tests/test_gpu_kernel_variants.py's cells (kernel_variant_cases): the C oracle — what
+    the GPU must equal bit for bit there — lies within the fp32 rounding bound of the float64 NumPy restatement at every
+    edge of the matrix (bag lengths around the walk batches, per-wave totals of 384 / 385 ids, bags of 1000, 64 active
+    lanes, filtered means, ids outside the vocabulary), and counts the same ids as bad."""
+    import kernel_variant_cases as K
+    from recom_amd.ops import concat_inputs
+    case = K.build_case(*key)
+    plan = case.spec.to_dict()
+    for t, (inputs, symbols) in enumerate(case.requests):
+        blob, offsets, shapes = concat_inputs(inputs)
+        got, bad = oracle.process_feature_columns(plan, blob, offsets, shapes, case.tables, symbols)
+        K.check_against_float64(got, key, t, (key, t))
+        # every out-of-vocabulary id that the filter did not drop, counted once per column it belongs to
+        want_bad = 0
+        for c in case.spec.columns:
+            if c.form == K.FORM_PASSTHROUGH:
+                continue
+            ids = np.asarray(inputs[c.ids_input], np.int64)
+            kept = np.ones(ids.size, bool) if c.xform_mode != K.XFORM_FILTER else \
+                (ids >= c.xform_lo[0]) & (ids <= c.xform_hi[0])
+            want_bad += int((kept & ((ids < 0) | (ids >= c.vocab))).sum())
+        assert bad == want_bad, (key, t, bad, want_bad)
+
+
+def test_kernel_variant_cells_cover_every_instantiation_and_store_policy():
+    """tests/test_gpu_kernel_variants.py's table names each of the 42 fused-kernel instantiations (dense and hybrid
+    <V, R, SHARDED>, ragged <V, SHARDED>) under each of the three store policies, and the dense and hybrid ones with
+    wide rows as well."""
+    import itertools
+    import kernel_variant_cases as K
+    cells = K.cells()
+    assert len({c.id for c in cells}) == len(cells)
+    insts = {K.instantiation(c) for c in cells}
+    want = {(k, v, r, s) for k, v, r, s in itertools.product(("dense", "hybrid"), K.VECS, K.RPWS, (False, True))} | \
+        {("ragged", v, 0, s) for v, s in itertools.product(K.VECS, (False, True))}
+    assert insts == want and len(want) == 42
+    covered = {(K.instantiation(c), c.store, c.wide) for c in cells}
+    for inst in want:
+        for store in K.STORES:
+            assert (inst, store, False) in covered, (inst, store)
+            if inst[0] != "ragged":
+                assert (inst, store, True) in covered, (inst, store)
