@@ -513,8 +513,7 @@ int fcp_process_feature_columns(fcp_plan_t *plan,
  * multiple.  (A verdict is kept per stream HANDLE for the life of the plan: a
  * process that destroys and re-creates its streams calls this function again.)
  * FCP_PRIVATE_NO_VERIFY skips all of it (the streams are used as
- * created); FCP_DIAG=lane_priority=normal|low|high chooses the priority the search
- * starts with; FCP_DIAG=private_verify_verbose prints the search.
+ * created); FCP_DIAG=private_verify_verbose prints the search.
  * Callers with a warm-up request (every deployment of the reference has one,
  * docs/build_from_source.md:42) call fcp_plan_verify_private_streams there: no
  * serving request then ever pays for the search.

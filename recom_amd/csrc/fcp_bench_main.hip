@@ -30,9 +30,6 @@ extern "C" int fcp_harness_create(fcp_plan_t *, const fcp_process_args_t *, int,
 extern "C" int fcp_harness_run(fcp_harness *, int, double *, float *, float *);
 extern "C" int fcp_harness_destroy(fcp_harness *);
 extern "C" int fcp_harness_copy_probe(size_t, int, float *);
-#if defined(FCP_STAMPS)
-extern "C" int fcp_debug_read_stamps(fcp_plan_t *, unsigned long long *, int);
-#endif
 extern "C" int fcp_harness_bw_probe(int, size_t, int, float *);
 extern "C" int fcp_harness_gather_probe(size_t, int, int, int, float *, double *);
 
@@ -525,50 +522,6 @@ int main(int argc, char **argv) {
               "\"frac_of_8TBs\": %.4f}\n",
               columns, batch, table_bytes / 1e9, steps, threads, wall * 1e3 / (steps * threads), us, alg / 1e6,
               alg / (us * 1e-6) / 1e9, alg / (us * 1e-6) / 8e12);
-#if defined(FCP_STAMPS)
-  {
-    // per-block timeline of the last launch (diagnostic build)
-    const int nb = 8 * ((int)((width / 4 + 63) / 64 + 7) / 8) * ((batch + 15) / 16);
-    std::vector<unsigned long long> st(8 * (size_t)nb);
-    CHECK_FCP(fcp_debug_read_stamps(plan, st.data(), nb));
-    unsigned long long t0 = ~0ull, t1 = 0;
-    int live = 0;
-    for (int b = 0; b < nb; ++b)
-      if (st[8 * b + 3]) {
-        ++live;
-        t0 = std::min(t0, st[8 * b]);
-        t1 = std::max(t1, st[8 * b + 3]);
-      }
-    std::printf("stamps: %d live blocks, kernel span %.2f us (100 MHz ticks)\n", live, (t1 - t0) / 100.0);
-    // histogram of block begin / end times and mean phase durations per bin of begin time:
-    // desc = phase 0; or = raw-id issue + first barrier; stage = boundary staging; raw = extra wait
-    // until the raw ids have landed; conv = phase 1b; rows = phase 2 (reads + stores acknowledged)
-    const unsigned long long bin = (t1 - t0) < 1600 ? 50 : 200; // ticks per histogram bin (0.5 or 2 us)
-    const int nbins = (int)((t1 - t0) / bin) + 1;
-    std::vector<int> begins(nbins, 0), ends(nbins, 0);
-    std::vector<std::vector<double>> d(6, std::vector<double>(nbins, 0.0));
-    for (int b = 0; b < nb; ++b) {
-      const unsigned long long *o = &st[8 * (size_t)b];
-      if (!o[3]) continue;
-      const int bb = (int)((o[0] - t0) / bin), be = (int)((o[3] - t0) / bin);
-      ++begins[bb];
-      ++ends[be];
-      d[0][bb] += (o[1] - o[0]) / 100.0;
-      d[1][bb] += (o[4] - o[1]) / 100.0;
-      d[2][bb] += (o[5] - o[4]) / 100.0;
-      d[3][bb] += (o[6] - o[5]) / 100.0;
-      d[4][bb] += (o[2] - o[6]) / 100.0;
-      d[5][bb] += (o[3] - o[2]) / 100.0;
-    }
-    for (int i = 0; i < nbins; ++i) {
-      if (!begins[i] && !ends[i]) continue;
-      const double n = begins[i] ? begins[i] : 1;
-      std::printf("  t=%5.1f us  begin %5d  end %5d   mean us: desc %.2f or %.2f stage %.2f raw %.2f conv %.2f rows+stores %.2f\n",
-                  i * (bin / 100.0), begins[i], ends[i], d[0][i] / n, d[1][i] / n, d[2][i] / n, d[3][i] / n, d[4][i] / n,
-                  d[5][i] / n);
-    }
-  }
-#endif
   CHECK_FCP(fcp_harness_destroy(h));
   CHECK_FCP(fcp_plan_destroy(plan));
   return 0;

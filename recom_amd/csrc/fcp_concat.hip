@@ -106,8 +106,7 @@ int fcp_concat_outputs_host(const void *const *host_inputs, const int32_t *dims,
   // Small payloads (the reference's models E / F: 32 dense features, 64 KB per request): the scatter kernel reads the
   // pinned slot through its device mapping — no copy, no device staging buffer, one runtime call less per request.
   // Large ones keep the H2D copy (the scatter would hold its CUs for the length of the PCIe transfer).
-  static const size_t direct_max = (size_t)fcp::diag_ll("concat_host_direct_max", 1 << 20); // tuning aid: bytes (0: always copy)
-  const bool direct = total <= direct_max;
+  const bool direct = total <= ((size_t)1 << 20);
   if (!direct && !malloc_temp) return fail(FCP_ERR_INVALID_ARGUMENT, "malloc_temp callback is required for payloads that are copied to the device");
   HostStageRing *ring = host_stage_ring(device);
   // Reserve a slot under the ring lock, then pack (the reference: one memcpy per input into a std::vector,

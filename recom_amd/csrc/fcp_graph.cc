@@ -17,7 +17,6 @@
 // The same walk exists in Python (recom_amd/graph/: the offline tool `python -m recom_amd.graph`);
 // tests/test_graph_plan.py requires both builders to write identical plan files and equal rewritten graphs.
 // Host-only plain C++ (compiled with g++ into libfcp_hip.so).
-#include "fcp_env.h"
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -36,12 +35,6 @@
 #include <vector>
 
 #include "../../include/fcp_hip.h"
-
-// diagnostic: FCP_DIAG=graph_debug prints the plan builder's decisions on stderr
-static bool graph_debug() {
-  static const bool on = fcp::diag_on("graph_debug");
-  return on;
-}
 
 int fcp_internal_fail(int code, const std::string &msg); // fcp_plan.hip: sets fcp_last_error
 
@@ -1022,7 +1015,6 @@ struct PlanBuilder {
         if (dt != DT_FLOAT) continue;
         shape = g.static_shape({&n, 0});
       }
-      if (graph_debug()) fprintf(stderr, "fcp_graph: table candidate %s (%s): rank %d\n", n.name.c_str(), n.op.c_str(), shape ? (int)shape->size() : -1);
       if (!shape || shape->size() != 2 || !GraphView::all_known(*shape) || std::min(*(*shape)[0], *(*shape)[1]) <= 0) continue;
       std::vector<std::string> stack{n.name};
       int lookups = 0;
@@ -1040,7 +1032,6 @@ struct PlanBuilder {
           }
         }
       }
-      if (graph_debug()) fprintf(stderr, "fcp_graph:   -> ok %d lookups %d\n", (int)ok, lookups);
       if (ok && lookups) tables[n.name] = {*(*shape)[0], *(*shape)[1]};
     }
   }
@@ -1554,10 +1545,7 @@ struct PlanBuilder {
       } catch (const Unsupported &) {
         continue;
       }
-      if (!axis || axis->v.empty() || ((int64_t)axis->v[0] != 1 && (int64_t)axis->v[0] != -1) || dtype != DT_FLOAT) {
-        if (graph_debug()) fprintf(stderr, "fcp_graph: concat %s skipped (axis const %d, dtype %d)\n", concat.name.c_str(), axis ? 1 : 0, dtype);
-        continue;
-      }
+      if (!axis || axis->v.empty() || ((int64_t)axis->v[0] != 1 && (int64_t)axis->v[0] != -1) || dtype != DT_FLOAT) continue;
       // snapshot: a group that turns out unusable must not leave operands behind
       const auto snap = std::make_tuple(host_ix, host_list, dev_ix, dev_list, sym_ix, sym_list);
       const int group = (int)out.groups.size();
@@ -1575,7 +1563,6 @@ struct PlanBuilder {
             ++lookups;
             value = tensor_name(r.first->name, r.second);
           } catch (const Unsupported &why) {
-            if (graph_debug()) fprintf(stderr, "fcp_graph: %s input %d (%s, %s): %s\n", concat.name.c_str(), i, r.first->name.c_str(), r.first->op.c_str(), why.what());
             col = host_column(ins[i], group, i);
             value = ins[i];
             if (tables.count(r.first->name) || !upstream_tables(*r.first).empty()) out.skipped.push_back({r.first->name, why.what()});
@@ -1585,7 +1572,6 @@ struct PlanBuilder {
         }
         if (lookups == 0) throw Unsupported("no lookup column converges here");
       } catch (const Unsupported &why) {
-        if (graph_debug()) fprintf(stderr, "fcp_graph: concat %s given up: %s\n", concat.name.c_str(), why.what());
         std::tie(host_ix, host_list, dev_ix, dev_list, sym_ix, sym_list) = snap;
         if (lookups) out.skipped.push_back({concat.name, why.what()});
         continue;

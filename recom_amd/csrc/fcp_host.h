@@ -189,7 +189,7 @@ struct LanePool {
   std::vector<hipStream_t> spacers;                   // streams that only hold hardware queues (verify_lanes)
   std::atomic<int> n_relying{0};                      // live plans that found the present mapping good, or use it unverified
   std::atomic<uint32_t> rr{0};
-  // Test aid (FCP_LANE_FAULT_US=N, read by fcp_plan_set_private_streams): every lane request first waits for the device's
+  // Test aid (FCP_DIAG=lane_fault_us=N, read by fcp_plan_set_private_streams): every lane request first waits for the device's
   // previous lane request and then spins for N us on its lane — lanes that serialise and stall, the signature of a
   // hardware-queue mapping that does not overlap (profiles/r04_private_streams_queue_mapping.txt: 29-86 us per S2
   // request), made deterministic for the supervisor's test.
@@ -266,7 +266,6 @@ struct fcp_plan {
   int32_t *d_seg_cols = nullptr;
   unsigned long long *d_bad = nullptr;
   float *d_zeros = nullptr;     // 256 zero bytes: the row a skipped id of a bag reads (ld_slot_or_zero)
-  unsigned long long *d_stamps = nullptr; // diagnostic builds only (-DFCP_STAMPS)
   std::vector<const void *> bound_tables;
   bool tables_bound = false;
 

@@ -120,7 +120,6 @@ struct FcpLaunch {
   FcpGroupLaunch groups[FCP_MAX_GROUPS];
   const FcpXform *xforms;      // per column (concat order), or null: no column has an id transform
   const float *zeros;          // 256 zero bytes (plan-owned): what a skipped id of a bag reads
-  unsigned long long *stamps;  // diagnostic builds (-DFCP_STAMPS) only: 8 timestamps per block
 };
 
 // Segment-offset pre-pass (ComputeSegmentOffsets, cuda_emitter.cc:768-818)

@@ -41,7 +41,6 @@
 #include "../../include/fcp_hip.h"
 #include <hip/hip_ext.h>
 #include "fcp_internal.h"
-#include "fcp_env.h"
 
 namespace {
 
@@ -75,14 +74,13 @@ template <int V> __device__ __forceinline__ VF<V> vzero() {
 
 // Output rows are written once and consumed by a later kernel: non-temporal stores
 // (measured on S2: 34.3 -> 30.5 us per request).  Table rows are read with the DEFAULT
-// cache policy: streaming them (-DFCP_NT_LOADS) changes nothing on S2 (1M-row tables,
+// cache policy: streaming them (non-temporal loads) changes nothing on S2 (1M-row tables,
 // uniform ids) but costs the reference's models E / F 4.5 us per request — their ~1000
 // bucketize / hash tables of ~100 rows are re-read by every row and belong in L2.
 // (r6) A per-column choice — non-temporal reads for tables far beyond an XCD's L2, default policy for the small hot ones —
 // was built and measured too, because a bare gather probe reads 11 % faster with `nt` at every row size (53.7 against 48.5
 // G rows/s): inside the fused kernels it moved nothing (S2 27.39 against 27.35 us, model F 12.9 / 12.9, RAGGED -0.5 us in
 // one encoding, +0 in the other: profiles/r06_streamed_table_reads_negative.txt) and was taken out again.
-// -DFCP_NO_NT restores the default policy for stores as well (tuning builds).
 // Write-through form (`sc1 nt`: the line leaves the XCD's L2 at once instead of at the kernel boundary) for
 // outputs larger than the L2s can hold — S2's 61 MB: 28.4 vs 29.0 us per request; outputs that FIT the
 // caches (DLRM 3.5 MB, models E / F 16 MB) lose with it (DLRM 4.7 -> 5.9 us, F 14.7 -> 17.7 us): the host
@@ -122,7 +120,7 @@ __device__ __forceinline__ void st_nt(FCP_GLOBAL VecType<1>::T *p, VecType<1>::T
   asm volatile("global_store_dword %0, %1, off nt" ::"v"(p), "v"(t) : "memory");
 }
 
-template <int V> __device__ __forceinline__ void st_out(float *p, const VF<V> &v, int policy = 0) {
+template <int V> __device__ __forceinline__ void st_out(float *p, const VF<V> &v, int policy) {
   typedef typename VecType<V>::T T;
   T t;
   __builtin_memcpy(&t, &v, sizeof(T));
@@ -130,12 +128,10 @@ template <int V> __device__ __forceinline__ void st_out(float *p, const VF<V> &v
     st_through(as_global(reinterpret_cast<T *>(p)), t);
     return;
   }
-#if !defined(FCP_NO_NT)
   if (!(policy & FCP_ST_PLAIN)) {
     st_nt(as_global(reinterpret_cast<T *>(p)), t);
     return;
   }
-#endif
   *as_global(reinterpret_cast<T *>(p)) = t;
 }
 
@@ -144,17 +140,8 @@ template <int V> __device__ __forceinline__ void st_out(float *p, const VF<V> &v
 template <int V> __device__ __forceinline__ VF<V> ld_slot32(const float *tb, uint32_t off);
 template <int V> __device__ __forceinline__ VF<V> ld_slot(const float *tb, uint32_t off, uint32_t spr) {
   typedef typename VecType<V>::T T;
-#if defined(FCP_ABLATE) && FCP_ABLATE == 4 // timing-only build 4: no table reads at all (ragged kernel too)
-  VF<V> z = vzero<V>();
-  z.v[0] = (float)off;
-  return z;
-#endif
   const FCP_GLOBAL T *g = as_global(reinterpret_cast<const T *>(tb)) + (uint64_t)off * spr;
-#if defined(FCP_NT_LOADS) // tuning build: stream table rows too (see the comment above st_out)
-  T t = __builtin_nontemporal_load(g);
-#else
   T t = *g;
-#endif
   VF<V> r;
   __builtin_memcpy(&r, &t, sizeof(T));
   return r;
@@ -164,17 +151,8 @@ template <int V> __device__ __forceinline__ VF<V> ld_slot(const float *tb, uint3
 // (S2: 0.15-0.25 us per request against the 64-bit multiply-add, profiles/r03_row_index_ab.txt).
 template <int V> __device__ __forceinline__ VF<V> ld_slot32(const float *tb, uint32_t off) {
   typedef typename VecType<V>::T T;
-#if defined(FCP_ABLATE) && FCP_ABLATE == 4 // timing-only build 4: no table reads at all (ragged kernel too)
-  VF<V> z = vzero<V>();
-  z.v[0] = (float)off;
-  return z;
-#endif
   const FCP_GLOBAL T *g = as_global(reinterpret_cast<const T *>(tb)) + off;
-#if defined(FCP_NT_LOADS) // tuning build: stream table rows too (see the comment above st_out)
-  T t = __builtin_nontemporal_load(g);
-#else
   T t = *g;
-#endif
   VF<V> r;
   __builtin_memcpy(&r, &t, sizeof(T));
   return r;
@@ -199,9 +177,6 @@ __device__ __forceinline__ int64_t ld_i64_a4(const char *p) {
 
 // cuda_emitter.cc:233-247 — r+1 = number of boundaries <= value.
 template <typename P> __device__ __forceinline__ int bucketize(P b, int n, float value) {
-#if defined(FCP_ABLATE) && FCP_ABLATE == 5 // timing-only build 5: no boundary search
-  return (int)value & 63;
-#endif
   int l = 0, r = n - 1;
   while (l <= r) {
     const int mid = (l + r) >> 1;
@@ -582,31 +557,7 @@ __device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *sm
   float *s_bnd = S.bnd;
 
   BlockPos B;
-#if defined(FCP_STAMPS) // diagnostic build: where does a block spend its time (never shipped)
-  const unsigned long long t_begin = __builtin_amdgcn_s_memrealtime();
-#endif
   const Hot H = load_hot(L);
-#if defined(FCP_ABLATE) && FCP_ABLATE == 6
-  // timing-only build 6 (S2's blob layout only; results are NOT the request's): what would a block-tile-major id layout buy?
-  // Every thread requests the 8-byte id words of its pairs at t = 0 — one contiguous 1152-byte chunk of valid int64 ids per
-  // block, at an address that needs nothing but the block index — in parallel with the slot map and the column records,
-  // instead of after them (the upper bound of "ids stored block-tile-major by ConcatInputs").
-  constexpr int PT4 = (FCP_WAVE * RB + FCP_BLOCK_THREADS - 1) / FCP_BLOCK_THREADS;
-  uint32_t early_lo[PT4], early_hi[PT4];
-  {
-    const int k = bid % 3000;
-    const char *chunk = H.blob + (size_t)(k % 100) * 38912 + 2048 + (size_t)(k / 100) * 1152;
-#pragma unroll
-    for (int h = 0; h < PT4; ++h) {
-      const int p = threadIdx.x + h * FCP_BLOCK_THREADS;
-      early_lo[h] = early_hi[h] = 0;
-      if (p < 160) { // a span of S2 holds 8-10 columns x 16 rows: the pairs a block really has
-        early_lo[h] = *as_global(reinterpret_cast<const uint32_t *>(chunk + 8 * (p % 144)));
-        early_hi[h] = *as_global(reinterpret_cast<const uint32_t *>(chunk + 8 * (p % 144) + 4));
-      }
-    }
-  }
-#endif
   if (!locate_block<RB>(L, H, bid, B)) return;
   const int tid = threadIdx.x;
   const int lane = tid & (FCP_WAVE - 1);
@@ -619,9 +570,6 @@ __device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *sm
   // ---- phase 0 ----------------------------------------------------------------------
   if (tid < B.ncols) stage_col(H, &s_col[tid], H.cols + B.first_col + tid, H.dyn + B.first_col + tid);
   __syncthreads();
-#if defined(FCP_STAMPS)
-  const unsigned long long t_desc = __builtin_amdgcn_s_memrealtime();
-#endif
 
   // ---- phase 1a: raw id words of this thread's (column, row) pairs ------------------------
   // issued before the boundary staging so that the two memory round trips overlap.  The column facts of
@@ -645,19 +593,12 @@ __device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *sm
     const int b = B.row_blk + p % RB;
     const unsigned form = FCP_F_FORM(pflags[h]);
     raw_lo[h] = raw_hi[h] = 0;
-#if defined(FCP_ABLATE) && FCP_ABLATE == 6
-    if (p < npairs && b < B.rows && form == FCP_FORM_GATHER) {
-      raw_lo[h] = early_lo[h];
-      raw_hi[h] = early_hi[h];
-    }
-#else
     if (p < npairs && b < B.rows && form == FCP_FORM_GATHER) {
       const bool is64 = FCP_F_IDSRC(pflags[h]) == FCP_IDS_I64;
       const char *a = pids[h] + (is64 ? 8 : 4) * (int64_t)b;
       raw_lo[h] = *as_global(reinterpret_cast<const uint32_t *>(a));
       raw_hi[h] = *as_global(reinterpret_cast<const uint32_t *>(a + (is64 ? 4 : 0)));
     }
-#endif
   }
 
   // ---- phase 0b: bucketize boundaries -> LDS (skipped when the span has none) --------------
@@ -670,9 +611,6 @@ __device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *sm
   const bool my_bkt = lane < B.ncols && FCP_F_IDSRC(s_col[lane].flags) == FCP_IDS_F32_BUCKETIZE &&
                       FCP_F_FORM(s_col[lane].flags) == FCP_FORM_GATHER && s_col[lane].bnd_step == 0.0f;
   const unsigned long long any_bkt = __ballot(my_bkt);
-#if defined(FCP_STAMPS)
-  const unsigned long long t_or = __builtin_amdgcn_s_memrealtime();
-#endif
   if (any_bkt) {
     const float *mine = my_bkt ? s_col[lane].boundaries : nullptr;
     const float *prev = reinterpret_cast<const float *>(__shfl_up((unsigned long long)mine, 1));
@@ -699,11 +637,6 @@ __device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *sm
     __syncthreads();
   }
 
-#if defined(FCP_STAMPS)
-  const unsigned long long t_stage = __builtin_amdgcn_s_memrealtime();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // diagnostic: when have the raw ids landed?
-  const unsigned long long t_raw = __builtin_amdgcn_s_memrealtime();
-#endif
   // ---- phase 1b: raw ids -> table slot offsets in LDS -----------------------------------------
 #pragma unroll
   for (int h = 0; h < PT; ++h) {
@@ -732,9 +665,6 @@ __device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *sm
     s_off[j * IDS + r] = off;
   }
   __syncthreads();
-#if defined(FCP_STAMPS)
-  const unsigned long long t_ids = __builtin_amdgcn_s_memrealtime();
-#endif
   if (q >= B.nslots) return;
 
   // ---- phase 2: R table reads in flight per lane, then R coalesced stores -------------------
@@ -749,44 +679,17 @@ __device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *sm
   uint32_t off[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) off[r] = s_off[j * IDS + r0 + r];
-#if defined(FCP_ABLATE) && FCP_ABLATE == 3 // timing-only build: sequential instead of random rows
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-    off[r] = (uint32_t)(((int64_t)(B.row_blk + r0 + r) * 131 + my_col * 977) % s_col[j].vocab);
-#endif
   VF<V> v[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     v[r] = vzero<V>();
-#if !(defined(FCP_ABLATE) && FCP_ABLATE == 1) // timing-only build 1: no table reads
     if (is_row(off[r])) v[r] = wide ? ld_slot<V>(tb, off[r], spr) : ld_slot32<V>(tb, off[r]);
-#else
-    v[r].v[0] = (float)off[r];
-#endif
   }
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const int b = B.row_blk + r0 + r;
-#if defined(FCP_ABLATE) && FCP_ABLATE == 2 // timing-only build 2: no output stores
-    asm volatile("" ::"v"(v[r].v[0]), "v"(v[r].v[V - 1]));
-    if (b < B.rows && v[r].v[0] == 1234.5f) st_out<V>(outp + (int64_t)b * ostride, v[r]);
-#else
     if (b < B.rows) st_out<V>(outp + (int64_t)b * ostride, v[r], H.store_through);
-#endif
   }
-#if defined(FCP_STAMPS)
-  if (L.stamps && tid == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's row reads have landed, its stores are issued and acknowledged
-    unsigned long long *o = L.stamps + 8ull * bid;
-    o[4] = t_or;
-    o[5] = t_stage;
-    o[6] = t_raw;
-    o[0] = t_begin;
-    o[1] = t_desc;
-    o[2] = t_ids;
-    o[3] = __builtin_amdgcn_s_memrealtime();
-  }
-#endif
 }
 
 template <int V, int R, bool SHARDED>
@@ -795,17 +698,12 @@ __global__ void __launch_bounds__(FCP_BLOCK_THREADS) fcp_dense_kernel(const FcpL
   dense_body<V, R, SHARDED>(L, blockIdx.x, smem);
 }
 
-// Table reads a lane of the ragged kernel keeps in flight while it walks a bag (tuning builds:
+// Table reads a lane of the ragged kernel keeps in flight while it walks a bag (measured:
 // 12 / 16 need 71 / 87 VGPRs and lose more to occupancy than they gain, profiles/HISTORY.md, round 1).
-#if !defined(FCP_WALK)
-#define FCP_WALK 8
-#endif
-#if !defined(FCP_WALK_FIRST) // widest first batch of a bag walk (10: 64 VGPRs, the most that keeps 8 waves per SIMD without scratch)
-#define FCP_WALK_FIRST 10
-#endif
-#if !defined(FCP_WALK_LONG) // the same in the rounds after the first (rows whose bags exceed the wave's tile)
-#define FCP_WALK_LONG 6 // (8 would need 66 VGPRs in the loop around the rounds)
-#endif
+constexpr int kWalk = 8;
+constexpr int kWalkFirst = 10; // widest first batch of a bag walk (10: 64 VGPRs, the most that keeps 8 waves per SIMD without scratch)
+constexpr int kWalkLong = 6;   // the same in the rounds after the first (rows whose bags exceed the wave's tile)
+                               // (8 would need 66 VGPRs in the loop around the rounds)
 
 // ---------------------------------------------------------------------------
 // Ragged kernel: any mix of column forms (dynamic shapes: multi-hot bags of
@@ -907,9 +805,6 @@ __device__ __forceinline__ void wave_lds_order() {
 template <int V> __device__ __forceinline__ VF<V> ld_slot_or_zero(const float *tb, const float *zeros, uint32_t off, uint32_t spr) {
   typedef typename VecType<V>::T T;
   const FCP_GLOBAL T *g = is_row(off) ? as_global(reinterpret_cast<const T *>(tb)) + (uint64_t)off * spr : as_global(reinterpret_cast<const T *>(zeros));
-#if defined(FCP_ABLATE) && FCP_ABLATE == 4 // timing-only build 4: no table reads at all
-  g = as_global(reinterpret_cast<const T *>(zeros));
-#endif
   const T t = *g;
   VF<V> r;
   __builtin_memcpy(&r, &t, sizeof(T));
@@ -917,8 +812,8 @@ template <int V> __device__ __forceinline__ VF<V> ld_slot_or_zero(const float *t
 }
 
 // The walk of one bag slice for one output slot: the n table slot offsets staged at s[0..n) are added to `acc`
-// in id order (sequential fp32 adds: the order of the oracle; TF-CPU's up to 9 ids per bag), FCP_WALK table reads in flight
-// per lane.  EVERY lane issues its first FCP_WALK reads at once, whatever its bag length; further batches
+// in id order (sequential fp32 adds: the order of the oracle; TF-CPU's up to 9 ids per bag), kWalk table reads in flight
+// per lane.  EVERY lane issues its first kWalk reads at once, whatever its bag length; further batches
 // only while some bag of the wave goes on.  (Round 2 walked "8, then 4" behind per-lane conditions: lanes with
 // up to 4 ids sat out the first pass and issued their reads only after it.)
 template <int V, int N>
@@ -937,7 +832,7 @@ __device__ __forceinline__ void bag_walk_batch(const float *tb, const float *zer
 
 template <int V, int WALK>
 __device__ __forceinline__ void bag_walk_sum(const float *tb, const float *zeros, uint32_t spr, const uint32_t *s, int n, VF<V> &acc) {
-  // The first batch is as wide as the wave's longest bag needs, up to FCP_WALK_FIRST reads per lane: every bag of
+  // The first batch is as wide as the wave's longest bag needs, up to kWalkFirst reads per lane: every bag of
   // the wave in ONE round of reads whenever none is longer than that (BASELINE's RAGGED and the reference's models
   // E / F draw 0..10 / 1..10 ids per row: with 8-wide batches nearly every wave ran a second round for its one or two
   // 9- and 10-id bags; RAGGED 30.2 -> 28.9 us, profiles/r03_ragged_walk_width_ab.txt).  Wave-uniform choices.
@@ -945,9 +840,9 @@ __device__ __forceinline__ void bag_walk_sum(const float *tb, const float *zeros
   if (WALK >= 8 && !__any(n > 4)) {
     bag_walk_batch<V, 4>(tb, zeros, spr, s, 0, n, acc);
     return;
-  } else if (WALK >= 8 && FCP_WALK_FIRST > WALK && __any(n > WALK)) {
-    bag_walk_batch<V, FCP_WALK_FIRST>(tb, zeros, spr, s, 0, n, acc);
-    base = FCP_WALK_FIRST;
+  } else if (WALK >= 8 && kWalkFirst > WALK && __any(n > WALK)) {
+    bag_walk_batch<V, kWalkFirst>(tb, zeros, spr, s, 0, n, acc);
+    base = kWalkFirst;
   } else {
     bag_walk_batch<V, WALK>(tb, zeros, spr, s, 0, n, acc);
   }
@@ -991,9 +886,6 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
   LdsCol *s_col = S.col;
 
   BlockPos B;
-#if defined(FCP_STAMPS)
-  const unsigned long long t_begin = __builtin_amdgcn_s_memrealtime();
-#endif
   // The front of a block (records -> CSR ranges -> ids) is a chain of dependent round trips with a handful of
   // instructions between them; issued at a higher wave priority those instructions do not queue behind the long
   // walk loops of the CU's other waves (back to 0 before the walk): RAGGED -0.35 us, batch 1024 -0.5 us
@@ -1020,9 +912,6 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
   // ---- phase 0 (block) --------------------------------------------------------------------
   if (tid < B.ncols) stage_col(H, &s_col[tid], H.cols + B.first_col + tid, H.dyn + B.first_col + tid);
   __syncthreads();
-#if defined(FCP_STAMPS)
-  const unsigned long long t_desc = __builtin_amdgcn_s_memrealtime();
-#endif
 
   // ---- phase 1a' (block): segment-id columns without a pre-pass: RB+1 row offsets per column ---
   if (H.seg_search) {
@@ -1037,9 +926,6 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
     }
     __syncthreads();
   }
-#if defined(FCP_STAMPS)
-  const unsigned long long t_seg = __builtin_amdgcn_s_memrealtime();
-#endif
   const int b = B.row_blk + wave;
   if (b >= B.rows) return; // wave-uniform; no block barrier follows
 
@@ -1107,9 +993,6 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
     for (int i = lane; i < pt; i += FCP_WAVE) ow[po + i] = (uint8_t)p;
   }
   wave_lds_order();
-#if defined(FCP_STAMPS)
-  const unsigned long long t_scan = __builtin_amdgcn_s_memrealtime();
-#endif
 
   // ---- one lane per staged id -> table slot offset in the wave's tile ---------------------------------------
   for (int base = 0; base < limit; base += FCP_WAVE) { // uniform trip count: the cross-lane reads need every lane
@@ -1126,9 +1009,6 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
     }
   }
   wave_lds_order();
-#if defined(FCP_STAMPS)
-  const unsigned long long t_ids = __builtin_amdgcn_s_memrealtime();
-#endif
 
   __builtin_amdgcn_s_setprio(0);
   // ---- phase 2 (wave): the owning lanes consume their column's slice ------------------------------------------
@@ -1162,7 +1042,7 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
   };
   {
     const int ptake = __shfl(take, j), poff = __shfl(offx, j);
-    if (live && ptake > 0) consume(std::integral_constant<int, FCP_WALK>(), wi + poff, ptake);
+    if (live && ptake > 0) consume(std::integral_constant<int, kWalk>(), wi + poff, ptake);
   }
 
   // ---- long bags (rare: a row whose bags hold more than CAPW ids, e.g. multi-hot history features of hundreds
@@ -1199,7 +1079,7 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
     }
     wave_lds_order();
     const int ptake = __shfl(tk, j), prank = __shfl(my_rank, j);
-    if (live && ptake > 0) consume(std::integral_constant<int, FCP_WALK_LONG>(), wi + (prank << sh_log2), ptake);
+    if (live && ptake > 0) consume(std::integral_constant<int, kWalkLong>(), wi + (prank << sh_log2), ptake);
     done += tk;
   }
   const int pcnt = __shfl(cnt, j);
@@ -1225,19 +1105,6 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
     for (int t = 0; t < V; ++t) acc.v[t] = acc.v[t] / fc;
   }
   st_out<V>(reinterpret_cast<float *>(H.arena + C.out_base) + e + (int64_t)b * C.out_stride, acc, H.store_through);
-#if defined(FCP_STAMPS)
-  if (L.stamps && tid == 0) { // wave 0 = first row of the block
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    unsigned long long *o = L.stamps + 8ull * bid;
-    o[0] = t_begin;
-    o[1] = t_desc;
-    o[4] = t_seg;
-    o[5] = t_scan;
-    o[6] = t_scan;
-    o[2] = t_ids;
-    o[3] = __builtin_amdgcn_s_memrealtime();
-  }
-#endif
 }
 
 template <int V, bool SHARDED>
@@ -1569,50 +1436,38 @@ void fcp_set_any_order(bool on) { tl_launch_flags = on ? (int)hipExtAnyOrderLaun
       hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, __VA_ARGS__);                        \
   } while (0)
 
-#define FCP_LAUNCH_DENSE(VV, RR)                                                                            \
-  do {                                                                                                      \
-    if (L.shard_world > 1)                                                                                  \
-      FCP_KLAUNCH((fcp_dense_kernel<VV, RR, true>), dim3(grid_blocks), dim3(FCP_BLOCK_THREADS), lds_pad, s, L); \
-    else                                                                                                    \
-      FCP_KLAUNCH((fcp_dense_kernel<VV, RR, false>), dim3(grid_blocks), dim3(FCP_BLOCK_THREADS), lds_pad, s, L); \
-  } while (0)
-#define FCP_LAUNCH_RAGGED(VV)                                                                               \
-  do {                                                                                                      \
-    if (L.shard_world > 1)                                                                                  \
-      FCP_KLAUNCH((fcp_ragged_kernel<VV, true>), dim3(grid_blocks), dim3(FCP_BLOCK_THREADS), lds_pad, s, L); \
-    else                                                                                                    \
-      FCP_KLAUNCH((fcp_ragged_kernel<VV, false>), dim3(grid_blocks), dim3(FCP_BLOCK_THREADS), lds_pad, s, L); \
-  } while (0)
+// A run-time value as a template argument: f(std::integral_constant<int, N>()) for the first N of the list equal to v,
+// for the last one when none is.
+template <int N, int... Rest, typename F> void with_int(int v, F &&f) {
+  if constexpr (sizeof...(Rest) == 0)
+    f(std::integral_constant<int, N>());
+  else if (v == N)
+    f(std::integral_constant<int, N>());
+  else
+    with_int<Rest...>(v, f);
+}
+template <typename F> void with_bool(bool v, F &&f) {
+  if (v)
+    f(std::true_type());
+  else
+    f(std::false_type());
+}
 
-// rows_per_wave: dense 1 | 2 | 4 (rows per block = 4 x that); ragged always 1.
+// vec: 4 | 2 | 1; rows_per_wave: dense 1 | 2 | 4 (rows per block = 4 x that); ragged always 1.
 int fcp_launch_fused(const FcpLaunch &L, int vec, bool dense_kernel, int grid_blocks, ihipStream_t *s) {
   if (grid_blocks <= 0) return 0;
-  // tuning aid: FCP_DIAG=lds_pad=<bytes> of unused dynamic LDS caps the blocks per CU
-  static const int lds_pad = (int)fcp::diag_ll("lds_pad", 0);
+  const dim3 grid(grid_blocks), block(FCP_BLOCK_THREADS);
+  const bool sharded = L.shard_world > 1;
   if (dense_kernel) {
-    const int R = L.rows_per_wave;
-#define FCP_DENSE_R(VV)                         \
-  switch (R) {                                  \
-  case 4: FCP_LAUNCH_DENSE(VV, 4); break;       \
-  case 2: FCP_LAUNCH_DENSE(VV, 2); break;       \
-  default: FCP_LAUNCH_DENSE(VV, 1); break;      \
-  }
-    if (vec == 4) {
-      FCP_DENSE_R(4)
-    } else if (vec == 2) {
-      FCP_DENSE_R(2)
-    } else {
-      FCP_DENSE_R(1)
-    }
-#undef FCP_DENSE_R
+    with_int<4, 2, 1>(vec, [&](auto V) {
+      with_int<4, 2, 1>(L.rows_per_wave, [&](auto R) {
+        with_bool(sharded, [&](auto SHARDED) { FCP_KLAUNCH((fcp_dense_kernel<V, R, SHARDED>), grid, block, 0, s, L); });
+      });
+    });
   } else {
-    if (vec == 4) {
-      FCP_LAUNCH_RAGGED(4);
-    } else if (vec == 2) {
-      FCP_LAUNCH_RAGGED(2);
-    } else {
-      FCP_LAUNCH_RAGGED(1);
-    }
+    with_int<4, 2, 1>(vec, [&](auto V) {
+      with_bool(sharded, [&](auto SHARDED) { FCP_KLAUNCH((fcp_ragged_kernel<V, SHARDED>), grid, block, 0, s, L); });
+    });
   }
   return (int)hipGetLastError();
 }
@@ -1625,28 +1480,11 @@ int fcp_launch_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch
   H.ragged_blocks = ragged_blocks;
   const dim3 grid(dense_blocks + ragged_blocks), block(FCP_BLOCK_THREADS);
   const bool sharded = Ldense.shard_world > 1;
-#define FCP_HYB(VV, RR)                                                                   \
-  do {                                                                                    \
-    if (sharded)                                                                          \
-      FCP_KLAUNCH((fcp_hybrid_kernel<VV, RR, true>), grid, block, 0, s, H);               \
-    else                                                                                  \
-      FCP_KLAUNCH((fcp_hybrid_kernel<VV, RR, false>), grid, block, 0, s, H);              \
-  } while (0)
-#define FCP_HYB_R(VV)                        \
-  switch (Ldense.rows_per_wave) {            \
-  case 4: FCP_HYB(VV, 4); break;             \
-  case 2: FCP_HYB(VV, 2); break;             \
-  default: FCP_HYB(VV, 1); break;            \
-  }
-  if (vec == 4) {
-    FCP_HYB_R(4)
-  } else if (vec == 2) {
-    FCP_HYB_R(2)
-  } else {
-    FCP_HYB_R(1)
-  }
-#undef FCP_HYB_R
-#undef FCP_HYB
+  with_int<4, 2, 1>(vec, [&](auto V) {
+    with_int<4, 2, 1>(Ldense.rows_per_wave, [&](auto R) {
+      with_bool(sharded, [&](auto SHARDED) { FCP_KLAUNCH((fcp_hybrid_kernel<V, R, SHARDED>), grid, block, 0, s, H); });
+    });
+  });
   return (int)hipGetLastError();
 }
 
@@ -1721,12 +1559,7 @@ int fcp_launch_concat_outputs(const void *const *inputs, const int32_t *dims, co
     if (gx <= 0) continue;
     if (gx > 0x7fffffff) return (int)hipErrorInvalidValue;
     const dim3 grid((unsigned)gx, (unsigned)m), block(FCP_BLOCK_THREADS);
-    if (vec == 4)
-      hipLaunchKernelGGL(fcp_concat_outputs_kernel<4>, grid, block, 0, s, A);
-    else if (vec == 2)
-      hipLaunchKernelGGL(fcp_concat_outputs_kernel<2>, grid, block, 0, s, A);
-    else
-      hipLaunchKernelGGL(fcp_concat_outputs_kernel<1>, grid, block, 0, s, A);
+    with_int<4, 2, 1>(vec, [&](auto V) { hipLaunchKernelGGL(fcp_concat_outputs_kernel<V>, grid, block, 0, s, A); });
     const int err = (int)hipGetLastError();
     if (err) return err;
   }
@@ -1741,15 +1574,9 @@ int fcp_launch_shard_finalize(const FcpLaunch &L, int group, const float *partia
   const int64_t nblocks = (int64_t)((nslots + FCP_BLOCK_THREADS - 1) / FCP_BLOCK_THREADS) * row_count;
   if (nblocks > 0x7fffffff) return (int)hipErrorInvalidValue;
   dim3 grid((unsigned)nblocks);
-  if (vec == 4) {
-    hipLaunchKernelGGL((fcp_shard_finalize_kernel<4>), grid, dim3(FCP_BLOCK_THREADS), 0, s, L, group,
-                       partials, world, row_begin, row_count, out);
-  } else if (vec == 2) {
-    hipLaunchKernelGGL((fcp_shard_finalize_kernel<2>), grid, dim3(FCP_BLOCK_THREADS), 0, s, L, group,
-                       partials, world, row_begin, row_count, out);
-  } else {
-    hipLaunchKernelGGL((fcp_shard_finalize_kernel<1>), grid, dim3(FCP_BLOCK_THREADS), 0, s, L, group,
-                       partials, world, row_begin, row_count, out);
-  }
+  with_int<4, 2, 1>(vec, [&](auto V) {
+    hipLaunchKernelGGL(fcp_shard_finalize_kernel<V>, grid, dim3(FCP_BLOCK_THREADS), 0, s, L, group, partials, world, row_begin,
+                       row_count, out);
+  });
   return (int)hipGetLastError();
 }

@@ -82,18 +82,12 @@ void pending_forget(const void *owner) {
 // The request stager is about to overwrite a device blob / a pinned buffer the kernels read directly: `stream` (the copy
 // stream) or the host waits for the private-stream request that read it last.  (The stager's own `consumed` events are
 // recorded on the caller's stream, which does not wait for private-stream kernels.)
-bool stager_reader_wait_off() { // test aid: FCP_DIAG=stager_no_reader_wait reproduces the hazard the two functions below close
-  static const bool off = fcp::diag_on("stager_no_reader_wait");
-  return off;
-}
 int stager_input_wait(const void *base, int64_t bytes, hipStream_t stream) {
-  if (stager_reader_wait_off()) return FCP_OK;
   std::lock_guard<std::mutex> lock(g_pending_mu); // (held over the runtime call: the owning plan may not go away meanwhile)
   if (hipEvent_t ev = pending_input_event(base, bytes)) HIP_TRY(hipStreamWaitEvent(stream, ev, 0));
   return FCP_OK;
 }
 int stager_input_synchronize(const void *base, int64_t bytes) {
-  if (stager_reader_wait_off()) return FCP_OK;
   std::lock_guard<std::mutex> lock(g_pending_mu);
   if (hipEvent_t ev = pending_input_event(base, bytes))
     if (hipEventQuery(ev) != hipSuccess) HIP_TRY(hipEventSynchronize(ev));
@@ -192,16 +186,14 @@ int fcp_plan_set_private_streams(fcp_plan_t *p, int32_t n_streams, uint32_t flag
   // independent streams do not show it (2..8 serve workers: 23-25 us).  The request stays accepted — the round robin
   // simply runs over three.
   constexpr int kMaxLanes = 3;
-  if (n_streams > kMaxLanes && !fcp::diag_on("private_lanes_uncapped")) n_streams = kMaxLanes;
+  if (n_streams > kMaxLanes) n_streams = kMaxLanes;
   p->lane_count = n_streams;
   p->pool = n_streams > 0 ? pool : nullptr;
   if (n_streams == 0) return FCP_OK;
-  // The device's pool holds three lanes (more only for experiments); a plan that asks for fewer uses the first ones.
-  // FCP_DIAG=lane_priority=normal|low|high: the priority lanes are CREATED with (normal: a mapping that does not overlap then
-  // costs 29-44 us per S2 request; with another priority 74-87 us).  Verification (below) moves on to the others.
-  int prio = 0;
-  if (const char *e = fcp::diag("lane_priority")) prio = !std::strcmp(e, "low") ? 1 : !std::strcmp(e, "high") ? 2 : 0;
-  return create_lanes(pool, std::max(n_streams, kMaxLanes), prio);
+  // The device's pool holds three lanes; a plan that asks for fewer uses the first ones.  The lanes are CREATED at normal
+  // priority (a mapping that does not overlap then costs 29-44 us per S2 request; with another priority 74-87 us).
+  // Verification (below) moves on to the others.
+  return create_lanes(pool, kMaxLanes, 0);
 }
 
 // ---- diagnostic: do the plan's private streams overlap behind THIS caller stream, in THIS process? ----------------------
@@ -281,7 +273,7 @@ int run_lane_probe(fcp_plan *p, hipStream_t caller, int requests, int spin_us, i
 // created after it), up to kMaxSpacers — and, whatever is left to try, until `budget_ms` of wall time are spent (a mapping
 // costs ~8 ms: the search never holds a request for more than the budget plus one probe).  The probe: 24 one-block kernels
 // of 80 us with their consumers, three times (the first pass brings the queues up, the better of the other two counts);
-// serial / lanes >= 2.15 (three lanes) counts as overlap (scripts/probes/lane_probe_vs_real.py, lanes_cold_start.py,
+// serial / lanes >= 2.15 (three lanes) counts as overlap (scripts/probes/lanes_cold_start.py,
 // profiles/r04_private_streams_queue_mapping.txt).  *ok = false: this caller's requests stay on its own stream.
 // `again`: forget an earlier verdict of this caller and verify afresh (the warm-up entry point after a cheap first look).
 int verify_lanes(fcp_plan *p, hipStream_t caller, int budget_ms, bool again, bool *ok) {
@@ -321,8 +313,6 @@ int verify_lanes(fcp_plan *p, hipStream_t caller, int budget_ms, bool again, boo
     return FCP_OK;
   };
   const int n = (int)pool->lanes.size();
-  int first_prio = 0;
-  if (const char *e = fcp::diag("lane_priority")) first_prio = !std::strcmp(e, "low") ? 1 : !std::strcmp(e, "high") ? 2 : 0;
   double ratio = 0;
   int rc = overlap(&ratio);
   if (rc) return rc;
@@ -343,7 +333,7 @@ int verify_lanes(fcp_plan *p, hipStream_t caller, int budget_ms, bool again, boo
       HIP_TRY(hipStreamSynchronize(sp));
     }
     for (int k = (spacers == 0 ? 1 : 0); !good && k < 3 && in_budget(); ++k) { // (spacers == 0, first priority: probed above)
-      const int prio = (first_prio + k) % 3;
+      const int prio = k; // 0 normal, 1 low, 2 high
       for (auto &l : pool->lanes)
         if (l->stream) HIP_TRY(hipStreamSynchronize(l->stream));
       destroy_lanes(pool);
@@ -628,8 +618,6 @@ int process_on_private_streams(fcp_plan_t *p, const fcp_process_args_t *a, fcp_p
     std::lock_guard<std::mutex> cal_lock(p->pool->cal_mu);
     if (!p->lane_relies.exchange(true)) p->pool->n_relying.fetch_add(1, std::memory_order_acq_rel);
   }
-  static const bool lane_stats = fcp::diag_on("lane_stats"); // diagnostic: host time of a private-stream request by part
-  auto now_ns = [] { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   // -- supervisor: which way does this request go? --------------------------------------------------------------------------
   bool to_lane = true, so_window = false, lane_window = false;
   int decision = 0; // +1: demote the caller after this request, -1: re-admit it
@@ -680,7 +668,6 @@ int process_on_private_streams(fcp_plan_t *p, const fcp_process_args_t *a, fcp_p
   }
   {
     PrivateLane &L = *p->pool->lanes[p->pool->rr.fetch_add(1, std::memory_order_relaxed) % (uint32_t)p->lane_count];
-    const uint64_t s0 = lane_stats ? now_ns() : 0;
     std::unique_lock<std::mutex> lane_lock(L.mu);
     if (!L.stream) { // the lanes are being re-created by another plan's verification (this plan uses them unverified)
       lane_lock.unlock();
@@ -716,13 +703,9 @@ int process_on_private_streams(fcp_plan_t *p, const fcp_process_args_t *a, fcp_p
     }
     // the completion event rides on the dispatch packet of the request's last kernel (no marker packet of its own);
     // a request without a kernel (nothing to compute) records it the plain way
-    static const bool attach = fcp::diag_ll("lane_stop_event", 1) != 0; // tuning aid: 0 = always record a marker
-    if (attach) fcp_set_stop_event(L.out[e]);
-    static const bool alias_done = fcp::diag_ll("lane_done_alias", 1) != 0; // tuning aid: 0 = the slot records an event of its own
-    if (alias_done) {
-      tl_lane_done = L.out[e];
-      tl_lane_done_gen = g_lane_generation.load(std::memory_order_acquire);
-    }
+    fcp_set_stop_event(L.out[e]);
+    tl_lane_done = L.out[e];
+    tl_lane_done_gen = g_lane_generation.load(std::memory_order_acquire);
     // the caller's stream is recorded, and the lane made to wait for it, inside the call: right behind malloc_buff
     if (!(p->lane_flags & FCP_PRIVATE_NO_CALLER_WAIT)) tl_lane_dep = &dep;
     rc = fcp_internal_process(p, &b, r);
@@ -735,8 +718,7 @@ int process_on_private_streams(fcp_plan_t *p, const fcp_process_args_t *a, fcp_p
       if (lane_window) sup_abort(p);
       return rc ? rc : fail(FCP_ERR_HIP, "private streams: the request never reached its allocation");
     }
-    const uint64_t s3 = lane_stats ? now_ns() : 0;
-    if (!attach || pending) HIP_TRY(hipEventRecord(L.out[e], L.stream));
+    if (pending) HIP_TRY(hipEventRecord(L.out[e], L.stream));
     pending_register(p, r->buffer, r->buffer_bytes, a->concated_inputs, a->concated_bytes, L.out[e]);
     if (fault) p->pool->last_out.store(L.out[e], std::memory_order_release);
     if (mark || in_window) {
@@ -748,15 +730,6 @@ int process_on_private_streams(fcp_plan_t *p, const fcp_process_args_t *a, fcp_p
         S.phase = 4;
         p->sup_window.store(false, std::memory_order_relaxed);
       }
-    }
-    if (lane_stats) {
-      static std::atomic<uint64_t> n{0}, a_proc{0}, a_reg{0};
-      const uint64_t s4 = now_ns();
-      a_proc += s3 - s0;
-      a_reg += s4 - s3;
-      if ((++n & 1023) == 0)
-        std::fprintf(stderr, "fcp private-stream request, host us: lane lock + request itself (incl. the record on the caller's stream and the lane's wait) %.2f, completion event + registry %.2f\n",
-                     a_proc.load() / 1e3 / n.load(), a_reg.load() / 1e3 / n.load());
     }
   }
   if (decision) switch_caller(p, (void *)caller, decision < 0);

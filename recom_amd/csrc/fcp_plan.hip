@@ -365,11 +365,6 @@ int finish_geometry(const fcp_plan *p, DynMeta *m) {
       // them SLOWER (DLRM 5.0 -> 7.0 us, S2 at batch 128 11.0 -> 11.9 us): a block's fixed staging chain
       // costs more than the idle CUs, see profiles/HISTORY.md, round 2.
       while (rpw < 4 && max_rows >= 32 * rpw) rpw *= 2; // >= 64 rows -> 4, 32..63 -> 2, < 32 -> 1
-      static const int forced = [] { // tuning aid: FCP_DIAG=rows_per_wave=1|2|4
-        const int v = (int)fcp::diag_ll("rows_per_wave", 0);
-        return (v == 1 || v == 2 || v == 4) ? v : 0;
-      }();
-      if (forced) rpw = forced;
     } // ragged kernel: one row per wave (2 interleaved rows measured slower: 33.7 vs 31.6 us)
     G2.rows_per_wave = rpw;
     int32_t blocks = 0;
@@ -383,8 +378,7 @@ int finish_geometry(const fcp_plan *p, DynMeta *m) {
       G.span_list_off = G.nlist == nspans_g ? -1 : p->list_off[kind][g];
       // listed spans are dealt to XCDs in groups of 8; fewer than 8 are not padded
       // (nsp8 = -nlist selects the plain mapping in the kernels)
-      static const bool no_xcd_map = fcp::diag_on("no_xcd_map"); // tuning aid: plain span order
-      G.nsp8 = (G.nlist >= 8 && !no_xcd_map) ? (G.nlist + 7) / 8 : -std::max(G.nlist, 1);
+      G.nsp8 = G.nlist >= 8 ? (G.nlist + 7) / 8 : -std::max(G.nlist, 1);
       G.block_begin = blocks;
       G.slot_map_off = p->group_map_off[g];
       G.csr_reg_stride = 0; // (fill_launch sets groups[0]'s per request)
@@ -579,7 +573,6 @@ void destroy_device(fcp_plan *p) {
   if (p->d_seg_cols) (void)hipFree(p->d_seg_cols);
   if (p->d_bad) (void)hipFree(p->d_bad);
   if (p->d_zeros) (void)hipFree(p->d_zeros);
-  if (p->d_stamps) (void)hipFree(p->d_stamps);
 }
 
 int init_device(fcp_plan *p) {
@@ -725,10 +718,6 @@ int init_device(fcp_plan *p) {
     (void)hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, p->desc.device);
     p->host_writes_dyn = large_bar != 0 && !p->env.dyn_upload_kernel; // (FCP_DYN_UPLOAD=kernel)
   }
-#if defined(FCP_STAMPS)
-  HIP_TRY(hipMalloc(&p->d_stamps, 8 * sizeof(unsigned long long) * 65536));
-  HIP_TRY(hipMemset(p->d_stamps, 0, 8 * sizeof(unsigned long long) * 65536));
-#endif
   for (auto &s : p->slots) {
     // rounded up to 16 bytes: the upload kernel moves uint4s
     const size_t dyn_bytes = (nc * sizeof(FcpColDyn) + 15) / 16 * 16;
@@ -1366,14 +1355,3 @@ int fcp_plan_last_launch(const fcp_plan_t *p, fcp_launch_info_t *out) {
 }
 
 } // extern "C"
-
-#if defined(FCP_STAMPS)
-// diagnostic builds only: per-block timestamps of the LAST dense launch (8 x u64 per block, 100 MHz ticks)
-extern "C" int fcp_debug_read_stamps(fcp_plan_t *p, unsigned long long *out, int n_blocks) {
-  if (!p || !p->d_stamps || n_blocks > 65536) return FCP_ERR_INVALID_ARGUMENT;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out, p->d_stamps, 8 * sizeof(unsigned long long) * (size_t)n_blocks, hipMemcpyDeviceToHost));
-  return FCP_OK;
-}
-#endif
-

@@ -145,26 +145,13 @@ int install_slot(fcp_plan *p, const fcp_process_args_t *a, DynSlot &s) {
     }
     if (!p->host_writes_dyn && hipEventQuery(s.uploaded) != hipSuccess) HIP_TRY(hipEventSynchronize(s.uploaded));
   }
-  static const bool stats = fcp::diag_on("install_stats"); // diagnostic: where a descriptor installation spends its host time
-  auto now_ns = [] { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const uint64_t t0 = stats ? now_ns() : 0;
   int rc = compute_dyn(p, a->concated_offsets, a->concated_shapes, a->symbols, a->concated_bytes, s.h_dyn, &s.meta);
   if (rc) return rc;
   p->last_work_bytes.store(s.meta.work_bytes, std::memory_order_relaxed);
-  const uint64_t t1 = stats ? now_ns() : 0;
   const size_t dyn_bytes = p->cols.size() * sizeof(FcpColDyn);
   if (p->host_writes_dyn) {
     std::memcpy(s.d_dyn, s.h_dyn, dyn_bytes); // CPU stores through the BAR into fine-grained VRAM
     __builtin_ia32_sfence();                  // posted before the launch's doorbell write
-    if (stats) {
-      static std::atomic<uint64_t> n{0}, ns_dyn{0}, ns_bar{0};
-      const uint64_t t2 = now_ns();
-      ns_dyn += t1 - t0;
-      ns_bar += t2 - t1;
-      if ((++n & 1023) == 0)
-        std::fprintf(stderr, "fcp install: %llu installs, shapes -> records %.2f us, records -> device (%zu bytes through the BAR) %.2f us\n",
-                     (unsigned long long)n.load(), ns_dyn.load() / 1e3 / n.load(), dyn_bytes, ns_bar.load() / 1e3 / n.load());
-    }
   } else {
     const int e = fcp_launch_upload(s.h_dyn_dev, s.d_dyn, dyn_bytes, stream);
     if (e) return hip_fail("descriptor upload launch", (hipError_t)e);
@@ -196,8 +183,6 @@ void publish_slot(fcp_plan *p, DynSlot &s, const std::vector<int32_t> &key, void
 //   (profiles/r06_arena_reuse_store_policy.txt).  A performance hint only: read and updated without the plan's mutex.
 int store_policy_for(fcp_plan *p, const void *arena, int64_t out_bytes) {
   const int64_t through_bytes = p->env.store_through_bytes;
-  // tuning aid: FCP_DIAG=store_plain_reuse=0 never plain stores, 2 always, default 1 = the rule above
-  static const int reuse_mode = (int)fcp::diag_ll("store_plain_reuse", 1);
   const uintptr_t ar = reinterpret_cast<uintptr_t>(arena);
   const uintptr_t a0 = p->recent_arena[0].load(std::memory_order_relaxed), a1 = p->recent_arena[1].load(std::memory_order_relaxed);
   const bool reused = ar == a0 || ar == a1;
@@ -206,9 +191,8 @@ int store_policy_for(fcp_plan *p, const void *arena, int64_t out_bytes) {
     p->recent_arena[0].store(ar, std::memory_order_relaxed);
   }
   constexpr int64_t kPlainMaxBytes = (int64_t)160 << 20;
-  if (reuse_mode == 2) return 4;
   if (out_bytes < through_bytes) return 0;
-  return (reuse_mode == 1 && reused && out_bytes <= kPlainMaxBytes) ? 4 : 1;
+  return (reused && out_bytes <= kPlainMaxBytes) ? 4 : 1;
 }
 
 void fill_launch(const fcp_plan *p, const DynSlot &s, int kind, const void *blob, void *arena, int store_policy, FcpLaunch *L) {
@@ -221,7 +205,6 @@ void fill_launch(const fcp_plan *p, const DynSlot &s, int kind, const void *blob
   L->blob = static_cast<const char *>(blob);
   L->arena = static_cast<char *>(arena);
   L->bad_ids = p->d_bad;
-  L->stamps = p->d_stamps;
   L->csr_arena_off = s.meta.csr_arena_off;
   L->shard_rank = p->desc.shard_rank;
   L->shard_world = p->desc.shard_world;
@@ -358,8 +341,7 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
   // Freshly installed descriptors: the slot's `done` event rides on the dispatch packet of the request's last kernel (its
   // stop event) instead of being recorded behind it — one runtime call (~1.9 us of host time) and one marker packet less
   // per request with new shapes.  (A private-lane request has already claimed the stop event for its completion event.)
-  static const bool done_on_kernel = fcp::diag_ll("done_stop_event", 1) != 0; // tuning aid: 0 = always record
-  const bool attach_done = install && done_on_kernel && !fcp_stop_event_pending() && !capturing;
+  const bool attach_done = install && !fcp_stop_event_pending() && !capturing;
   if (attach_done) fcp_set_stop_event(slot->done);
   struct ClearStop { // (an early return between here and the launch must not leave the event armed for this thread's next launch)
     bool armed;

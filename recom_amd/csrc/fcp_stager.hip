@@ -96,7 +96,7 @@ struct fcp_stager {
   // Fallback of the copying mode: on a busy host hipMemcpyAsync sometimes BLOCKS the caller for 25-70 us per call, request
   // after request (profiles/r04_pcie_staging_memcpy_anomaly.txt: one run in two with unpinned pack workers, rarely with
   // pinned ones), which doubles the pipelined time.  Eight such calls among the last 32 and the next 256 requests are served zero
-  // copy (steady 65 us on S2); then the copy engine gets another chance.  FCP_STAGER_NO_FALLBACK=1 disables it.
+  // copy (steady 65 us on S2); then the copy engine gets another chance.
   uint32_t blocked_hist = 0;
   int direct_left = 0;
   uint64_t n_fallbacks = 0, n_blocked = 0;
@@ -110,12 +110,12 @@ struct fcp_stager {
   // Groups cost throughput (the caller watches instead of packing, four copy launches instead of one: S2 58 -> 66 us per
   // request pipelined) and buy latency (lone request 142 -> 130 us): they are used when the caller is NOT issuing back to
   // back — more than kLatencyGapNs since the previous staging call returned — i.e. when nothing is there to overlap with
-  // but the request itself.  FCP_STAGER_GROUPS_ALWAYS=1: every request.
+  // but the request itself.  FCP_DIAG=stager_groups_always: every request.
   uint64_t t_last_return_ns = 0;
   bool groups_always = false;
   std::atomic<uint64_t> max_copy_call_ns{0}, n_copy_calls{0}, n_copy_over_1ms{0};
   uint64_t n_total_calls = 0;
-  // FCP_STAGER_STATS=1: where a call spends its host time (ns per phase, printed when the stager is destroyed)
+  // FCP_DIAG=stager_stats: where a call spends its host time (ns per phase, printed when the stager is destroyed)
   bool stats = false;
   uint64_t n_calls = 0, ns_wait = 0, ns_layout = 0, ns_pack = 0, ns_enqueue = 0, ns_api[4] = {0, 0, 0, 0};
 };
@@ -186,8 +186,7 @@ int fcp_stager_create_ex(int32_t device, int64_t capacity_bytes, int32_t max_inp
   {
     // pack next to the GPU: the H2D copy reads the pinned ring from that socket's memory
     cpu_set_t near;
-    static const bool no_pin = fcp::diag_on("stager_no_pin"); // tuning aid
-    const bool pin = !no_pin && fcp::cpus_near_device(device, &near);
+    const bool pin = fcp::cpus_near_device(device, &near);
     s->pool = new fcp::PackPool(n_threads, pin ? &near : nullptr);
   }
   s->byte_off.resize(2 * (size_t)max_inputs + 2); // offsets [0, n], lengths [n + 1, 2n + 1] (stage_layout)
@@ -281,22 +280,14 @@ int stage_layout(const fcp_host_tensor_t *inputs, int32_t n, const uint8_t *mode
 
 // A request is a thousand or two SMALL tensors (RAGGED: 11 KB of ids and 22 KB of indices per column), each somewhere else
 // in memory: the hardware prefetcher starts over at every one of them.  While tensor i is packed the head of tensor
-// i + 1 is requested (FCP_DIAG=pack_prefetch_bytes=N, default 2 KiB: tuning aid; 0 = off).
+// i + 1 is requested: its first 2 KiB, with the non-temporal hint.
 inline void prefetch_head(const fcp_host_tensor_t &t) {
-  static const int64_t bytes = fcp::diag_ll("pack_prefetch_bytes", 2048);
   if (!t.data) return;
   int64_t n = t.elem_size;
   for (int32_t j = 0; j < t.rank; ++j) n *= t.dims[j];
-  if (n > bytes) n = bytes;
-  static const int hint = (int)fcp::diag_ll("pack_prefetch_hint", 0); // tuning aid: 0 = non-temporal, 1 = every cache level, 2 = L2 and up
+  if (n > 2048) n = 2048;
   const char *p = static_cast<const char *>(t.data);
-  if (hint == 2) {
-    for (int64_t o = 0; o < n; o += 64) __builtin_prefetch(p + o, 0, 2);
-  } else if (hint == 1) {
-    for (int64_t o = 0; o < n; o += 64) __builtin_prefetch(p + o, 0, 3);
-  } else {
-    for (int64_t o = 0; o < n; o += 64) __builtin_prefetch(p + o, 0, 0);
-  }
+  for (int64_t o = 0; o < n; o += 64) __builtin_prefetch(p + o, 0, 0);
 }
 
 // One input into its place in the staged blob (`nbytes` = its bytes there).
@@ -336,11 +327,8 @@ bool pack_on_pool(fcp::PackPool &pool, int n_threads, const fcp_host_tensor_t *i
     in_off[i + 1] = in_off[i] + ne * inputs[i].elem_size;
   }
   const int64_t total = in_off[n];
-  static const int per_thread = [] { // tuning aid: chunks per pack thread (every chunk costs two contended atomics)
-    const int v = (int)fcp::diag_ll("pack_chunks_per_thread", 0);
-    return v > 0 ? v : 4;
-  }();
-  const int chunks = (int)std::min<int64_t>(std::max<int64_t>(1, total / (64 << 10)), (int64_t)per_thread * n_threads);
+  constexpr int kChunksPerThread = 4; // (every chunk costs two contended atomics)
+  const int chunks = (int)std::min<int64_t>(std::max<int64_t>(1, total / (64 << 10)), (int64_t)kChunksPerThread * n_threads);
   std::atomic<int> refused{0};
   // group bookkeeping: chunk c belongs to group c * ng / chunks; first input of every chunk up front (the groups' byte ranges)
   constexpr int kMaxGroups = 16;
@@ -354,26 +342,7 @@ bool pack_on_pool(fcp::PackPool &pool, int n_threads, const fcp_host_tensor_t *i
     for (int g = 0; g < ng; ++g) group_left[g].store(0, std::memory_order_relaxed);
     for (int c = 0; c < chunks; ++c) group_left[c * ng / chunks].fetch_add(1, std::memory_order_relaxed);
   }
-  // FCP_DIAG=pack_trace (diagnostic): when did every chunk of a call start and end, and on which thread — printed for every 128th call
-  static const bool trace = fcp::diag_on("pack_trace");
-  static std::atomic<uint64_t> n_calls{0};
-  struct ChunkTrace { uint64_t t0, t1; unsigned long tid; };
-  std::vector<ChunkTrace> tr;
-  const bool tracing = trace && (n_calls.fetch_add(1) & 127) == 100;
-  auto now_ns = [] { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  if (tracing) tr.resize((size_t)chunks);
-  const uint64_t t_pub = tracing ? now_ns() : 0;
   auto chunk_fn = [&](int c) {
-    struct Stamp { // (scope guard: the end stamp on every exit path of the chunk)
-      ChunkTrace *e;
-      uint64_t (*now)();
-      ~Stamp() { if (e) e->t1 = now(); }
-    };
-    if (tracing) {
-      tr[(size_t)c].t0 = now_ns();
-      tr[(size_t)c].tid = (unsigned long)pthread_self();
-    }
-    Stamp stamp{tracing ? &tr[(size_t)c] : nullptr, +[] { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }};
     const int64_t b0 = total * c / chunks, b1 = total * (c + 1) / chunks;
     int lo = (int)(std::lower_bound(in_off, in_off + n, b0) - in_off);
     const int hi = c + 1 == chunks ? n : (int)(std::lower_bound(in_off, in_off + n, b1) - in_off); // (the last chunk also takes trailing empty inputs)
@@ -414,13 +383,6 @@ bool pack_on_pool(fcp::PackPool &pool, int n_threads, const fcp_host_tensor_t *i
     pool.run(chunks, chunk_fn);
     for (int g = 0; g < ng; ++g) ship(g);
   }
-  if (tracing) {
-    const uint64_t t_end = now_ns();
-    std::fprintf(stderr, "fcp pack trace: %d chunks, %d threads, call %.1f us; chunk: start-after-publish us, duration us, thread\n", chunks,
-                 n_threads, (t_end - t_pub) / 1e3);
-    for (int c = 0; c < chunks; ++c)
-      std::fprintf(stderr, "  %2d: %6.1f %6.1f %lx\n", c, (tr[(size_t)c].t0 - t_pub) / 1e3, (tr[(size_t)c].t1 - tr[(size_t)c].t0) / 1e3, tr[(size_t)c].tid & 0xffffff);
-  }
   return refused.load() == 0;
 }
 } // namespace
@@ -437,8 +399,7 @@ int fcp_stager_stage_ex(fcp_stager_t *s, const fcp_host_tensor_t *inputs, int32_
   std::lock_guard<std::mutex> lock(s->mu);
   auto now_ns = [] { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const uint64_t t_begin = s->stats ? now_ns() : 0;
-  static const bool early_wake = !fcp::diag_on("stager_no_early_wake"); // tuning aid
-  if (early_wake) s->pool->expect(); // the pack workers wake up while this thread waits for the slot and lays the blob out
+  s->pool->expect(); // the pack workers wake up while this thread waits for the slot and lays the blob out
   // whatever consumes the previous slot has been enqueued on the caller's stream by now
   if (s->last >= 0) {
     StageSlot &prev = s->slots[s->last];
@@ -456,7 +417,6 @@ int fcp_stager_stage_ex(fcp_stager_t *s, const fcp_host_tensor_t *inputs, int32_
   } else if (hipEventQuery(sl.copied) != hipSuccess) {
     HIP_TRY(hipEventSynchronize(sl.copied));
   }
-  static const bool no_fallback = fcp::diag_on("stager_no_fallback");
   const bool direct = s->zero_copy || s->direct_left > 0;
   if (s->direct_left > 0) --s->direct_left;
   const uint64_t t_waited = s->stats ? now_ns() : 0;
@@ -521,7 +481,7 @@ int fcp_stager_stage_ex(fcp_stager_t *s, const fcp_host_tensor_t *inputs, int32_
     // (whatever was shipped before a refusal is ordinary traffic on the copy stream: the slot is simply reused)
     if (ship.err.load()) return hip_fail("H2D copy of a request group", (hipError_t)ship.err.load());
     const uint64_t worst = ship.max_ns.load();
-    if (!no_fallback && sorted) {
+    if (sorted) {
       s->blocked_hist = (s->blocked_hist << 1) | (worst > 20000 ? 1u : 0u); // the last 32 requests: whose copy calls blocked > 20 us
       s->n_blocked += worst > 20000;
       if (__builtin_popcount(s->blocked_hist) >= 8) { // the copy call holds the host up: the kernels read the pinned ring for a while

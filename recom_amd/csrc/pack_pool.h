@@ -2,7 +2,6 @@
 // Plain C++ (no HIP) so that tests/native/pack_pool_stress.cc can run it under
 // ThreadSanitizer on the CPU.
 #pragma once
-#include "fcp_env.h"
 #include <atomic>
 #include <condition_variable>
 #include <cstdint>
@@ -108,17 +107,10 @@ public:
 
 private:
   void wake() {
-    if (kFanout <= 0) {
-      cv_.notify_all();
-    } else {
-      for (int i = 0; i < kFanout; ++i) cv_.notify_one();
-    }
+    for (int i = 0; i < kFanout; ++i) cv_.notify_one();
   }
-  // FCP_PACK_FANOUT (tuning aid): 0 = the caller wakes every sleeper itself (notify_all); k > 0 = the caller wakes k, every
-  // woken worker k more
-  const int kFanout = [] {
-    return (int)fcp::diag_ll("pack_fanout", 2); // tuning aid
-  }();
+  // the caller wakes kFanout sleepers, every woken worker kFanout more
+  static constexpr int kFanout = 2;
   static constexpr int kIdxBits = 20, kMaxChunks = (1 << kIdxBits) - 1;
   static uint64_t pack(uint64_t e, int n, int idx) {
     return (e << (2 * kIdxBits)) | ((uint64_t)n << kIdxBits) | (uint64_t)idx;
@@ -154,8 +146,7 @@ private:
           });
           seen_expect = expected_.load(std::memory_order_acquire);
           lk.unlock();
-          if (kFanout > 0)
-            for (int i = 0; i < kFanout; ++i) cv_.notify_one(); // the wake-up tree: kFanout more sleepers each
+          for (int i = 0; i < kFanout; ++i) cv_.notify_one(); // the wake-up tree: kFanout more sleepers each
           spins = 0; // announced: spin until the job is there, at most kSpins pauses
         }
       }
@@ -164,10 +155,8 @@ private:
     }
   }
   // how long a woken worker spins for the announced job: ~20-40 us of pause instructions, a few times the layout phase
-  // that separates expect() from run() (FCP_DIAG=pack_spins=N: tuning aid)
-  const int kSpins = [] {
-    return (int)fcp::diag_ll("pack_spins", 1 << 10);
-  }();
+  // that separates expect() from run()
+  static constexpr int kSpins = 1 << 10;
   cpu_set_t affinity_;
   bool pinned_ = false;
   std::vector<std::thread> workers_;

@@ -10,7 +10,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# FCP_LIB_DIR: tuning aid, loads an alternative build (e.g. build/abl4) of the same sources
+# FCP_LIB_DIR: loads the library from another build directory (`make -C recom_amd/csrc OUT=<dir>`, e.g. of another commit)
 LIB_PATH = os.path.join(os.environ.get("FCP_LIB_DIR", _HERE), "libfcp_hip.so")
 
 FCP_ABI_VERSION = 2
