@@ -415,6 +415,23 @@ typedef struct fcp_launch_info {
   int32_t segment_offsets;  /* FCP_LAUNCH_SEG_*: segment-id columns took the pre-pass kernel, or the blocks searched */
 } fcp_launch_info_t;
 int fcp_plan_last_launch(const fcp_plan_t *plan, fcp_launch_info_t *out);
+/* Where the plan's most recent request put its segment-offset scratch (the pre-pass's CSR offsets, or the inverse map of
+ * an any-order ScatterNd column): *csr_arena_off = its byte offset in the request's arena (-1 before the first request),
+ * csr_base[k] = the int32 index of column k's range inside it, or -1 for a column without one (k < capacity; either
+ * pointer may be NULL).  Relaxed stores, as fcp_plan_last_launch. */
+int fcp_plan_last_csr(const fcp_plan_t *plan, int64_t *csr_arena_off, int32_t *csr_base, int32_t capacity);
+/* Process-wide launch counters of the kernels outside the fused matrix, one per instantiation (relaxed atomics: the
+ * stager's copies are enqueued from pack-pool threads).  counts[i] for i < min(capacity, FCP_AUX_KERNELS), in the order
+ * of the enum; `reset`: zero them after reading.  Returns FCP_AUX_KERNELS, or a negative status. */
+enum {
+  FCP_AUX_SEGMENT_OFFSETS = 0, /* the pre-pass: fcp_segment_offsets_kernel          */
+  FCP_AUX_SHARD_FINALIZE_V4 = 1, FCP_AUX_SHARD_FINALIZE_V2 = 2, FCP_AUX_SHARD_FINALIZE_V1 = 3,
+  FCP_AUX_CONCAT_V4 = 4, FCP_AUX_CONCAT_V2 = 5, FCP_AUX_CONCAT_V1 = 6,
+  FCP_AUX_UPLOAD = 7,          /* descriptor upload: fcp_upload_kernel              */
+  FCP_AUX_H2D_COPY = 8,        /* the request stager's copy: fcp_h2d_copy_kernel   */
+  FCP_AUX_KERNELS = 9
+};
+int fcp_aux_launch_counts(int64_t *counts, int32_t capacity, int32_t reset);
 
 /* ---- ProcessFeatureColumns (cuda_emitter.cc:2303-2494) ------------------- */
 /* HIP graphs: a request whose shapes are resident (it ran once on this stream) only

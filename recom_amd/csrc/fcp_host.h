@@ -302,6 +302,10 @@ struct fcp_plan {
   // computes anyway, read by diagnostics only
   struct LastLaunch {
     std::atomic<int32_t> kernel{0}, rows_per_wave{0}, store_policy{0}, dense_blocks{0}, ragged_blocks{0}, segment_offsets{0};
+    // fcp_plan_last_csr: the segment-offset scratch (arena byte offset, -1 before the first request) and, per plan column,
+    // its int32 index there (only seg_cols have one; the others stay -1)
+    std::atomic<int64_t> csr_arena_off{-1};
+    std::unique_ptr<std::atomic<int32_t>[]> csr_base;
   } last_launch;
   // Run-time supervision of the lanes (LaneSupervisor below): a verdict is learnt once, a mapping can go bad later (another
   // library of the process creates streams; the runtime re-maps queues): sampled windows of lane requests are timed

@@ -36,6 +36,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <atomic>
 #include <type_traits>
 
 #include "../../include/fcp_hip.h"
@@ -64,6 +65,7 @@ template <> struct VecType<2> { typedef float __attribute__((ext_vector_type(2))
 template <> struct VecType<1> { typedef float T; };
 
 template <int V> struct alignas(4 * V) VF { float v[V]; };
+template <int V> struct alignas(4 * V) VU { uint32_t v[V]; }; // the same slot as bit patterns
 
 template <int V> __device__ __forceinline__ VF<V> vzero() {
   VF<V> r;
@@ -1321,6 +1323,20 @@ __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
   const FcpColStatic cs = L.cols[c];
   const FcpColDyn cd = L.dyn[c];
   if (FCP_F_FORM(cs.flags) == FCP_FORM_EXTERNAL) return; // the hole stays for fcp_concat_outputs_host
+  if (FCP_F_FORM(cs.flags) != FCP_FORM_SEGMENT_REDUCE) {
+    // one owner per row (gather, scatter, passthrough, BatchColReduction): every other rank wrote +0.0, all bits clear, so
+    // the OR of the slices' bits is the owner's value, -0.0 and NaN payloads included (a sum from +0.0 turns -0.0 into +0.0)
+    VU<V> bits;
+#pragma unroll
+    for (int t = 0; t < V; ++t) bits.v[t] = 0u;
+    for (int w = 0; w < world; ++w) {
+      const VU<V> x = *reinterpret_cast<const VU<V> *>(partials + ((int64_t)w * row_count + bl) * W + (int64_t)q * V);
+#pragma unroll
+      for (int t = 0; t < V; ++t) bits.v[t] |= x.v[t];
+    }
+    *reinterpret_cast<VU<V> *>(out + bl * W + (int64_t)q * V) = bits;
+    return;
+  }
   VF<V> acc = vzero<V>();
   for (int w = 0; w < world; ++w) {
     const VF<V> x = *reinterpret_cast<const VF<V> *>(partials + ((int64_t)w * row_count + bl) * W + (int64_t)q * V);
@@ -1488,6 +1504,25 @@ int fcp_launch_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch
   return (int)hipGetLastError();
 }
 
+// Launch counters of the kernels outside the fused matrix (fcp_aux_launch_counts): process-wide, relaxed — the stager's
+// copies are enqueued from pack-pool threads.  A launch counts once the runtime has taken it.
+static std::atomic<int64_t> g_aux_launches[FCP_AUX_KERNELS];
+static int counted(int which, int err) {
+  if (!err) g_aux_launches[which].fetch_add(1, std::memory_order_relaxed);
+  return err;
+}
+// FCP_AUX_*_V4 / _V2 / _V1 follow each other
+static int vec_slot(int vec) { return vec == 4 ? 0 : (vec == 2 ? 1 : 2); }
+
+extern "C" int fcp_aux_launch_counts(int64_t *counts, int32_t capacity, int32_t reset) {
+  if (capacity < 0 || (capacity > 0 && !counts)) return -FCP_ERR_INVALID_ARGUMENT;
+  for (int i = 0; i < FCP_AUX_KERNELS; ++i) {
+    const int64_t v = reset ? g_aux_launches[i].exchange(0, std::memory_order_relaxed) : g_aux_launches[i].load(std::memory_order_relaxed);
+    if (i < capacity) counts[i] = v;
+  }
+  return FCP_AUX_KERNELS;
+}
+
 int fcp_launch_h2d_copy(const void *host_mapped_src, void *dst, size_t bytes, ihipStream_t *s) {
   if (bytes == 0) return 0;
   if ((bytes & 3) || ((reinterpret_cast<uintptr_t>(host_mapped_src) ^ reinterpret_cast<uintptr_t>(dst)) & 15) ||
@@ -1496,7 +1531,7 @@ int fcp_launch_h2d_copy(const void *host_mapped_src, void *dst, size_t bytes, ih
   const int blocks = (int)std::min<size_t>(64, (bytes / 16 + FCP_BLOCK_THREADS - 1) / FCP_BLOCK_THREADS + 1);
   hipLaunchKernelGGL(fcp_h2d_copy_kernel, dim3(blocks), dim3(FCP_BLOCK_THREADS), 0, s, static_cast<const char *>(host_mapped_src),
                      static_cast<char *>(dst), bytes);
-  return (int)hipGetLastError();
+  return counted(FCP_AUX_H2D_COPY, (int)hipGetLastError());
 }
 
 int fcp_launch_upload(const void *host_mapped_src, void *dst, size_t bytes, ihipStream_t *s) {
@@ -1505,7 +1540,7 @@ int fcp_launch_upload(const void *host_mapped_src, void *dst, size_t bytes, ihip
   const int blocks = n16 >= 4096 ? 8 : (n16 >= 1024 ? 4 : 1);
   hipLaunchKernelGGL(fcp_upload_kernel, dim3(blocks), dim3(FCP_BLOCK_THREADS), 0, s,
                      static_cast<const uint4 *>(host_mapped_src), static_cast<uint4 *>(dst), n16);
-  return (int)hipGetLastError();
+  return counted(FCP_AUX_UPLOAD, (int)hipGetLastError());
 }
 
 // any_order: FCP_ORDER_INPUTS_READY plans — the pre-pass reads the blob and writes the new arena's scratch only, so it needs
@@ -1519,7 +1554,7 @@ int fcp_launch_segment_offsets(const FcpSegLaunch &L, int n_seg_cols, int max_nn
                           (int)hipExtAnyOrderLaunch, L);
   else
     hipLaunchKernelGGL(fcp_segment_offsets_kernel, dim3(gx, n_seg_cols), dim3(FCP_BLOCK_THREADS), 0, s, L);
-  return (int)hipGetLastError();
+  return counted(FCP_AUX_SEGMENT_OFFSETS, (int)hipGetLastError());
 }
 
 int fcp_launch_concat_outputs(const void *const *inputs, const int32_t *dims, const int32_t *col_offsets, const int32_t *in_strides,
@@ -1560,7 +1595,7 @@ int fcp_launch_concat_outputs(const void *const *inputs, const int32_t *dims, co
     if (gx > 0x7fffffff) return (int)hipErrorInvalidValue;
     const dim3 grid((unsigned)gx, (unsigned)m), block(FCP_BLOCK_THREADS);
     with_int<4, 2, 1>(vec, [&](auto V) { hipLaunchKernelGGL(fcp_concat_outputs_kernel<V>, grid, block, 0, s, A); });
-    const int err = (int)hipGetLastError();
+    const int err = counted(FCP_AUX_CONCAT_V4 + vec_slot(vec), (int)hipGetLastError());
     if (err) return err;
   }
   return 0;
@@ -1578,5 +1613,5 @@ int fcp_launch_shard_finalize(const FcpLaunch &L, int group, const float *partia
     hipLaunchKernelGGL(fcp_shard_finalize_kernel<V>, grid, dim3(FCP_BLOCK_THREADS), 0, s, L, group, partials, world, row_begin,
                        row_count, out);
   });
-  return (int)hipGetLastError();
+  return counted(FCP_AUX_SHARD_FINALIZE_V4 + vec_slot(vec), (int)hipGetLastError());
 }

@@ -832,6 +832,8 @@ int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext,
   std::stable_partition(p->seg_cols.begin(), p->seg_cols.end(), [&](int32_t k) { return p->cols[k].d.form != FCP_FORM_GATHER_SCATTER; });
   p->n_seg_plain = 0;
   for (int32_t k : p->seg_cols) p->n_seg_plain += p->cols[k].d.form != FCP_FORM_GATHER_SCATTER;
+  p->last_launch.csr_base.reset(new std::atomic<int32_t>[p->cols.size() > 0 ? p->cols.size() : 1]);
+  for (size_t k = 0; k < p->cols.size(); ++k) p->last_launch.csr_base[k].store(-1, std::memory_order_relaxed);
   // Segment-id columns (SparseTensor indices / row ids): unsharded plans let every block find its rows'
   // ranges with a 16-ary search (fcp_kernels.hip::seg_lower_bound) instead of running the
   // ComputeSegmentOffsets pre-pass as a second, dependent launch.  Row-sharded plans keep the
@@ -1351,6 +1353,15 @@ int fcp_plan_last_launch(const fcp_plan_t *p, fcp_launch_info_t *out) {
   out->dense_blocks = ll.dense_blocks.load(std::memory_order_relaxed);
   out->ragged_blocks = ll.ragged_blocks.load(std::memory_order_relaxed);
   out->segment_offsets = ll.segment_offsets.load(std::memory_order_relaxed);
+  return FCP_OK;
+}
+
+int fcp_plan_last_csr(const fcp_plan_t *p, int64_t *csr_arena_off, int32_t *csr_base, int32_t capacity) {
+  if (!p || capacity < 0 || (capacity > 0 && !csr_base)) return fail(FCP_ERR_INVALID_ARGUMENT, "null plan / bad capacity");
+  const fcp_plan::LastLaunch &ll = p->last_launch;
+  if (csr_arena_off) *csr_arena_off = ll.csr_arena_off.load(std::memory_order_relaxed);
+  for (int32_t k = 0; k < capacity && k < (int32_t)p->cols.size(); ++k)
+    csr_base[k] = ll.csr_base ? ll.csr_base[k].load(std::memory_order_relaxed) : -1;
   return FCP_OK;
 }
 

@@ -312,6 +312,8 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
     ll.dense_blocks.store(m.geo[0].grid_blocks, std::memory_order_relaxed);
     ll.ragged_blocks.store(m.geo[1].grid_blocks, std::memory_order_relaxed);
     ll.segment_offsets.store(p->seg_cols.empty() ? 0 : (m.seg_search ? 2 : 1), std::memory_order_relaxed);
+    ll.csr_arena_off.store(m.csr_arena_off, std::memory_order_relaxed);
+    for (int k : p->seg_cols) ll.csr_base[k].store(slot->h_dyn[p->pos_of[k]].csr_base, std::memory_order_relaxed);
   }
   if (!p->seg_cols.empty() && !m.seg_search) {
     FcpSegLaunch S;

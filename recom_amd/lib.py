@@ -26,6 +26,9 @@ FLAG_HOST_ONLY = 1 << 31  # plan without device resources (layout queries only)
 LAUNCH_KERNELS = {0: "none", 1: "dense", 2: "ragged", 3: "hybrid"}
 LAUNCH_STORES = {0: "nt", 1: "sc1_nt", 4: "plain"}
 LAUNCH_SEGMENT_OFFSETS = {0: "none", 1: "prepass", 2: "search"}
+# fcp_aux_launch_counts: the kernels outside the fused matrix, one counter per instantiation (FCP_AUX_* order)
+AUX_KERNELS = ("segment_offsets", "shard_finalize_v4", "shard_finalize_v2", "shard_finalize_v1",
+               "concat_v4", "concat_v2", "concat_v1", "upload", "h2d_copy")
 
 
 class FcpError(RuntimeError):
@@ -143,7 +146,7 @@ EXPORTS = [
     "fcp_graph_build", "fcp_graph_free", "fcp_placement_assign", "fcp_concat_outputs_scatter_strided",
     "fcp_plan_set_private_streams", "fcp_result_wait", "fcp_result_synchronize", "fcp_plan_set_request_order",
     "fcp_plan_probe_private_streams", "fcp_plan_private_streams_verdict", "fcp_plan_verify_private_streams",
-    "fcp_plan_private_streams_stats", "fcp_plan_last_launch",
+    "fcp_plan_private_streams_stats", "fcp_plan_last_launch", "fcp_plan_last_csr", "fcp_aux_launch_counts",
 ]
 
 _lib = None
@@ -285,10 +288,24 @@ def load() -> C.CDLL:
         L.fcp_plan_set_request_order.argtypes = [C.c_void_p, C.c_int32]
     if hasattr(L, "fcp_plan_last_launch"):
         L.fcp_plan_last_launch.argtypes = [C.c_void_p, C.POINTER(LaunchInfo)]
+    if hasattr(L, "fcp_aux_launch_counts"):
+        L.fcp_plan_last_csr.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_int32]
+        L.fcp_aux_launch_counts.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     if L.fcp_abi_version() != FCP_ABI_VERSION:
         raise ImportError("libfcp_hip.so ABI version mismatch; rebuild")
     _lib = L
     return L
+
+
+def aux_launch_counts(reset: bool = False) -> dict:
+    """``fcp_aux_launch_counts``: process-wide launches of each kernel outside the fused matrix, by ``AUX_KERNELS`` name;
+    ``reset`` zeroes the counters after reading them."""
+    L = load()
+    counts = (C.c_int64 * len(AUX_KERNELS))()
+    n = L.fcp_aux_launch_counts(counts, len(AUX_KERNELS), 1 if reset else 0)
+    if n != len(AUX_KERNELS):
+        raise FcpError(-n if n < 0 else FCP_ERR_UNSUPPORTED, "fcp_aux_launch_counts", f"{n} counters")
+    return dict(zip(AUX_KERNELS, counts[:]))
 
 
 def check(status: int, what: str) -> None:

@@ -309,6 +309,15 @@ class Plan:
                     dense_blocks=li.dense_blocks, ragged_blocks=li.ragged_blocks,
                     segment_offsets=_lib.LAUNCH_SEGMENT_OFFSETS[li.segment_offsets])
 
+    def last_csr(self):
+        """``fcp_plan_last_csr``: (byte offset of the most recent request's segment-offset scratch in its arena, or -1;
+        int32[n_columns] index of each column's range in it, -1 for a column without one).  Read-only diagnostics."""
+        off = C.c_int64()
+        n = self.spec.n_columns
+        base = np.empty(max(n, 1), np.int32)
+        _lib.check(self._L.fcp_plan_last_csr(self.handle, C.byref(off), base.ctypes.data, n), "fcp_plan_last_csr")
+        return off.value, base[:n]
+
 
 @dataclass
 class ProcessOutputs:
@@ -481,12 +490,17 @@ class FeatureColumnProcess:
         return ProcessOutputs(out_ptrs, out_shapes, strides, arena, groups, gshapes)
 
     def shard_finalize(self, concated_inputs, concated_offsets, concated_shapes, inputs, symbols, group: int,
-                       partial_slices, world: int, row_begin: int, row_count: int, stream: Optional[int] = None):
-        """Sum ``world`` partial slices in rank order + mean division."""
+                       partial_slices, world: int, row_begin: int, row_count: int, stream: Optional[int] = None, out=None):
+        """Sum ``world`` partial slices in rank order + mean division; columns with one owner per row take
+        the owner's value.  ``out``: a contiguous float32 [row_count, width] device tensor to write into (its EXTERNAL
+        holes are left alone), else a fresh one."""
         torch = self.torch
         a, _keep = self._args(concated_inputs, concated_offsets, concated_shapes, inputs, symbols, stream)
         width = self.plan.group_width(group)
-        out = torch.empty((row_count, width), dtype=torch.float32, device=self.device)
+        if out is None:
+            out = torch.empty((row_count, width), dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != (row_count, width) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"shard_finalize: out= must be a contiguous float32 [{row_count}, {width}] tensor")
         _lib.check(self._L.fcp_shard_finalize(self.plan.handle, C.byref(a), group, partial_slices.data_ptr(),
                                               world, row_begin, row_count, out.data_ptr(), a.stream),
                    "fcp_shard_finalize")

@@ -115,6 +115,20 @@ int main(void) {
     CHECK(fcp_plan_last_launch(plan, NULL) == FCP_ERR_INVALID_ARGUMENT);
     CHECK(fcp_plan_last_launch(NULL, &li) == FCP_ERR_INVALID_ARGUMENT);
   }
+  { /* where the CSR scratch lies: nothing yet; the kernel launch counters: nothing launched by this process */
+    int64_t csr_off = 7, aux[FCP_AUX_KERNELS + 1];
+    int32_t csr_base[2] = {7, 7};
+    int32_t i;
+    CHECK(fcp_plan_last_csr(plan, &csr_off, csr_base, 2) == FCP_OK && csr_off == -1 && csr_base[0] == -1 && csr_base[1] == -1);
+    CHECK(fcp_plan_last_csr(plan, NULL, NULL, 0) == FCP_OK);
+    CHECK(fcp_plan_last_csr(NULL, &csr_off, NULL, 0) == FCP_ERR_INVALID_ARGUMENT);
+    CHECK(fcp_plan_last_csr(plan, &csr_off, NULL, 1) == FCP_ERR_INVALID_ARGUMENT);
+    aux[FCP_AUX_KERNELS] = 99;
+    CHECK(fcp_aux_launch_counts(aux, FCP_AUX_KERNELS + 1, 1) == FCP_AUX_KERNELS && aux[FCP_AUX_KERNELS] == 99);
+    for (i = 0; i < FCP_AUX_KERNELS; ++i) CHECK(aux[i] == 0);
+    CHECK(fcp_aux_launch_counts(NULL, 0, 0) == FCP_AUX_KERNELS);
+    CHECK(fcp_aux_launch_counts(NULL, 1, 0) < 0);
+  }
   { /* the serving-mode entry points (round 4) from plain C: a plan without a device refuses them, arguments are checked */
     double serial_us = 0.0, lanes_us = 0.0;
     int32_t verdict = 7;

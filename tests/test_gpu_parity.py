@@ -269,9 +269,14 @@ def test_concat_outputs_many_inputs(torch_cuda, oracle):
     from recom_amd.ops import concat_outputs
     rng = np.random.default_rng(0)
     xs = [rng.standard_normal((19, int(d))).astype(np.float32) for d in rng.integers(1, 40, 450)]
+    for x in xs[::7]:                 # -0.0, +-inf, a NaN payload and a subnormal: copies keep every bit
+        x[0, 0] = np.float32(-0.0)
+        x[1, 0] = np.float32(-np.inf)
+        x[2, 0] = np.float32(1e-42)
+        x[-1, -1] = np.uint32(0x7FC01234).view(np.float32)
     got = concat_outputs([torch_cuda.from_numpy(x).cuda() for x in xs])
     torch_cuda.cuda.synchronize()
-    assert np.array_equal(got.cpu().numpy(), oracle.concat_outputs(xs))
+    assert np.array_equal(got.cpu().numpy().view(np.uint32), oracle.concat_outputs(xs).view(np.uint32))
 
 
 def test_bad_ids_read_as_zero_and_are_counted(torch_cuda, oracle):
@@ -366,7 +371,7 @@ def test_row_sharded_partials_and_finalize(torch_cuda, oracle):
         # per-rank partials equal the sharded oracle bit for bit
         want, _ = oracle.process_feature_columns(spec.to_dict(), *packed, [t[rank::world] for t in tabs_np],
                                                  req.symbols)
-        assert np.array_equal(out.groups[0].cpu().numpy(), want[0])
+        assert np.array_equal(out.groups[0].cpu().numpy().view(np.uint32), want[0].view(np.uint32))
         parts.append(out.groups[0].clone())
         ops.append(op)
         shard_tabs.append(tabs)
@@ -382,8 +387,8 @@ def test_row_sharded_partials_and_finalize(torch_cuda, oracle):
     offs = m.spec.column_offsets()
     for k, c in enumerate(m.spec.columns):
         a, b = got[:, offs[k]:offs[k] + c.dim], ref[:, offs[k]:offs[k] + c.dim]
-        if c.form in (1, 3, 4, 5):  # exactly one owner (table-free columns: rank 0): exact
-            assert np.array_equal(a, b)
+        if c.form in (1, 3, 4, 5):  # exactly one owner (table-free columns: rank 0): the same bits
+            assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
         else:
             assert np.abs(a - b).max() < 1e-5
 
@@ -412,13 +417,13 @@ def test_column_sharded_blocks_concat(torch_cuda, oracle):
         torch.cuda.synchronize()
         want, _ = oracle.process_feature_columns(sub.spec.to_dict(), *packed, [tabs_np[i] for i in sub.device_inputs],
                                                  req.symbols)
-        assert np.array_equal(out.groups[0].cpu().numpy(), want[0])
+        assert np.array_equal(out.groups[0].cpu().numpy().view(np.uint32), want[0].view(np.uint32))
         blocks.append(out.groups[0].clone())
     ref = full.groups[0].cpu().numpy()
     for begin, count in batch_slices(ref.shape[0], world):
         got = concat_outputs([b[begin:begin + count].contiguous() for b in blocks])
         torch.cuda.synchronize()
-        assert np.array_equal(got.cpu().numpy(), ref[begin:begin + count])
+        assert np.array_equal(got.cpu().numpy().view(np.uint32), ref[begin:begin + count].view(np.uint32))
 
 
 def _graph_through_hip(torch, gd, feeds, variables, fetches, tmp_path, host_concat="passthrough", staged=False, private_streams=0):

@@ -636,6 +636,41 @@ def test_hot_kernels_keep_full_occupancy(tmp_path):
     assert kinds["sc1 nt"] >= 4 and kinds["nt"] >= 4 and kinds["plain"] >= 4, kinds
 
 
+def test_every_kernel_of_the_code_object_has_a_cell(tmp_path):
+    """The device code of fcp_kernels.hip holds exactly the fused instantiations of tests/kernel_variant_cases.py and the
+    nine others of tests/aux_kernel_cases.py (each with a launch counter): a kernel added without a cell fails here."""
+    import shutil
+    import subprocess
+    import aux_kernel_cases as A
+    import kernel_variant_cases as K
+    from recom_amd import lib
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not (os.path.exists(hipcc) or shutil.which("hipcc")):
+        pytest.skip("no hipcc")
+    asm = tmp_path / "k.s"
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "-O3", "--offload-device-only", "-S",
+                        os.path.join(ROOT, "recom_amd", "csrc", "fcp_kernels.hip"), "-o", str(asm)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    found = []
+    for mangled in re.findall(r"^\s*\.amdhsa_kernel (\S+)", asm.read_text(), re.M):
+        m = re.search(r"\d+(fcp_[a-z0-9_]+_kernel)(?:I((?:L[ib]\d+E)+)E)?", mangled)
+        assert m, mangled
+        args = [("true" if v == "1" else "false") if t == "b" else v for t, v in re.findall(r"L([ib])(\d+)E", m.group(2) or "")]
+        found.append(m.group(1) + (f"<{', '.join(args)}>" if args else ""))
+    assert len(found) == len(set(found)), found
+
+    def fused(kernel, vec, rpw, sharded):
+        s = "true" if sharded else "false"
+        return f"fcp_ragged_kernel<{vec}, {s}>" if kernel == "ragged" else f"fcp_{kernel}_kernel<{vec}, {rpw}, {s}>"
+    want_fused = {fused(*K.instantiation(c)) for c in K.cells()}
+    assert len(want_fused) == 42
+    assert tuple(A.AUX_INSTANTIATIONS) == lib.AUX_KERNELS          # one launch counter per kernel, in the ABI's order
+    want = want_fused | set(A.AUX_INSTANTIATIONS.values())
+    assert len(want) == 51
+    assert set(found) == want, (sorted(set(found) - want), sorted(want - set(found)))
+
+
 def test_shard_exchange_entry_points_without_a_gpu():
     """The exchange under the C ABI (fcp_shard.hip): the batch split equals recom_amd.shard.batch_slices; bad
     arguments are refused before RCCL or a device is touched."""

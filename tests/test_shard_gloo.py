@@ -51,6 +51,10 @@ def _worker(rank, world, port, out_dir):
         acc = np.zeros((count, slices.shape[2]), np.float32)
         for w in range(world):  # rank order, fp32 — what fcp_shard_finalize does
             acc = acc + slices[w].numpy()
+        owner_bits = np.bitwise_or.reduce(slices.numpy().view(np.uint32), axis=0)
+        for k, c in enumerate(spec.columns):  # one owner per row: the owner's bits (every other rank wrote +0.0)
+            if c.concat_group == 0 and c.form in (1, 3, 4, 5):
+                acc[:, offs[k]:offs[k] + c.dim] = owner_bits[:, offs[k]:offs[k] + c.dim].view(np.float32)
         for k, c in enumerate(spec.columns):
             if c.concat_group == 0 and c.form == 2 and c.combiner == 2:
                 rows = int(case.symbols[c.rows_arg])
@@ -75,7 +79,8 @@ def _worker(rank, world, port, out_dir):
             continue
         a, b = got[:, offs[k]:offs[k] + c.dim], ref[:, offs[k]:offs[k] + c.dim]
         if c.form in (1, 3, 4, 5):
-            assert np.array_equal(a, b), f"rank {rank} column {k}: single-owner column must be exact"
+            assert np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32)), \
+                f"rank {rank} column {k}: single-owner column must be exact"
         else:
             assert np.abs(a - b).max(initial=0) < 1e-5, f"rank {rank} column {k}"
     gathered = path.all_gather_batch(mine, rows).numpy()
