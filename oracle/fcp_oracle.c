@@ -659,8 +659,8 @@ static int64_t process_column(const orc_plan_t *p, int32_t k, const int8_t *blob
   /* count globally-bad ids once, then map to the local shard */
   if (sharded) {
     if (!scatter)
-      for (int64_t i = 0; i < nnz; ++i)
-        if (ids[i] < 0 || ids[i] >= c->vocab) ++bad;
+      for (int64_t i = 0; i < nnz; ++i) /* (an id the filter drops never reaches the lookup: not counted, as unsharded) */
+        if ((ids[i] < 0 || ids[i] >= c->vocab) && !(keep && !keep[i])) ++bad;
     shard_ids(p, ids, nnz, c->vocab);
   }
   const float *table = tables[c->table_input];

@@ -343,10 +343,16 @@ static_assert(offsetof(FcpColStatic, flags) == 32 && offsetof(FcpColStatic, tabl
 // the interval test of Addons>SelectValue / Addons>GatherIndiceValue /
 // Addons>GatherValueGenIndice (select_value_ops.cc:33-56 and siblings), fused: closed intervals,
 // `lo <= id && id <= hi` (the reference's `||` accepts everything).  Returns the id the
-// lookup sees, or kDroppedId: the filter removed it.  Out of line and fed from the per-column side table
+// lookup sees and, next to it, whether the filter removed it — a flag of its own, not a reserved id: every
+// int64 is a legal id, interval end and substitute (INT64_MIN inside a filter's interval is kept, reaches the
+// lookup, reads zeros and counts in a mean).  Out of line and fed from the per-column side table
 // (FcpLaunch::xforms) on purpose: columns without a transform — nearly all — pay one compare, no registers
 // and no record bytes for it (inlined with the intervals in the column record it cost S2 2 us of 29: 76 VGPRs).
-constexpr int64_t kDroppedId = INT64_MIN;
+// The pair comes back in registers (three VGPRs), nothing goes through memory.
+struct XformedId {
+  int64_t id;
+  uint32_t dropped;
+};
 
 // ---- Fingerprint64 of a short byte string (FarmHash farmhashna::Hash64, lengths 1..32; TensorFlow's
 // StringToHashBucketFast, core/kernels/string_to_hash_bucket_fast_op.h) -----------------------------------
@@ -407,19 +413,20 @@ __device__ uint64_t fingerprint64_decimal(int64_t value) {
   return hash_len16(rot64(a + b, 43) + rot64(c, 30) + e, a + rot64(b + k2, 18) + c, mul);
 }
 
-__device__ __attribute__((noinline)) int64_t apply_xform(uint32_t xform, const FcpXform *xf, int64_t id) {
+__device__ __attribute__((noinline)) XformedId apply_xform(uint32_t xform, const FcpXform *xf, int64_t id) {
   const FCP_GLOBAL FcpXform *x = as_global(xf);
   if (xform & FCP_XFORM_HASH_BIT) id = (int64_t)(fingerprint64_decimal(id) % (uint64_t)x->hash_buckets);
   const unsigned mode = xform & 3u;
-  if (mode == FCP_XFORM_NONE) return id;
+  if (mode == FCP_XFORM_NONE) return {id, 0u};
   bool in = id >= x->lo0 && id <= x->hi0;
   const int n = (int)((xform & ~FCP_XFORM_HASH_BIT) >> 2);
   for (int i = 1; i < n && !in; ++i) {
     const FCP_GLOBAL int64_t *e = as_global(x->extra) + 2 * (i - 1);
     in = id >= e[0] && id <= e[1];
   }
-  if (in) return id;
-  return mode == FCP_XFORM_FILTER ? kDroppedId : x->sub;
+  if (in) return {id, 0u};
+  if (mode == FCP_XFORM_FILTER) return {id, 1u};
+  return {x->sub, 0u};
 }
 
 // The index expression the reference inlines per column (EmitInputInline,
@@ -449,8 +456,9 @@ __device__ __forceinline__ uint32_t slot_offset_from_raw(const LdsCol &c, const 
   }
   bad = false;
   if (c.xform) { // rare
-    id = apply_xform(c.xform, xf, id);
-    if (id == kDroppedId) return kFiltered;
+    const XformedId x = apply_xform(c.xform, xf, id);
+    if (x.dropped) return kFiltered;
+    id = x.id;
   }
   bad = (uint64_t)id >= (uint64_t)c.vocab;
   if (bad) return kBadRow;

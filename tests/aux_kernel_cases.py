@@ -286,7 +286,8 @@ def finalize_plan(vec: int):
 
 def finalize_tables(spec, rng) -> List[np.ndarray]:
     """Table 0 (gather) and 1 (scatter) carry -0.0, NaN payloads and subnormals in whole rows; the pooled tables are
-    normal values (a NaN's payload through an add is the hardware's business, not the finalize's)."""
+    normal values here — pooled sums and means over non-finite and subnormal values, through the finalize's adds as well,
+    are the cells of tests/value_edge_cases.py (where a NaN an add produced is compared by class, not by payload)."""
     dims = {}
     vocab = {}
     for c in spec.columns:

@@ -107,13 +107,28 @@ def random_model(rng, dense_only=False, extended=True, n_groups_fixed=None, form
                       xform_hi=tuple(int(v) for v in his), xform_substitute=int(rng.integers(-1, vocab + 1)))
         oob = extended and not hashb and rng.random() < 0.25
         xf["hash_buckets"] = hashb
+        # value edges (tests/value_edge_cases.py pins them as cells), with small probability and from a generator of their
+        # own, so that the plan a seed draws is otherwise what it was: an interval end or the substitute at an int64
+        # extreme, hashed ids of short decimal length
+        short = False
+        if extended:
+            erng = np.random.default_rng([20250, len(cols), vocab, dim, hashb])
+            if xf["xform_mode"] != XFORM_NONE and len(xf["xform_lo"]) and erng.random() < 0.15:
+                j = int(erng.integers(0, len(xf["xform_lo"])))
+                end, v = ("xform_lo", -2 ** 63) if erng.random() < 0.5 else ("xform_hi", 2 ** 63 - 1)
+                xf[end] = tuple(v if i == j else x for i, x in enumerate(xf[end]))
+            if xf["xform_mode"] == XFORM_SELECT and erng.random() < 0.15:
+                xf["xform_substitute"] = int(erng.choice([-2 ** 63, 2 ** 63 - 1]))
+            short = bool(hashb) and erng.random() < 0.3
 
-        def draw_ids(r, n, src=src, vocab=vocab, bnd=bnd, hashb=hashb, oob=oob):
+        def draw_ids(r, n, src=src, vocab=vocab, bnd=bnd, hashb=hashb, oob=oob, short=short):
             if src == IDS_F32_BUCKETIZE:
                 return random_values(r, n, bnd) if extended else r.uniform(-12, 12, n).astype(np.float32)
             dt = np.int64 if src == IDS_I64 else np.int32
             if hashb:
                 info = np.iinfo(dt)
+                if short:       # decimal strings of 1 to 8 bytes: the short branches of Fingerprint64
+                    return (r.integers(0, 10 ** r.integers(1, 8, n)) * r.choice([1, 1, -1], n)).astype(dt)
                 return r.integers(info.min, info.max, n, dtype=dt, endpoint=True)
             ids = r.integers(0, vocab, n).astype(dt)
             if oob and n:

@@ -636,6 +636,44 @@ def test_hot_kernels_keep_full_occupancy(tmp_path):
     assert kinds["sc1 nt"] >= 4 and kinds["nt"] >= 4 and kinds["plain"] >= 4, kinds
 
 
+def test_float_modes_and_the_ieee_division_of_the_pooling_kernels(tmp_path):
+    """What the pooled special values of tests/value_edge_cases.py rest on, read from the gfx950 code object (no GPU needed):
+    every fused kernel and every fcp_shard_finalize_kernel<V> runs with fp32 subnormals kept on input and output
+    (float_denorm_mode_32 = 3) and in IEEE mode, and a mean divides with the IEEE sequence (v_div_scale_f32 ..
+    v_div_fixup_f32) — a flag that flushes subnormals, or turns `acc / n` into a multiplication by a reciprocal, fails here.
+    The kernels that divide: the unsharded ragged and hybrid ones and the finalize (a row-sharded rank emits sums)."""
+    import re
+    import shutil
+    import subprocess
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not (os.path.exists(hipcc) or shutil.which("hipcc")):
+        pytest.skip("no hipcc")
+    asm = tmp_path / "k.s"
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "-O3", "--offload-device-only", "-S",
+                        os.path.join(ROOT, "recom_amd", "csrc", "fcp_kernels.hip"), "-o", str(asm)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    text = asm.read_text()
+    seen = {"fused": 0, "finalize": 0, "dividing": 0}
+    for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", text, re.S):
+        name, desc = m.group(1), m.group(2)
+        fused = any(k in name for k in ("fcp_dense_kernel", "fcp_ragged_kernel", "fcp_hybrid_kernel"))
+        finalize = "fcp_shard_finalize_kernel" in name
+        if not (fused or finalize):
+            continue
+        seen["fused" if fused else "finalize"] += 1
+        assert re.search(r"\.amdhsa_float_denorm_mode_32 3\b", desc), f"{name}: fp32 subnormals are flushed"
+        assert re.search(r"\.amdhsa_ieee_mode 1\b", desc), f"{name}: not in IEEE mode"
+        label = re.search(r"^" + re.escape(name) + r":", text, re.M)
+        assert label, name
+        body = text[label.end():m.start()]                   # (the kernel's descriptor follows its code)
+        divides = finalize or (("fcp_ragged_kernel" in name or "fcp_hybrid_kernel" in name) and "ELb0E" in name)
+        if divides:
+            seen["dividing"] += 1
+            assert "v_div_scale_f32" in body and "v_div_fixup_f32" in body, f"{name}: the mean is not an IEEE division"
+    assert seen == {"fused": 42, "finalize": 3, "dividing": 3 + 9 + 3}, seen
+
+
 def test_every_kernel_of_the_code_object_has_a_cell(tmp_path):
     """The device code of fcp_kernels.hip holds exactly the fused instantiations of tests/kernel_variant_cases.py and the
     nine others of tests/aux_kernel_cases.py (each with a launch counter): a kernel added without a cell fails here."""

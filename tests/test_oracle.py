@@ -9,6 +9,7 @@ NumPy restatement, (4) the reference's dim>20 summation order restated in
 outputs of the reference's OWN device templates, compiled unmodified for gfx950
 and run on an MI355X (make_ref_device_goldens.py) — bit for bit, see the last test.
 """
+import dataclasses
 import os
 
 import numpy as np
@@ -621,3 +622,201 @@ def test_kernel_variant_cells_cover_every_instantiation_and_store_policy():
             assert (inst, store, False) in covered, (inst, store)
             if inst[0] != "ragged":
                 assert (inst, store, True) in covered, (inst, store)
+
+
+# ---- value edges (tests/value_edge_cases.py): the C oracle against the case module's NumPy restatements ----------------
+def _id_cells():
+    import value_edge_cases as E
+    return E.id_cells()
+
+
+def _oracle_ranks(oracle, E, case, world, t):
+    """[(rank, oracle groups, oracle bad ids, restated groups, restated bad ids)] of request t, every rank of `world`."""
+    from recom_amd.ops import concat_inputs
+    inputs, symbols = case.requests[t]
+    blob, offsets, shapes = concat_inputs(inputs)
+    out = []
+    for rank in range(world):
+        spec = case.spec.with_shard(rank, world) if world > 1 else case.spec
+        tabs = [np.ascontiguousarray(x[rank::world]) for x in case.tables]
+        got, bad = oracle.process_feature_columns(spec.to_dict(), blob, offsets, shapes, tabs, symbols)
+        want, want_bad = E.restate(case.spec, case.tables, inputs, symbols, rank, world)
+        out.append((rank, got, bad, want, want_bad))
+    return out
+
+
+@pytest.mark.parametrize("cell", _id_cells(), ids=[c.id for c in _id_cells()])
+def test_id_path_cells_oracle_equals_the_numpy_restatement(oracle, cell):
+    """Every id-path cell: the C oracle's outputs (every rank of a sharded cell) equal the case module's NumPy restatement
+    (np_fingerprint64 % buckets, plain interval logic) bit for bit, and count the same bad ids."""
+    import value_edge_cases as E
+    case = E.id_case(cell)
+    for t in range(2):                           # (request 2 is request 0 again)
+        for rank, got, bad, want, want_bad in _oracle_ranks(oracle, E, case, cell.world, t):
+            for g in range(case.spec.n_groups):
+                E.assert_same(got[g], want[g], (cell.id, t, rank, g), E.copy_mask(case.spec, g))
+            assert bad == want_bad, (cell.id, t, rank, bad, want_bad)
+
+
+def test_id_path_cells_keep_their_promises():
+    """The generator: every value of every axis, every (hash, mode) pair, every interval list under both transforms; each
+    hashed cell's ids have decimal strings at both ends of every length branch of Fingerprint64 the id type can reach
+    (1-3, 4-7, 8-16, 17-20 bytes; int32: up to 11), the digit-count edges and the extremes; hashed outputs are buckets."""
+    import itertools
+    import value_edge_cases as E
+    cells = E.id_cells()
+    assert len({c.id for c in cells}) == len(cells)
+    for axis, values in (("src", E.SOURCES), ("hash", E.HASHES), ("mode", E.MODES), ("ivals", E.INTERVALS),
+                         ("sub", E.SUBSTITUTES), ("world", E.WORLDS), ("dim", (1, 2, 4))):
+        assert {getattr(c, axis) for c in cells} == set(values), axis
+    assert {(c.hash, c.mode) for c in cells} == set(itertools.product(E.HASHES, E.MODES))
+    assert {(c.ivals, c.mode) for c in cells} >= set(itertools.product(E.INTERVALS, ("select", "filter")))
+    assert {(c.hash, c.world) for c in cells if c.hash} >= {(h, w) for h in E.HASHES[1:] for w in (1, 2)}
+    assert any(c.hash and c.mode == "filter" and c.world > 1 and c.vocab < c.hash for c in cells)   # hash -> filter -> vocabulary -> split
+    for src in ("i64", "i32"):
+        ids = E._hashed_ids(src)
+        lens = {len(str(int(v))) for v in ids}
+        assert lens >= set(E.HASH_LEN_EDGES[src]), (src, sorted(lens))
+        for sign in (1, -1):
+            for n in range(1, 20 if src == "i64" else 11):
+                assert sum(1 for v in ids if len(str(abs(int(v)))) == n and (int(v) < 0) == (sign < 0)) >= 4 or \
+                    (n == 1 and sign == 1) or (src == "i32" and n == 10), (src, sign, n)
+        have = set(int(v) for v in ids)
+        kmax = 18 if src == "i64" else 9
+        assert all(s * (10 ** k + d) in have for k in range(kmax + 1) for d in (-1, 0, 1) for s in (1, -1))
+        assert {0, -1, E.I32_MIN, E.I32_MAX} <= have and (src == "i32" or {E.I64_MIN, E.I64_MAX, 1 << 31, 1 << 32} <= have)
+    cell = next(c for c in cells if c.hash == 997 and c.mode == "none")
+    case = E.id_case(cell)
+    inputs, symbols = case.requests[0]
+    want, _ = E.restate(case.spec, case.tables, inputs, symbols)
+    buckets = np.asarray([O.np_fingerprint64(str(int(v)).encode()) % 997 for v in inputs[0]])
+    assert np.array_equal(want[0][:, 0], np.where(buckets < cell.vocab, buckets, 0).astype(np.float32))
+
+
+def test_int64_min_is_an_id_like_any_other(oracle):
+    """INT64_MIN inside a filter's interval is kept: it reaches the lookup, is outside the vocabulary, reads zeros and counts
+    in the mean's divisor and as a bad id; as a SELECT substitute, or selected by an interval, it is counted as a bad id."""
+    import value_edge_cases as E
+    from recom_amd.ops import concat_inputs
+    spec, tables, inputs, symbols, want, want_bad = E.min_collision_case()
+    blob, offsets, shapes = concat_inputs(inputs)
+    got, bad = oracle.process_feature_columns(spec.to_dict(), blob, offsets, shapes, tables, symbols)
+    assert np.array_equal(got[0], want) and bad == want_bad == 1
+    res, rbad = E.restate(spec, tables, inputs, symbols)
+    assert np.array_equal(res[0], want) and rbad == 1
+    f64 = O.np_process_feature_columns(spec.to_dict(), blob, offsets, shapes, tables, symbols)
+    assert np.array_equal(f64[0], want.astype(np.float64))
+    col = spec.columns[0]
+    for xf in (dict(xform_lo=(0,), xform_hi=(5,), xform_substitute=E.I64_MIN),
+               dict(xform_lo=(E.I64_MIN, 0), xform_hi=(E.I64_MIN + 1, 5), xform_substitute=E.I64_MIN)):
+        sel = dataclasses.replace(spec, columns=[dataclasses.replace(col, xform_mode=E.XFORM_SELECT, **xf)])
+        got, bad = oracle.process_feature_columns(sel.to_dict(), blob, offsets, shapes, tables, symbols)
+        res, rbad = E.restate(sel, tables, inputs, symbols)
+        assert np.array_equal(got[0], np.asarray([[3.5, 4.0], [3.5, 4.0]], np.float32)) and np.array_equal(res[0], got[0])
+        assert bad == rbad == 2
+
+
+def _special_cells():
+    import value_edge_cases as E
+    return E.special_cells()
+
+
+@pytest.mark.parametrize("cell", _special_cells(), ids=[c.id for c in _special_cells()])
+def test_pooled_special_cells_oracle_equals_the_numpy_restatement(oracle, cell):
+    """Pooled specials: the C oracle (every rank's partials of a sharded cell) equals the float32 NumPy restatement — adds
+    one by one in id order from +0.0, the division in float32 — bit for bit wherever that is not NaN, and is NaN where it
+    is; the float64 restatement agrees on which elements are NaN and on the infinities it has."""
+    import value_edge_cases as E
+    from recom_amd.ops import concat_inputs
+    case = E.special_case(cell.kernel, cell.vec)
+    for t in range(2):
+        for rank, got, bad, want, want_bad in _oracle_ranks(oracle, E, case, cell.world, t):
+            for g in range(case.spec.n_groups):
+                E.assert_same(got[g], want[g], (cell.id, t, rank, g), E.copy_mask(case.spec, g))
+            assert bad == want_bad, (cell.id, t, rank, bad, want_bad)
+        if cell.world == 1:
+            inputs, symbols = case.requests[t]
+            blob, offsets, shapes = concat_inputs(inputs)
+            with np.errstate(all="ignore"):
+                f64 = O.np_process_feature_columns(case.spec.to_dict(), blob, offsets, shapes, case.tables, symbols)
+            for g in range(case.spec.n_groups):
+                assert np.array_equal(np.isnan(f64[g]), np.isnan(want[g])), (cell.id, t, g)
+                inf = np.isinf(f64[g])
+                assert np.array_equal(f64[g][inf], want[g][inf].astype(np.float64)), (cell.id, t, g)
+
+
+@pytest.mark.parametrize("kernel,vec", [(k, v) for k in ("ragged", "hybrid") for v in (1, 2, 4)])
+def test_pooled_special_cases_keep_their_promises(kernel, vec):
+    """On the reference alone: every outcome of the list shows in at least eight output elements of the plan — unsharded,
+    and after the finalize of world 2 and world 3, where inf - inf, the FLT_MAX overflow and a subnormal sum must come out
+    of the cross-rank add itself —, NaN elements are at most one eighth of the pooled elements of any request, every bag
+    length of the list and a long bag occur, and the layout lands in the kernel it names."""
+    import value_edge_cases as E
+    case = E.special_case(kernel, vec)
+    spec = case.spec
+    pooled = [c.form == E.FORM_SEGMENT_REDUCE for c in spec.columns]
+    assert any(pooled) and (kernel == "hybrid") == (not all(pooled))
+    assert np.gcd.reduce([c.dim for c in spec.columns]) == vec
+    offs = spec.column_offsets()
+    for world in E.WORLDS:
+        results = []
+        for t in range(E.N_REQUESTS):
+            inputs, symbols = case.requests[t]
+            if world == 1:
+                res, _ = E.restate(spec, case.tables, inputs, symbols)
+            else:
+                parts = [E.restate(spec, case.tables, inputs, symbols, r, world)[0] for r in range(world)]
+                res = [E.finalized(spec, g, np.stack([p[g] for p in parts]), inputs, int(symbols[g]))
+                       for g in range(spec.n_groups)]
+                # the cross-rank add itself: no single rank's partial already holds the outcome
+                for k, ocs in case.outcomes[t].items():
+                    c = spec.columns[k]
+                    sl = slice(offs[k], offs[k] + c.dim)
+                    for r, o in enumerate(ocs):
+                        if o == "inf_minus_inf":
+                            assert np.isnan(res[c.concat_group][r, sl]).all() and \
+                                not any(np.isnan(p[c.concat_group][r, sl]).any() for p in parts), (kernel, vec, world, t, k, r)
+                        if o == "fmax_cross_rank":
+                            assert (res[c.concat_group][r, sl] == np.inf).all() and \
+                                not any(np.isinf(p[c.concat_group][r, sl]).any() for p in parts), (kernel, vec, world, t, k, r)
+                        if o == "subnormal_sum":
+                            assert sum(1 for p in parts if p[c.concat_group][r, sl].any()) >= 2, (kernel, vec, world, t, k, r)
+            share = E.nan_share(case, res)
+            assert share <= 1 / 8, (kernel, vec, world, t, share)
+            results.append(res)
+        counts = E.outcome_counts(case, results)
+        assert all(n >= 8 for n in counts.values()), (kernel, vec, world, counts)
+    lens = set()
+    for (inputs, symbols), oc in zip(case.requests, case.outcomes):
+        for k in oc:
+            c = spec.columns[k]
+            lens |= set(np.diff(E.row_offsets(c, inputs[c.seg_input], int(symbols[c.concat_group]))).tolist())
+    assert lens >= set(E.BAG_LENS) and max(lens) > 384
+
+
+def test_big_sharded_case_keeps_its_promises():
+    """The table of 2^32 + 2^16 rows over three ranks: ids on both sides of 2^31 - 1 (where the split changes from a 32-bit
+    to a 64-bit division) and of 2^32, decoy rows distinct from the true rows and from each other, inside each rank's table,
+    and the ranks' expected partials adding up to the unsharded answer."""
+    import value_edge_cases as E
+    spec, requests, value, true, decoy = E.big_case()
+    ids = set(int(i) for i in requests[0][0][0])
+    for c in (1 << 31, 1 << 32):
+        assert {c + d for d in range(-2, 3)} <= ids
+    assert {E.BIG_VOCAB - 1, E.BIG_VOCAB, -1, 0} <= ids and E.BIG_VOCAB == (1 << 32) + (1 << 16)
+    assert all(E.big_rows(r) < (1 << 32) - 3 and E.big_rows(r) * 4 < (16 << 30) for r in range(E.BIG_WORLD))
+    vals = [float(v) for d in true + decoy for v in d.values()]
+    assert len(set(vals)) == len(vals)
+    for r in range(E.BIG_WORLD):
+        assert not set(true[r]) & set(decoy[r]) and all(0 <= row < E.big_rows(r) for row in list(true[r]) + list(decoy[r]))
+        assert len(decoy[r]) >= len(value)
+        for i, v in value.items():          # where a truncated id and a 32-bit division would read: never the true value
+            wrong = (i % (1 << 32)) // E.BIG_WORLD
+            if i >= (1 << 32):
+                assert {**true[r], **decoy[r]}.get(wrong) != v, (r, i)
+    for inputs, symbols in requests[:2]:
+        whole, bad = E.big_expected(value, inputs, 0, 1)
+        parts = [E.big_expected(value, inputs, r, E.BIG_WORLD) for r in range(E.BIG_WORLD)]
+        assert all(p[1] == bad for p in parts) and bad >= 3
+        for g in range(2):
+            assert np.array_equal(sum(p[0][g].astype(np.float64) for p in parts), whole[g].astype(np.float64))
