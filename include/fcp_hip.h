@@ -66,8 +66,9 @@ enum {
   /* GatherV2(table, ids): out[i,:] = W[ids[i],:]
    * cuda_emitter.cc:250-293 (GatherRowsToGlbMem), driver :1246-1330 */
   FCP_FORM_GATHER = 1,
-  /* SparseSegment{Sum,Mean}[WithNumSegments](table, ids, seg_ids, B)
-   * cuda_emitter.cc:402-501, :564-661 (dim<=20) and :768-962 (dim>20) */
+  /* SparseSegment{Sum,Mean,SqrtN}[WithNumSegments](table, ids, seg_ids, B)
+   * cuda_emitter.cc:402-501, :564-661 (dim<=20) and :768-962 (dim>20); SqrtN and per-id weights
+   * (fcp_column_ext_t::weights_input1) have no reference counterpart */
   FCP_FORM_SEGMENT_REDUCE = 2,
   /* ScatterNd(rows, GatherV2(table, ids), [B,dim]): zero-fill, then
    * out[rows[i],:] = W[ids[i],:]   cuda_emitter.cc:296-345, :1332-1442
@@ -97,7 +98,12 @@ enum {
   FCP_FORM_EXTERNAL = 6
 };
 
-enum { FCP_COMBINER_NONE = 0, FCP_COMBINER_SUM = 1, FCP_COMBINER_MEAN = 2 };
+/* The combiners of TensorFlow's embedding columns (embedding_lookup_sparse): the bag's rows are added in id order from
+ * +0.0f; MEAN divides by the number of ids that reached the lookup, SQRTN (SparseSegmentSqrtN) by the correctly rounded
+ * float32 square root of that number — one IEEE float32 division per element.  With per-id weights
+ * (fcp_column_ext_t::weights_input1) the denominators are the sum of the weights and the square root of the sum of
+ * their squares.  A zero denominator gives a row of +0.0 (TF's div_no_nan).  SQRTN: FCP_FORM_SEGMENT_REDUCE only. */
+enum { FCP_COMBINER_NONE = 0, FCP_COMBINER_SUM = 1, FCP_COMBINER_MEAN = 2, FCP_COMBINER_SQRTN = 3 };
 
 /* How the id stream of a column is stored in the blob (what EmitInputInline
  * folds into the index expression, cuda_emitter.cc:1769-1949). */
@@ -303,7 +309,15 @@ typedef struct fcp_column_ext {
   int32_t seg_map_n;        /* 0 = none, else 1..FCP_SEG_MAP_MAX coordinates  */
   int32_t seg_map_sym;      /* symbol index, or -1                            */
   int32_t seg_map_sym_slot; /* 0..3: seg_map_mul[slot]; 4: seg_map_div        */
-  int32_t reserved0;
+  /* 1 + the host-input index of the column's per-id weights, 0 = unweighted (an all-zero record stays "no extension"):
+   * float32, one per id, in the order of the ids — sp_weights of embedding_lookup_sparse / weighted_categorical_column,
+   * i.e. the TF op sequence GatherV2 -> Mul(rows, weights) -> SegmentSum [-> div_no_nan by SegmentSum(weights) (mean) or
+   * by Sqrt(SegmentSum(weights^2)) (sqrtn)].  Every gathered row is multiplied by its weight — a rounded product, then a
+   * rounded add, never a fused multiply-add — in id order.  An id the column's FILTER drops contributes neither a term nor
+   * a weight; an id outside [0, vocab) reads zeros and its weight counts in the denominator.  FCP_FORM_SEGMENT_REDUCE
+   * only, any segment encoding (a folded SparseReshape included); the tensor holds exactly as many elements as the ids
+   * tensor (else the request returns FCP_ERR_SHAPE_MISMATCH). */
+  int32_t weights_input1;
   int64_t seg_map_mul[FCP_SEG_MAP_MAX];
   int64_t seg_map_div;
   int64_t reserved1[2];
@@ -322,7 +336,9 @@ int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext,
  *   hi1 ..." to every column line; version 3 files may end with a stage section
  *   (fcp_plan_file_stage_info) that tells Addons>ConcatInputs how to pack;
  *   version 4 files may carry, before it, "segmaps M" + M lines "column n sym
- *   slot mul0 mul1 mul2 mul3 div" (fcp_column_ext_t::seg_map_*).
+ *   slot mul0 mul1 mul2 mul3 div" (fcp_column_ext_t::seg_map_*); version 5 files
+ *   (plans with per-id weights or FCP_COMBINER_SQRTN) carry, before both,
+ *   "weights M" + M lines "column input" (fcp_column_ext_t::weights_input1 - 1).
  * `flags`: fcp_plan_desc_t::flags.  FCP_ERR_INVALID_ARGUMENT for a missing or
  * malformed file. */
 int fcp_plan_create_from_file(const char *path, int32_t device, uint32_t flags,
@@ -400,11 +416,15 @@ int fcp_plan_read_bad_ids(fcp_plan_t *plan, void *stream, int64_t *count);
  * the request of fcp_shard_step_run) — so a test can assert which instantiation it reached.  The request path records
  * it with relaxed stores and no lock: while host threads issue requests on the plan concurrently the fields may come
  * from different requests.  Before the first request: kernel FCP_LAUNCH_NONE, and zero block counts. */
-enum { FCP_LAUNCH_NONE = 0, FCP_LAUNCH_DENSE = 1, FCP_LAUNCH_RAGGED = 2, FCP_LAUNCH_HYBRID = 3 };
+enum {
+  FCP_LAUNCH_NONE = 0, FCP_LAUNCH_DENSE = 1, FCP_LAUNCH_RAGGED = 2, FCP_LAUNCH_HYBRID = 3,
+  /* the ragged body with per-id weights and the sqrtn combiner: every span of a plan that has a weighted or SQRTN column */
+  FCP_LAUNCH_RAGGED_WEIGHTED = 4
+};
 enum { FCP_LAUNCH_STORE_NT = 0, FCP_LAUNCH_STORE_SC1_NT = 1, FCP_LAUNCH_STORE_PLAIN = 4 };
 enum { FCP_LAUNCH_SEG_NONE = 0, FCP_LAUNCH_SEG_PREPASS = 1, FCP_LAUNCH_SEG_SEARCH = 2 };
 typedef struct fcp_launch_info {
-  int32_t kernel;           /* FCP_LAUNCH_*: no kernel (empty request), dense, ragged, or the hybrid of the two */
+  int32_t kernel;           /* FCP_LAUNCH_*: no kernel (empty request), dense, ragged, the hybrid of the two, or the weighted ragged kernel */
   int32_t vec;              /* floats per slot (V of the instantiation): the gcd of the plan's column dims, 1 | 2 | 4 */
   int32_t rows_per_wave;    /* dense body (R of the instantiation): 1 | 2 | 4 */
   int32_t store_policy;     /* FCP_LAUNCH_STORE_*: output stores `nt`, write-through `sc1 nt`, or plain */

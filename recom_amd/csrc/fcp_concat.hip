@@ -211,7 +211,7 @@ int fcp_shard_finalize(fcp_plan_t *p, const fcp_process_args_t *a, int32_t group
   void *scratch = nullptr;
   bool need_csr = false;
   for (int k : p->seg_cols)
-    if (p->cols[k].d.form == FCP_FORM_SEGMENT_REDUCE && p->cols[k].d.combiner == FCP_COMBINER_MEAN) need_csr = true;
+    if (p->cols[k].d.form == FCP_FORM_SEGMENT_REDUCE && p->cols[k].d.combiner != FCP_COMBINER_SUM) need_csr = true; // MEAN, SQRTN: a denominator per row
   if (need_csr) {
     if (!a->malloc_temp) return fail(FCP_ERR_INVALID_ARGUMENT, "malloc_temp is required for mean columns with segment ids");
     const int64_t bytes = m.arena_bytes - m.csr_arena_off;
@@ -238,7 +238,7 @@ int fcp_shard_finalize(fcp_plan_t *p, const fcp_process_args_t *a, int32_t group
     if (e) return hip_fail("segment-offsets launch", (hipError_t)e);
   }
   const int e = fcp_launch_shard_finalize(L, group, static_cast<const float *>(partial_slices), world, row_begin,
-                                          row_count, static_cast<float *>(out), p->vec, stream);
+                                          row_count, static_cast<float *>(out), p->vec, stream, slot_weights(p, slot->d_dyn));
   if (e) return hip_fail("shard-finalize launch", (hipError_t)e);
   if (install) { // the descriptors were installed by this call
     HIP_TRY(hipEventRecord(slot->done, stream));

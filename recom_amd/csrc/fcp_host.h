@@ -51,6 +51,7 @@ struct HostColumn {
   fcp_column_desc_t d;
   fcp_column_ext_t ext = {}; // extensions (segment-id map); all zeros = none
   std::vector<float> boundaries;
+  int32_t weights_input = -1; // host input of the per-id weights (fcp_column_ext_t::weights_input1 - 1), or -1
   std::vector<int64_t> xf_lo, xf_hi; // id transform intervals (closed)
   int64_t xf_const_off = -1;         // byte offset in the const buffer of intervals 1.. as (lo, hi) pairs
   int32_t out_off = 0;
@@ -260,6 +261,12 @@ struct fcp_plan {
   FcpXform *d_xforms = nullptr; // per column, only for plans with id transforms
   FcpSegMap *d_segmaps = nullptr; // per column, only for plans with segment-id maps
   bool has_seg_map = false;
+  // Per-id weights / the sqrtn combiner (fcp_weighted.hip).  has_weights: some pooled column has weights — every descriptor
+  // slot then carries, behind its FcpColDyn records, one int64 per column (concat order): the byte offset of the column's
+  // weights in the request's blob, or -1 (shape-dependent like the records, installed and uploaded with them; plans
+  // without weighted columns have no such array).  weighted_kernel: has_weights, or some column's combiner is SQRTN — all
+  // spans of the plan run the weighted ragged kernel.
+  bool has_weights = false, weighted_kernel = false;
   bool wide_rows = false; // some table shard has >= 2^32 - 3 slots: FcpLaunch::store_through bit 1
   std::vector<FcpColStatic> h_cols;
   char *d_const = nullptr;
@@ -340,6 +347,15 @@ struct DeviceGuard {
 // fcp_plan.hip
 int compute_dyn(const fcp_plan *p, const int32_t *offsets, const int32_t *shapes, const int32_t *symbols, int64_t blob_bytes,
                 FcpColDyn *dyn, DynMeta *m);
+// plans with weighted columns: the weights' byte offsets (per column, concat order; -1 = unweighted) for these shapes
+int compute_weights(const fcp_plan *p, const int32_t *offsets, const int32_t *shapes, int64_t *wts);
+// bytes of one descriptor slot: the FcpColDyn records and, in plans with weighted columns, the weights' offsets behind them
+inline size_t slot_dyn_bytes(const fcp_plan *p) {
+  return p->cols.size() * sizeof(FcpColDyn) + (p->has_weights ? p->cols.size() * sizeof(int64_t) : 0);
+}
+inline const int64_t *slot_weights(const fcp_plan *p, const FcpColDyn *dyn) {
+  return p->has_weights ? reinterpret_cast<const int64_t *>(dyn + p->cols.size()) : nullptr;
+}
 // fcp_process.hip
 bool stream_is_capturing(hipStream_t stream);
 int bind_tables(fcp_plan *p, const void *const *input_ptrs, bool capturing);

@@ -146,6 +146,12 @@ void fcp_set_any_order(bool on);
 int fcp_launch_fused(const FcpLaunch &L, int vec, bool dense_kernel, int grid_blocks, ihipStream_t *s);
 int fcp_launch_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch &Lragged, int ragged_blocks, int vec,
                       ihipStream_t *s);
+// (fcp_weighted.hip) the ragged body with per-id weights and the sqrtn combiner, for plans that have either; wts: per
+// column (concat order) the byte offset of its float32 weights in the blob, or -1 — the tail of the request's descriptor
+// slot in plans with weighted columns, null in plans that only use sqrtn
+int fcp_launch_weighted(const FcpLaunch &L, const int64_t *wts, int vec, int grid_blocks, ihipStream_t *s);
+// what the next fused launch of this thread would carry (stop event, any-order flag): taken and cleared
+void fcp_take_launch_extras(void **stop_event, int *flags);
 int fcp_launch_upload(const void *host_mapped_src, void *dst, size_t bytes, ihipStream_t *s);
 // bytes (a multiple of 4) from host-mapped pinned memory to device memory by a kernel; both 4-byte aligned and equally
 // misaligned against 16 bytes
@@ -158,4 +164,4 @@ int fcp_launch_concat_outputs(const void *const *inputs, const int32_t *dims, co
                               ihipStream_t *s);
 int fcp_launch_shard_finalize(const FcpLaunch &L, int group, const float *partials, int world,
                               int64_t row_begin, int64_t row_count, float *out, int vec,
-                              ihipStream_t *s);
+                              ihipStream_t *s, const int64_t *wts = nullptr);

@@ -123,8 +123,10 @@ int validate_desc(const fcp_plan_desc_t *d) {
         return fail(FCP_ERR_INVALID_ARGUMENT, where + "pooled column needs an explicit row source");
     }
     if (c.form == FCP_FORM_SEGMENT_REDUCE && c.combiner != FCP_COMBINER_SUM &&
-        c.combiner != FCP_COMBINER_MEAN)
-      return fail(FCP_ERR_INVALID_ARGUMENT, where + "segment-reduce needs sum or mean");
+        c.combiner != FCP_COMBINER_MEAN && c.combiner != FCP_COMBINER_SQRTN)
+      return fail(FCP_ERR_INVALID_ARGUMENT, where + "segment-reduce needs sum, mean or sqrtn");
+    if (c.form != FCP_FORM_SEGMENT_REDUCE && c.combiner == FCP_COMBINER_SQRTN)
+      return fail(FCP_ERR_INVALID_ARGUMENT, where + "the sqrtn combiner applies to pooled columns only");
     if (c.form == FCP_FORM_BATCH_COL_REDUCTION && d->host_input_ranks[c.ids_input] != 3)
       return fail(FCP_ERR_INVALID_ARGUMENT, where + "BatchColReduction input must be rank 3");
     if (c.rows_source < FCP_ROWS_FROM_IDS || c.rows_source > FCP_ROWS_FROM_INPUT_DIM0)
@@ -144,9 +146,15 @@ int validate_desc(const fcp_plan_desc_t *d) {
 int validate_ext(const fcp_plan_desc_t *d, const fcp_column_ext_t *ext) {
   for (int k = 0; k < d->n_columns; ++k) {
     const fcp_column_ext_t &e = ext[k];
-    if (e.seg_map_n == 0) continue;
     const fcp_column_desc_t &c = d->columns[k];
     const std::string where = "column " + std::to_string(k) + ": ";
+    if (e.weights_input1 != 0) { // per-id weights (read before the map check below skips the record)
+      if (c.form != FCP_FORM_SEGMENT_REDUCE) return fail(FCP_ERR_INVALID_ARGUMENT, where + "per-id weights apply to pooled columns only");
+      if (e.weights_input1 < 0 || e.weights_input1 > d->n_host_inputs)
+        return fail(FCP_ERR_INVALID_ARGUMENT, where + "weights input out of range");
+      if (d->host_input_elem_sizes[e.weights_input1 - 1] != 4) return fail(FCP_ERR_INVALID_ARGUMENT, where + "per-id weights are float32");
+    }
+    if (e.seg_map_n == 0) continue;
     if (e.seg_map_n < 0 || e.seg_map_n > FCP_SEG_MAP_MAX) return fail(FCP_ERR_INVALID_ARGUMENT, where + "seg_map_n out of range");
     if (c.form != FCP_FORM_SEGMENT_REDUCE || (c.seg_kind != FCP_SEG_IDS_I32 && c.seg_kind != FCP_SEG_IDS_I64))
       return fail(FCP_ERR_INVALID_ARGUMENT, where + "a segment-id map needs a pooled column with segment ids");
@@ -504,6 +512,24 @@ int compute_dyn_fast(const fcp_plan *p, const int32_t *offsets, const int32_t *s
   return finish_geometry(p, m);
 }
 
+int compute_weights(const fcp_plan *p, const int32_t *offsets, const int32_t *shapes, int64_t *wts) {
+  auto numel = [&](int i) {
+    int64_t n = 1;
+    for (int j = 0; j < p->ranks[i]; ++j) n *= shapes[p->shape_off[i] + j];
+    return n;
+  };
+  for (size_t pos = 0; pos < p->cols.size(); ++pos) {
+    const HostColumn &hc = p->cols[p->order[pos]];
+    wts[pos] = -1;
+    if (hc.weights_input < 0) continue;
+    if (numel(hc.weights_input) != numel(hc.d.ids_input))
+      return fail(FCP_ERR_SHAPE_MISMATCH, "column " + std::to_string(p->order[pos]) + ": the weights tensor does not hold one weight per id");
+    if (offsets[hc.weights_input] % 4) return fail(FCP_ERR_UNSUPPORTED, "blob tensor not 4-byte aligned");
+    wts[pos] = offsets[hc.weights_input];
+  }
+  return FCP_OK;
+}
+
 int compute_dyn(const fcp_plan *p, const int32_t *offsets, const int32_t *shapes, const int32_t *symbols,
                 int64_t blob_bytes, FcpColDyn *dyn, DynMeta *m) {
   const bool slow_only = fcp::diag_on("dyn_general"); // test aid (looked up per call: only on a descriptor miss)
@@ -720,7 +746,7 @@ int init_device(fcp_plan *p) {
   }
   for (auto &s : p->slots) {
     // rounded up to 16 bytes: the upload kernel moves uint4s
-    const size_t dyn_bytes = (nc * sizeof(FcpColDyn) + 15) / 16 * 16;
+    const size_t dyn_bytes = (slot_dyn_bytes(p) + 15) / 16 * 16;
     HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_dyn), dyn_bytes, hipHostMallocMapped));
     HIP_TRY(hipHostGetDevicePointer(&s.h_dyn_dev, s.h_dyn, 0));
     if (p->host_writes_dyn) {
@@ -736,7 +762,7 @@ int init_device(fcp_plan *p) {
     }
   }
   for (auto &s : p->slots) {
-    const size_t dyn_bytes = (nc * sizeof(FcpColDyn) + 15) / 16 * 16;
+    const size_t dyn_bytes = (slot_dyn_bytes(p) + 15) / 16 * 16;
     if (!s.d_dyn) HIP_TRY(hipMalloc(&s.d_dyn, dyn_bytes));
     HIP_TRY(hipEventCreateWithFlags(&s.uploaded, hipEventDisableTiming));
     s.done = nullptr; // created per stream on first use (done_event_for)
@@ -821,6 +847,11 @@ int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext,
       hc.ext = ext[k];
       p->has_seg_map = true;
     }
+    if (ext && ext[k].weights_input1 > 0) {
+      hc.weights_input = ext[k].weights_input1 - 1;
+      p->has_weights = true;
+    }
+    if (p->has_weights || hc.d.combiner == FCP_COMBINER_SQRTN) p->weighted_kernel = true;
     if (hc.d.dim % 4) gcd4 = (hc.d.dim % 2) ? 1 : std::min(gcd4, 2);
     const int f = hc.d.form;
     if ((f == FCP_FORM_SEGMENT_REDUCE || f == FCP_FORM_GATHER_SCATTER) && hc.d.seg_kind != FCP_SEG_CSR_I32)
@@ -928,7 +959,8 @@ int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext,
   p->dense_only = true;
   for (int g = 0; g < ng; ++g) {
     const int nspans = (p->group_nslots[g] + FCP_WAVE - 1) / FCP_WAVE;
-    std::vector<char> ragged(nspans, 0);
+    // (a plan with a weighted or sqrtn column runs ALL its spans through the weighted ragged kernel: no weighted hybrid)
+    std::vector<char> ragged(nspans, p->weighted_kernel ? 1 : 0);
     for (int k = 0; k < desc->n_columns; ++k) {
       const HostColumn &hc = p->cols[k];
       if (hc.d.concat_group != g) continue;
@@ -970,7 +1002,7 @@ struct ParsedPlanFile {
   std::vector<fcp_column_desc_t> cols;
   std::vector<std::vector<float>> bnd;
   std::vector<std::vector<int64_t>> xlo, xhi;
-  std::vector<fcp_column_ext_t> ext; // "segmaps" section (version 4); empty = no column has extensions
+  std::vector<fcp_column_ext_t> ext; // "weights" (version 5) and "segmaps" (version 4) sections; empty = no column has extensions
   // "stage" section (version 3): what Addons>ConcatInputs does to each of ITS inputs while packing
   std::vector<uint8_t> stage_modes;
   std::vector<int32_t> stage_rows_symbol;
@@ -990,7 +1022,7 @@ int parse_plan_file(const char *path, ParsedPlanFile &P) {
   int version = 0, n_host = 0, n_cols = 0;
   fcp_plan_desc_t &d = P.d;
   std::memset(&d, 0, sizeof(d));
-  if (std::fscanf(f, "%31s %d", tag, &version) != 2 || std::strcmp(tag, "fcp_plan") || version < 1 || version > 4)
+  if (std::fscanf(f, "%31s %d", tag, &version) != 2 || std::strcmp(tag, "fcp_plan") || version < 1 || version > 5)
     return fail(FCP_ERR_INVALID_ARGUMENT, where + "bad header");
   if (std::fscanf(f, "%31s %d", tag, &d.layout) != 2 || std::strcmp(tag, "layout"))
     return fail(FCP_ERR_INVALID_ARGUMENT, where + "expected 'layout'");
@@ -1041,18 +1073,29 @@ int parse_plan_file(const char *path, ParsedPlanFile &P) {
       c.xform_hi = c.xform_n ? P.xhi[k].data() : nullptr;
     }
   }
-  // optional trailing sections: "segmaps M" + M x "column n sym slot mul0 mul1 mul2 mul3 div" (version 4), then
-  // "stage N symbols_input K" + N x "mode rows_symbol" (version 3)
-  bool seen_maps = false;
+  // optional trailing sections: "weights M" + M x "column input" (version 5), then "segmaps M" + M x "column n sym slot
+  // mul0 mul1 mul2 mul3 div" (version 4), then "stage N symbols_input K" + N x "mode rows_symbol" (version 3)
+  bool seen_maps = false, seen_weights = false;
   for (;;) {
     int count = 0;
     const int got = std::fscanf(f, "%31s %d", tag, &count);
     if (got == EOF || got == 0) break;
     if (got != 2) return fail(FCP_ERR_INVALID_ARGUMENT, where + "malformed trailing section");
-    if (version >= 4 && !std::strcmp(tag, "segmaps") && !seen_maps && !P.has_stage) {
+    if (version >= 5 && !std::strcmp(tag, "weights") && !seen_weights && !seen_maps && !P.has_stage) {
+      if (count < 0 || count > n_cols) return fail(FCP_ERR_INVALID_ARGUMENT, where + "bad 'weights M'");
+      seen_weights = true;
+      if (count > 0) P.ext.assign(n_cols, fcp_column_ext_t{});
+      for (int i = 0; i < count; ++i) {
+        int col = -1, input = -1;
+        if (std::fscanf(f, "%d %d", &col, &input) != 2 || col < 0 || col >= n_cols || input < 0 || input >= n_host ||
+            P.ext[col].weights_input1 != 0)
+          return fail(FCP_ERR_INVALID_ARGUMENT, where + "malformed weights entry " + std::to_string(i));
+        P.ext[col].weights_input1 = input + 1;
+      }
+    } else if (version >= 4 && !std::strcmp(tag, "segmaps") && !seen_maps && !P.has_stage) {
       if (count < 0 || count > n_cols) return fail(FCP_ERR_INVALID_ARGUMENT, where + "bad 'segmaps M'");
       seen_maps = true;
-      P.ext.assign(n_cols, fcp_column_ext_t{});
+      if (P.ext.empty()) P.ext.assign(n_cols, fcp_column_ext_t{});
       for (int i = 0; i < count; ++i) {
         int col = -1, n = 0, sym = -1, slot = 0;
         long long mul[4] = {0, 0, 0, 0}, div = 1;

@@ -147,8 +147,12 @@ int install_slot(fcp_plan *p, const fcp_process_args_t *a, DynSlot &s) {
   }
   int rc = compute_dyn(p, a->concated_offsets, a->concated_shapes, a->symbols, a->concated_bytes, s.h_dyn, &s.meta);
   if (rc) return rc;
+  if (p->has_weights) { // the weights' blob offsets ride behind the records: one install, one upload
+    rc = compute_weights(p, a->concated_offsets, a->concated_shapes, reinterpret_cast<int64_t *>(s.h_dyn + p->cols.size()));
+    if (rc) return rc;
+  }
   p->last_work_bytes.store(s.meta.work_bytes, std::memory_order_relaxed);
-  const size_t dyn_bytes = p->cols.size() * sizeof(FcpColDyn);
+  const size_t dyn_bytes = slot_dyn_bytes(p);
   if (p->host_writes_dyn) {
     std::memcpy(s.d_dyn, s.h_dyn, dyn_bytes); // CPU stores through the BAR into fine-grained VRAM
     __builtin_ia32_sfence();                  // posted before the launch's doorbell write
@@ -306,7 +310,9 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
   fill_launch(p, *slot, 1, a->concated_inputs, arena, store_policy, &L);
   { // fcp_plan_last_launch (diagnostics): the dispatch below, as it will be made
     fcp_plan::LastLaunch &ll = p->last_launch;
-    ll.kernel.store((int32_t)(m.geo[0].grid_blocks > 0) | (int32_t)(m.geo[1].grid_blocks > 0) << 1, std::memory_order_relaxed);
+    ll.kernel.store(p->weighted_kernel ? (m.geo[1].grid_blocks > 0 ? FCP_LAUNCH_RAGGED_WEIGHTED : FCP_LAUNCH_NONE)
+                                       : (int32_t)(m.geo[0].grid_blocks > 0) | (int32_t)(m.geo[1].grid_blocks > 0) << 1,
+                    std::memory_order_relaxed);
     ll.rows_per_wave.store(m.geo[0].rows_per_wave, std::memory_order_relaxed);
     ll.store_policy.store(store_policy, std::memory_order_relaxed);
     ll.dense_blocks.store(m.geo[0].grid_blocks, std::memory_order_relaxed);
@@ -358,8 +364,12 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
     ~ClearAnyOrder() { fcp_set_any_order(false); }
   } clear_any_order;
   if (p->request_order == FCP_ORDER_INPUTS_READY && !queued_before && !capturing) fcp_set_any_order(true);
-  // hybrid dispatch: spans with pooled columns -> ragged body, all other spans -> dense body
-  if (m.geo[1].grid_blocks > 0 && m.geo[0].grid_blocks > 0) {
+  // hybrid dispatch: spans with pooled columns -> ragged body, all other spans -> dense body; a plan with per-id weights
+  // or the sqrtn combiner: every span -> the weighted ragged kernel (plan creation listed them all as ragged)
+  if (p->weighted_kernel) {
+    const int e = fcp_launch_weighted(L, slot_weights(p, slot->d_dyn), p->vec, m.geo[1].grid_blocks, stream);
+    if (e) return hip_fail("weighted ragged kernel launch", (hipError_t)e);
+  } else if (m.geo[1].grid_blocks > 0 && m.geo[0].grid_blocks > 0) {
     FcpLaunch Ld;
     fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &Ld);
     const int e = fcp_launch_hybrid(Ld, m.geo[0].grid_blocks, L, m.geo[1].grid_blocks, p->vec, stream);

@@ -23,7 +23,7 @@ FCP_ERR_UNSUPPORTED = 5
 FCP_ERR_NO_DEVICE = 6
 FLAG_HOST_ONLY = 1 << 31  # plan without device resources (layout queries only)
 # fcp_launch_info_t (fcp_plan_last_launch): names of the kernel, store-policy and segment-offset codes
-LAUNCH_KERNELS = {0: "none", 1: "dense", 2: "ragged", 3: "hybrid"}
+LAUNCH_KERNELS = {0: "none", 1: "dense", 2: "ragged", 3: "hybrid", 4: "ragged_weighted"}
 LAUNCH_STORES = {0: "nt", 1: "sc1_nt", 4: "plain"}
 LAUNCH_SEGMENT_OFFSETS = {0: "none", 1: "prepass", 2: "search"}
 # fcp_aux_launch_counts: the kernels outside the fused matrix, one counter per instantiation (FCP_AUX_* order)
@@ -54,9 +54,9 @@ class ColumnDesc(C.Structure):
 
 
 class ColumnExt(C.Structure):
-    """fcp_column_ext_t: per-column extensions (segment-id maps)"""
+    """fcp_column_ext_t: per-column extensions (segment-id maps, per-id weights)"""
     _fields_ = [
-        ("seg_map_n", C.c_int32), ("seg_map_sym", C.c_int32), ("seg_map_sym_slot", C.c_int32), ("reserved0", C.c_int32),
+        ("seg_map_n", C.c_int32), ("seg_map_sym", C.c_int32), ("seg_map_sym_slot", C.c_int32), ("weights_input1", C.c_int32),
         ("seg_map_mul", C.c_int64 * 4), ("seg_map_div", C.c_int64), ("reserved1", C.c_int64 * 2),
     ]
 

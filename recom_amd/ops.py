@@ -182,9 +182,10 @@ class Plan:
             spec.n_device_inputs, spec.n_groups, spec.n_symbols, spec.layout, device,
             spec.shard_rank, spec.shard_world, flags)
         handle = C.c_void_p()
-        if any(len(c.seg_mul) for c in spec.columns):                  # per-column extensions: segment-id maps
+        if any(len(c.seg_mul) or c.weights_input != -1 for c in spec.columns):   # per-column extensions: segment-id maps, weights
             ext = (_lib.ColumnExt * spec.n_columns)()
             for k, c in enumerate(spec.columns):
+                ext[k].weights_input1 = int(c.weights_input) + 1          # 0 = unweighted
                 if len(c.seg_mul):
                     ext[k].seg_map_n, ext[k].seg_map_sym, ext[k].seg_map_sym_slot = len(c.seg_mul), c.seg_sym, c.seg_sym_slot
                     for j, v in enumerate(list(c.seg_mul)[:4]):
@@ -299,7 +300,7 @@ class Plan:
 
     def last_launch(self) -> dict:
         """``fcp_plan_last_launch``: what the plan's most recent request enqueued — kernel (``none`` / ``dense`` /
-        ``ragged`` / ``hybrid``), ``vec``, dense ``rows_per_wave``, ``store`` (``nt`` / ``sc1_nt`` / ``plain``),
+        ``ragged`` / ``hybrid`` / ``ragged_weighted``), ``vec``, dense ``rows_per_wave``, ``store`` (``nt`` / ``sc1_nt`` / ``plain``),
         ``wide_rows``, ``shard_world``, ``dense_blocks`` / ``ragged_blocks``, ``segment_offsets`` (``none`` /
         ``prepass`` / ``search``).  Read-only diagnostics: which kernel instantiation a request reached."""
         li = _lib.LaunchInfo()

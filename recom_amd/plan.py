@@ -19,13 +19,13 @@ import numpy as np
 
 # --- enums (== include/fcp_hip.h) -------------------------------------------
 FORM_GATHER = 1            # GatherV2(table, ids)              cuda_emitter.cc:250-293
-FORM_SEGMENT_REDUCE = 2    # SparseSegment{Sum,Mean}WithNumSegments  :402-661, :768-962
+FORM_SEGMENT_REDUCE = 2    # SparseSegment{Sum,Mean,SqrtN}WithNumSegments  :402-661, :768-962 (+ per-id weights)
 FORM_GATHER_SCATTER = 3    # ScatterNd(rows, GatherV2(...))    :296-345
 FORM_PASSTHROUGH = 4       # ConcatOutputs host_inputs         concat_outputs_op_gpu.cu.cc:186-216
 FORM_BATCH_COL_REDUCTION = 5  # Sum(x, axis=1)                 cuda_emitter.cc:1180-1244
 FORM_EXTERNAL = 6          # a concat slot filled by ConcatOutputs `host_inputs` (fcp_concat_outputs_host)
 
-COMBINER_NONE, COMBINER_SUM, COMBINER_MEAN = 0, 1, 2
+COMBINER_NONE, COMBINER_SUM, COMBINER_MEAN, COMBINER_SQRTN = 0, 1, 2, 3
 IDS_I32, IDS_I64, IDS_F32_BUCKETIZE = 0, 1, 2
 SEG_NONE, SEG_IDS_I32, SEG_IDS_I64, SEG_CSR_I32 = 0, 1, 2, 3
 ROWS_FROM_IDS, ROWS_FROM_SYMBOL, ROWS_FROM_INPUT_DIM0, ROWS_FROM_GROUP = 0, 1, 2, 3
@@ -75,6 +75,11 @@ class ColumnSpec:
     seg_div: int = 1
     seg_sym: int = -1
     seg_sym_slot: int = 0
+    # >= 0: the host input that holds one float32 weight per id, in the order of the ids — TensorFlow's
+    # weighted_categorical_column / embedding_lookup_sparse(sp_ids, sp_weights, combiner): every gathered row is multiplied
+    # by its weight (a rounded product, then a rounded add); MEAN divides by the sum of the weights, SQRTN by the square
+    # root of the sum of their squares.  Pooled columns only.  (fcp_column_ext_t::weights_input1 in include/fcp_hip.h)
+    weights_input: int = -1
 
     def validate(self) -> None:
         if self.form not in (1, 2, 3, 4, 5, 6):
@@ -94,8 +99,12 @@ class ColumnSpec:
                 raise ValueError("pooled/scatter column needs segment input")
             if self.rows_source == ROWS_FROM_IDS:
                 raise ValueError("pooled/scatter column needs an explicit row count source")
-        if self.form == FORM_SEGMENT_REDUCE and self.combiner not in (COMBINER_SUM, COMBINER_MEAN):
-            raise ValueError("segment-reduce column needs sum or mean")
+        if self.form == FORM_SEGMENT_REDUCE and self.combiner not in (COMBINER_SUM, COMBINER_MEAN, COMBINER_SQRTN):
+            raise ValueError("segment-reduce column needs sum, mean or sqrtn")
+        if self.form != FORM_SEGMENT_REDUCE and self.combiner == COMBINER_SQRTN:
+            raise ValueError("the sqrtn combiner applies to pooled columns only")
+        if self.weights_input != -1 and (self.form != FORM_SEGMENT_REDUCE or self.weights_input < 0):
+            raise ValueError("per-id weights apply to pooled columns only")
         if len(self.seg_mul):
             if self.form != FORM_SEGMENT_REDUCE or self.seg_kind not in (SEG_IDS_I32, SEG_IDS_I64):
                 raise ValueError("a segment-id map needs a pooled column with segment ids")
@@ -165,9 +174,11 @@ class PlanSpec:
             if key in seen:
                 raise ValueError(f"column {k}: duplicate concat slot {key}")
             seen.add(key)
-            for idx in (c.ids_input, c.seg_input):
+            for idx in (c.ids_input, c.seg_input, c.weights_input):
                 if idx >= len(self.host_input_ranks):
                     raise ValueError(f"column {k}: host input index out of range")
+            if c.weights_input >= 0 and self.host_input_elem_sizes[c.weights_input] != 4:
+                raise ValueError(f"column {k}: per-id weights are float32")
             if c.table_input >= self.n_device_inputs:
                 raise ValueError(f"column {k}: table_input out of range")
             if c.rows_source == ROWS_FROM_SYMBOL and not 0 <= c.rows_arg < self.n_symbols:
@@ -279,7 +290,8 @@ class PlanSpec:
                 c0 = self.columns[ks[0]]
                 same = all((self.columns[k].seg_stride, self.columns[k].rows_source, self.columns[k].rows_arg) ==
                            (c0.seg_stride, c0.rows_source, c0.rows_arg) for k in ks)
-                other = any(c.ids_input == i or (c.rows_source == ROWS_FROM_INPUT_DIM0 and c.rows_arg == i) for c in self.columns)
+                other = any(c.ids_input == i or c.weights_input == i or (c.rows_source == ROWS_FROM_INPUT_DIM0 and c.rows_arg == i)
+                            for c in self.columns)
                 readers = sum(1 for c in self.columns if c.seg_input == i)
                 if same and not other and readers == len(ks) and c0.rows_source == ROWS_FROM_SYMBOL:
                     modes[i] = STAGE_SEG_TO_CSR
@@ -319,7 +331,7 @@ class PlanSpec:
         host, dev = set(), set()
         for k in keep:
             c = self.columns[k]
-            for i in (c.ids_input, c.seg_input):
+            for i in (c.ids_input, c.seg_input, c.weights_input):
                 if i >= 0:
                     host.add(i)
             if c.rows_source == ROWS_FROM_INPUT_DIM0:
@@ -334,6 +346,7 @@ class PlanSpec:
             c = self.columns[k]
             cols.append(dataclasses.replace(
                 c, ids_input=hmap.get(c.ids_input, -1), seg_input=hmap.get(c.seg_input, -1),
+                weights_input=hmap.get(c.weights_input, -1),
                 table_input=dmap.get(c.table_input, -1),
                 rows_arg=hmap[c.rows_arg] if c.rows_source == ROWS_FROM_INPUT_DIM0 else c.rows_arg))
         spec = dataclasses.replace(self, columns=cols, host_input_ranks=[self.host_input_ranks[i] for i in host_l],
@@ -345,7 +358,8 @@ class PlanSpec:
     def algorithmic_bytes(self, shapes: Sequence[int], symbols: Optional[Sequence[int]] = None) -> dict:
         """Algorithmic bytes of one request: table rows read + ids read + CSR
         offsets / segment ids read + bucketize boundaries + pooled output written
-        once in concat layout.  No intermediate traffic is counted."""
+        once in concat layout (+ 4 bytes per id of a weighted column: key ``weights``, present only in plans that have
+        one).  No intermediate traffic is counted."""
         so = self.shape_offsets()
 
         def numel(i: int) -> int:
@@ -354,7 +368,7 @@ class PlanSpec:
                 n *= int(shapes[so[i] + j])
             return n
 
-        rows_b = ids_b = seg_b = bnd_b = out_b = 0
+        rows_b = ids_b = seg_b = bnd_b = out_b = w_b = 0
         for c in self.columns:
             if c.form == FORM_EXTERNAL:      # written by fcp_concat_outputs_host, not by the fused kernel
                 continue
@@ -376,9 +390,14 @@ class PlanSpec:
                     seg_b += nnz * 8
                 if c.id_source == IDS_F32_BUCKETIZE:
                     bnd_b += len(c.boundaries) * 4
-        read = rows_b + ids_b + seg_b + bnd_b
-        return {"rows": rows_b, "ids": ids_b, "segments": seg_b, "boundaries": bnd_b,
-                "out": out_b, "read": read, "total": read + out_b}
+                if c.weights_input >= 0:
+                    w_b += nnz * 4
+        read = rows_b + ids_b + seg_b + bnd_b + w_b
+        out = {"rows": rows_b, "ids": ids_b, "segments": seg_b, "boundaries": bnd_b,
+               "out": out_b, "read": read, "total": read + out_b}
+        if any(c.weights_input >= 0 for c in self.columns):
+            out["weights"] = w_b
+        return out
 
     def column_rows(self, c: ColumnSpec, shapes: Sequence[int], symbols: Optional[Sequence[int]]) -> int:
         if c.rows_source == ROWS_FROM_GROUP:

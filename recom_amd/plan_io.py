@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .plan import ColumnSpec, PlanSpec, StageInfo
+from .plan import COMBINER_SQRTN, ColumnSpec, PlanSpec, StageInfo
 
 
 def save_plan(spec: PlanSpec, path: str, stage: "StageInfo | None" = None) -> None:
@@ -18,7 +18,9 @@ def save_plan(spec: PlanSpec, path: str, stage: "StageInfo | None" = None) -> No
         raise ValueError("the stage section lists one entry per host input of the plan")
     with open(path, "w") as f:
         maps = [(k, c) for k, c in enumerate(spec.columns) if len(c.seg_mul)]
-        f.write(f"fcp_plan {4 if maps else 3 if stage is not None else 2}\n")
+        weights = [(k, c) for k, c in enumerate(spec.columns) if c.weights_input >= 0]
+        v5 = bool(weights) or any(c.combiner == COMBINER_SQRTN for c in spec.columns)
+        f.write(f"fcp_plan {5 if v5 else 4 if maps else 3 if stage is not None else 2}\n")
         f.write(f"layout {spec.layout}\n")
         f.write(f"groups {spec.n_groups} symbols {spec.n_symbols} device_inputs {spec.n_device_inputs}\n")
         f.write(f"host_inputs {spec.n_host_inputs}\n")
@@ -35,6 +37,10 @@ def save_plan(spec: PlanSpec, path: str, stage: "StageInfo | None" = None) -> No
             x = [c.xform_mode, len(c.xform_lo), c.xform_substitute, c.hash_buckets] + \
                 [v for p in zip(c.xform_lo, c.xform_hi) for v in p]
             f.write(" " + " ".join(str(int(v)) for v in x) + "\n")
+        if v5:       # version 5: per-id weights — column, host input (a plan that only uses the sqrtn combiner: "weights 0")
+            f.write(f"weights {len(weights)}\n")
+            for k, c in weights:
+                f.write(f"{k} {int(c.weights_input)}\n")
         if maps:     # version 4: segment-id maps — column, coordinates, symbol, symbol slot, mul0..mul3, div
             f.write(f"segmaps {len(maps)}\n")
             for k, c in maps:
@@ -59,7 +65,7 @@ def load_plan(path: str) -> PlanSpec:
     if nxt() != "fcp_plan":
         raise ValueError("bad plan header")
     version = int(nxt())
-    if version not in (1, 2, 3, 4):
+    if version not in (1, 2, 3, 4, 5):
         raise ValueError("bad plan header")
     assert nxt() == "layout"
     layout = int(nxt())
@@ -91,9 +97,21 @@ def load_plan(path: str) -> PlanSpec:
                                rows_arg=v[11], concat_group=v[12], concat_slot=v[13], boundaries=b,
                                xform_mode=mode, xform_lo=tuple(lo), xform_hi=tuple(hi), xform_substitute=sub,
                                hash_buckets=hb))
+    import dataclasses
     rest = list(it)
+    if rest[:1] == ["weights"]:
+        if version < 5:
+            raise ValueError(f"a weights section needs a version-5 plan file: {path}")
+        m = int(rest[1])
+        if m < 0 or len(rest) < 2 + 2 * m:
+            raise ValueError(f"truncated weights section in {path}")
+        for j in range(m):
+            k, i = int(rest[2 + 2 * j]), int(rest[3 + 2 * j])
+            if not 0 <= k < len(cols) or cols[k].weights_input >= 0 or not 0 <= i < n_host:
+                raise ValueError(f"malformed weights entry {j} in {path}")
+            cols[k] = dataclasses.replace(cols[k], weights_input=i)
+        rest = rest[2 + 2 * m:]
     if version >= 4 and rest[:1] == ["segmaps"]:
-        import dataclasses
         for j in range(int(rest[1])):
             v = [int(x) for x in rest[2 + 9 * j: 11 + 9 * j]]
             cols[v[0]] = dataclasses.replace(cols[v[0]], seg_mul=tuple(v[4:4 + v[1]]), seg_div=v[8], seg_sym=v[2],

@@ -249,11 +249,14 @@ def _ragged_lengths(rng: np.random.Generator, B: int, max_len: int, min_len: int
 
 
 def _add_ragged(b: _Builder, vocab: int, dim: int, slot: int, combiner: int, seg: str, max_len: int = 10,
-                group: int = 0, symbol: int = 0, dist: str = "uniform", form: int = FORM_SEGMENT_REDUCE) -> None:
+                group: int = 0, symbol: int = 0, dist: str = "uniform", form: int = FORM_SEGMENT_REDUCE,
+                weighted: bool = False) -> None:
     """Form 2 (RewriteSeedWithNumSegments, lookup_optimizer.cc:157-268) or form 3
     (RewriteGatherScatter, :324-440).  ``seg``: 'csr' (int32 offsets[B+1]),
     'indices' (SparseTensor indices int64[nnz,2], stride 2 — what the reference
-    graph delivers), 'rowids32' (int32[nnz])."""
+    graph delivers), 'rowids32' (int32[nnz]).  ``weighted``: one float32 weight per id, uniform in
+    [0.5, 1.5), as the column's last input (drawn after everything else of the column: its other tensors are those of
+    the unweighted column)."""
     t = b.table(vocab, dim)
     ids_in = b.host_input(1, 8)
     if seg == "csr":
@@ -262,6 +265,7 @@ def _add_ragged(b: _Builder, vocab: int, dim: int, slot: int, combiner: int, seg
         seg_in, kind, stride = b.host_input(2, 8), SEG_IDS_I64, 2
     else:
         seg_in, kind, stride = b.host_input(1, 4), SEG_IDS_I32, 1
+    w_in = b.host_input(1, 4) if weighted else -1
     mlen = 1 if form == FORM_GATHER_SCATTER else max_len
 
     def gen(rng: np.random.Generator, B: int) -> List[np.ndarray]:
@@ -270,17 +274,20 @@ def _add_ragged(b: _Builder, vocab: int, dim: int, slot: int, combiner: int, seg
         ids = _draw_ids(rng, nnz, vocab, dist)
         rows = np.repeat(np.arange(B, dtype=np.int64), lens)
         if seg == "csr":
-            offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
-            return [ids, offs]
-        if seg == "indices":
+            out = [ids, np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)]
+        elif seg == "indices":
             pos = np.concatenate([np.arange(l, dtype=np.int64) for l in lens]) if nnz else np.zeros(0, np.int64)
-            return [ids, np.stack([rows, pos], axis=1).astype(np.int64).reshape(nnz, 2)]
-        return [ids, rows.astype(np.int32)]
+            out = [ids, np.stack([rows, pos], axis=1).astype(np.int64).reshape(nnz, 2)]
+        else:
+            out = [ids, rows.astype(np.int32)]
+        if weighted:
+            out.append(rng.uniform(0.5, 1.5, nnz).astype(np.float32))
+        return out
 
     b.gens.append(gen)
     b.columns.append(ColumnSpec(form, dim, vocab, combiner if form == FORM_SEGMENT_REDUCE else COMBINER_NONE,
                                 IDS_I64, t, ids_in, seg_in, kind, stride, ROWS_FROM_SYMBOL, symbol, None,
-                                group, slot))
+                                group, slot, weights_input=w_in))
 
 
 def _finish(name: str, b: _Builder, batch: int, n_groups: int = 1, n_symbols: int = 0, description: str = "",
@@ -366,13 +373,15 @@ def model_dlrm(batch: int = 2048, dim: int = 16, cardinalities: Sequence[int] = 
 
 
 def model_ragged(columns: int = 512, vocab: int = 100_000, batch: int = 256, seg: str = "csr",
-                 max_len: int = 10, dims: Sequence[int] = (8, 16, 32, 64), dist: str = "uniform") -> SynthModel:
+                 max_len: int = 10, dims: Sequence[int] = (8, 16, 32, 64), dist: str = "uniform",
+                 weighted: bool = False) -> SynthModel:
     """RAGGED: 512 multi-hot columns, ids/row ~ U{0..10}, sum/mean alternating,
-    nnz re-drawn per request (dynamic shapes)."""
+    nnz re-drawn per request (dynamic shapes).  ``weighted``: every column with per-id weights (what weights cost:
+    scripts/weighted_bags_cost.py)."""
     b = _Builder()
     for c in range(columns):
         comb = COMBINER_SUM if c % 2 == 0 else COMBINER_MEAN
-        _add_ragged(b, vocab, dims[c % len(dims)], slot=c, combiner=comb, seg=seg, max_len=max_len, dist=dist)
+        _add_ragged(b, vocab, dims[c % len(dims)], slot=c, combiner=comb, seg=seg, max_len=max_len, dist=dist, weighted=weighted)
     return _finish("RAGGED", b, batch, n_symbols=1,
                    description=f"{columns} cols multi-hot U{{0..{max_len}}}, vocab {vocab}, B {batch}, seg={seg}")
 
