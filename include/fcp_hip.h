@@ -170,8 +170,24 @@ enum {
   /* Count ids outside [0, vocab) into the plan's device error counter.  Such
    * rows always read as zeros (TF-GPU GatherV2 semantics); the reference
    * reads out of bounds. */
-  FCP_FLAG_COUNT_BAD_IDS = 1u << 0
+  FCP_FLAG_COUNT_BAD_IDS = 1u << 0,
+  /* Narrow output (FCP_LAYOUT_CONCAT, unsharded): the concat groups are written as bf16 / fp16 instead of float32.
+   * A narrow element is fl16(x) of the float32 value x the same plan without the bit would have written, rounded ONCE,
+   * to nearest-even, at the store: overflow goes to +-inf (fp16: |x| >= 65520; bf16: the last half-ulp below 2^128),
+   * underflow is gradual (subnormals, then zero: float32 subnormals stay bf16 subnormals and become +-0 in fp16),
+   * -0.0 stays -0.0, NaN stays NaN (sign and payload unspecified).  The geometry is unchanged IN ELEMENTS — widths,
+   * column offsets, output_shapes, group_shapes, output_row_strides — and halves in BYTES: a group occupies
+   * rows x width x 2 bytes (128-byte aligned, as ever), output_ptrs / group_ptrs address 2-byte elements, buffer_bytes and
+   * fcp_plan_arena_bytes follow, the CSR scratch sits (4-byte aligned) behind the narrow outputs.  At most one of the
+   * two bits (both: FCP_ERR_INVALID_ARGUMENT); neither: the float32 plan, bit for bit.  Refused with
+   * FCP_ERR_UNSUPPORTED: shard_world > 1 (partial sums cross the exchange in float32), FCP_LAYOUT_PER_COLUMN (the
+   * reference's float32 arena), any FCP_FORM_EXTERNAL column (fcp_concat_outputs_host scatters float32 payloads), any
+   * column with per-id weights or FCP_COMBINER_SQRTN. */
+  FCP_FLAG_OUT_BF16 = 1u << 1,
+  FCP_FLAG_OUT_F16 = 1u << 2
 };
+/* element type of the plan's outputs (fcp_plan_out_dtype) */
+enum { FCP_OUT_F32 = 0, FCP_OUT_BF16 = 1, FCP_OUT_F16 = 2 };
 /* A plan without device resources: layout / arena / table-byte queries and plan-file checks on a machine
  * without a GPU (offline graph tooling).  Anything that computes returns FCP_ERR_NO_DEVICE — there is no
  * CPU fallback.  (A macro: the value does not fit an int enumerator.) */
@@ -338,9 +354,13 @@ int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext,
  *   version 4 files may carry, before it, "segmaps M" + M lines "column n sym
  *   slot mul0 mul1 mul2 mul3 div" (fcp_column_ext_t::seg_map_*); version 5 files
  *   (plans with per-id weights or FCP_COMBINER_SQRTN) carry, before both,
- *   "weights M" + M lines "column input" (fcp_column_ext_t::weights_input1 - 1).
- * `flags`: fcp_plan_desc_t::flags.  FCP_ERR_INVALID_ARGUMENT for a missing or
- * malformed file. */
+ *   "weights M" + M lines "column input" (fcp_column_ext_t::weights_input1 - 1);
+ *   version 6 files (narrow-output plans, and only those) carry "out_dtype bf16" or
+ *   "out_dtype f16" as their SECOND line, between the header and "layout"; the line
+ *   anywhere else, twice, with another name, or in a file of version <= 5 is malformed.
+ * `flags`: fcp_plan_desc_t::flags.  FCP_FLAG_OUT_BF16 / _F16 on a file without the
+ * line select the dtype; bits that name the file's dtype are fine, the other dtype is
+ * FCP_ERR_INVALID_ARGUMENT.  FCP_ERR_INVALID_ARGUMENT for a missing or malformed file. */
 int fcp_plan_create_from_file(const char *path, int32_t device, uint32_t flags,
                               fcp_plan_t **plan);
 int fcp_plan_destroy(fcp_plan_t *plan);
@@ -354,6 +374,8 @@ int fcp_plan_counts(const fcp_plan_t *plan, int32_t *n_columns, int32_t *n_group
  * column indices, *n the count (either may be NULL). */
 int fcp_plan_output_columns(const fcp_plan_t *plan, int32_t *n, int32_t *indices,
                             int32_t capacity);
+/* FCP_OUT_*: the element type of the plan's outputs (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16). */
+int fcp_plan_out_dtype(const fcp_plan_t *plan, int32_t *out);
 /* Bytes of embedding tables this plan reads on THIS device (its shard of every
  * table, shared tables counted once) and the largest single table's bytes
  * (unsharded) — the inputs of the placement gate, fcp_placement_decide. */
@@ -419,7 +441,9 @@ int fcp_plan_read_bad_ids(fcp_plan_t *plan, void *stream, int64_t *count);
 enum {
   FCP_LAUNCH_NONE = 0, FCP_LAUNCH_DENSE = 1, FCP_LAUNCH_RAGGED = 2, FCP_LAUNCH_HYBRID = 3,
   /* the ragged body with per-id weights and the sqrtn combiner: every span of a plan that has a weighted or SQRTN column */
-  FCP_LAUNCH_RAGGED_WEIGHTED = 4
+  FCP_LAUNCH_RAGGED_WEIGHTED = 4,
+  /* the narrow-output instantiations of the three (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16 plans) */
+  FCP_LAUNCH_DENSE_NARROW = 5, FCP_LAUNCH_RAGGED_NARROW = 6, FCP_LAUNCH_HYBRID_NARROW = 7
 };
 enum { FCP_LAUNCH_STORE_NT = 0, FCP_LAUNCH_STORE_SC1_NT = 1, FCP_LAUNCH_STORE_PLAIN = 4 };
 enum { FCP_LAUNCH_SEG_NONE = 0, FCP_LAUNCH_SEG_PREPASS = 1, FCP_LAUNCH_SEG_SEARCH = 2 };

@@ -108,6 +108,83 @@ template <int V> __device__ __forceinline__ void st_out(float *p, const VF<V> &v
   *as_global(reinterpret_cast<T *>(p)) = t;
 }
 
+// ---- narrow output (fcp_narrow.hip: FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16 plans) ------------------------------------------
+// A narrow element is fl16(x) of the float32 value x the float32 plan stores: ONE rounding to nearest-even, at the store.
+// bf16 in integers (the high half of the pattern plus the carry of the rounding: ties to even, overflow into the exponent
+// gives +-inf, float32 subnormals round like every other value, -0.0 stays -0.0; a NaN keeps its sign and becomes quiet so
+// that no payload can round to inf); fp16 is the hardware conversion v_cvt_f16_f32 in the kernel's mode (round-to-nearest-
+// even, denormals kept: |x| >= 65520 -> inf, gradual underflow, float32 subnormals -> +-0).
+__device__ __forceinline__ uint32_t narrow_bf16(float x) {
+  const uint32_t u = __float_as_uint(x);
+  const uint32_t r = (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+  return (u & 0x7FFFFFFFu) > 0x7F800000u ? ((u >> 16) | 0x40u) : r;
+}
+__device__ __forceinline__ uint32_t narrow_f16(float x) {
+  const _Float16 h = (_Float16)x;
+  uint16_t b;
+  __builtin_memcpy(&b, &h, 2);
+  return b;
+}
+
+// The V narrow elements of a slot as one store of 2 * V bytes: dwordx2 | dword | short.
+template <int V> struct NarrowType;
+template <> struct NarrowType<4> { typedef uint32_t __attribute__((ext_vector_type(2))) T; };
+template <> struct NarrowType<2> { typedef uint32_t T; };
+template <> struct NarrowType<1> { typedef uint16_t T; };
+
+// the same three cache policies as st_out, the hinted forms in inline asm for the same reason (st_nt above)
+__device__ __forceinline__ void st_through16(FCP_GLOBAL NarrowType<4>::T *p, NarrowType<4>::T t) {
+  asm volatile("global_store_dwordx2 %0, %1, off sc1 nt" ::"v"(p), "v"(t) : "memory");
+}
+__device__ __forceinline__ void st_through16(FCP_GLOBAL NarrowType<2>::T *p, NarrowType<2>::T t) {
+  asm volatile("global_store_dword %0, %1, off sc1 nt" ::"v"(p), "v"(t) : "memory");
+}
+__device__ __forceinline__ void st_through16(FCP_GLOBAL NarrowType<1>::T *p, NarrowType<1>::T t) {
+  asm volatile("global_store_short %0, %1, off sc1 nt" ::"v"(p), "v"((uint32_t)t) : "memory");
+}
+__device__ __forceinline__ void st_nt16(FCP_GLOBAL NarrowType<4>::T *p, NarrowType<4>::T t) {
+  asm volatile("global_store_dwordx2 %0, %1, off nt" ::"v"(p), "v"(t) : "memory");
+}
+__device__ __forceinline__ void st_nt16(FCP_GLOBAL NarrowType<2>::T *p, NarrowType<2>::T t) {
+  asm volatile("global_store_dword %0, %1, off nt" ::"v"(p), "v"(t) : "memory");
+}
+__device__ __forceinline__ void st_nt16(FCP_GLOBAL NarrowType<1>::T *p, NarrowType<1>::T t) {
+  asm volatile("global_store_short %0, %1, off nt" ::"v"(p), "v"((uint32_t)t) : "memory");
+}
+
+// p: BYTE address of the slot's first narrow element (2 * V-byte aligned); out_kind: FCP_OUT_BF16 | FCP_OUT_F16, the same
+// for every wave of the launch (a kernel argument)
+template <int V> __device__ __forceinline__ void st_out_narrow(char *p, const VF<V> &v, int policy, int out_kind) {
+  typedef typename NarrowType<V>::T T;
+  uint32_t h[V];
+  if (out_kind == FCP_OUT_BF16) {
+#pragma unroll
+    for (int i = 0; i < V; ++i) h[i] = narrow_bf16(v.v[i]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < V; ++i) h[i] = narrow_f16(v.v[i]);
+  }
+  T t;
+  if constexpr (V == 4) {
+    t.x = h[0] | (h[1] << 16);
+    t.y = h[2] | (h[3] << 16);
+  } else if constexpr (V == 2) {
+    t = h[0] | (h[1] << 16);
+  } else {
+    t = (uint16_t)h[0];
+  }
+  FCP_GLOBAL T *g = as_global(reinterpret_cast<T *>(p));
+  if (policy & FCP_ST_THROUGH) {
+    st_through16(g, t);
+    return;
+  }
+  if (!(policy & FCP_ST_PLAIN)) {
+    st_nt16(g, t);
+    return;
+  }
+  *g = t;
+}
+
 // Row `off` of a table of `spr` slots (of V floats) per row whose lane-specific base is `tb`: one v_mad_u64_u32
 // (row x slots per row, 64-bit: a table may be of any size, rows < 2^32 - 3) + one global_load.
 template <int V> __device__ __forceinline__ VF<V> ld_slot32(const float *tb, uint32_t off);
@@ -529,8 +606,11 @@ template <int R> struct DenseLds {
   float bnd[BND];
 };
 
-template <int V, int R, bool SHARDED>
-__device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *smem) {
+// NARROW: the instantiation for bf16 / fp16 output plans (fcp_narrow.hip); `out_kind` (FCP_OUT_*) is launch-uniform.  Only the
+// output address (2 bytes per element) and the store differ, and both sit behind `if constexpr (NARROW)`: the float32
+// instantiations are the code they were.
+template <int V, int R, bool SHARDED, bool NARROW = false>
+__device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *smem, int out_kind = 0) {
   constexpr int RB = DenseLds<R>::RB, IDS = DenseLds<R>::IDS, BND = DenseLds<R>::BND;
   DenseLds<R> &S = *reinterpret_cast<DenseLds<R> *>(smem);
   LdsCol *s_col = S.col;
@@ -655,6 +735,8 @@ __device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *sm
   const int64_t ostride = s_col[j].out_stride;
   if (FCP_F_FORM(s_col[j].flags) == FCP_FORM_EXTERNAL) return; // somebody else's slot (ConcatOutputs host input)
   float *outp = reinterpret_cast<float *>(H.arena + s_col[j].out_base) + e;
+  char *outp16 = nullptr; // narrow output: the same element, 2 bytes each
+  if constexpr (NARROW) outp16 = H.arena + s_col[j].out_base + 2 * (int64_t)e;
   const int r0 = wave * R;
   const uint32_t spr = (uint32_t)(s_col[j].dim / V); // slots per table row
   uint32_t off[R];
@@ -669,7 +751,11 @@ __device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *sm
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const int b = B.row_blk + r0 + r;
-    if (b < B.rows) st_out<V>(outp + (int64_t)b * ostride, v[r], H.store_through);
+    if constexpr (NARROW) {
+      if (b < B.rows) st_out_narrow<V>(outp16 + 2 * (int64_t)b * ostride, v[r], H.store_through, out_kind);
+    } else {
+      if (b < B.rows) st_out<V>(outp + (int64_t)b * ostride, v[r], H.store_through);
+    }
   }
 }
 
@@ -910,8 +996,9 @@ struct RaggedLds {
 // WEIGHTED: the instantiation for plans with per-id weights or the sqrtn combiner (fcp_weighted.hip).  `wts`: per column
 // (concat order) the byte offset of its float32 weights in the blob, or -1.  Everything it adds sits behind
 // `if constexpr (WEIGHTED)`: the unweighted instantiations are the code they were.
-template <int V, bool SHARDED, bool WEIGHTED = false>
-__device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *smem, const int64_t *wts = nullptr) {
+// NARROW: as in the dense body — bf16 / fp16 output plans (fcp_narrow.hip), everything behind `if constexpr (NARROW)`.
+template <int V, bool SHARDED, bool WEIGHTED = false, bool NARROW = false>
+__device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *smem, const int64_t *wts = nullptr, int out_kind = 0) {
   constexpr int RB = RaggedLds::RB, CAPW = RaggedLds::CAPW;
   RaggedLds &S = *reinterpret_cast<RaggedLds *>(smem);
   LdsCol *s_col = S.col;
@@ -1172,6 +1259,10 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
     const float fc = (float)(pcnt - dropped); // sum / count of the ids that reached the lookup
 #pragma unroll
     for (int t = 0; t < V; ++t) acc.v[t] = acc.v[t] / fc;
+  }
+  if constexpr (NARROW) {
+    st_out_narrow<V>(H.arena + C.out_base + 2 * (e + (int64_t)b * C.out_stride), acc, H.store_through, out_kind);
+    return;
   }
   st_out<V>(reinterpret_cast<float *>(H.arena + C.out_base) + e + (int64_t)b * C.out_stride, acc, H.store_through);
 }

@@ -366,7 +366,8 @@ int fcp_harness_run_private(fcp_harness *h, int steps, int depth, double *wall_m
 // worker `t`'s stream (what fcp_harness_run_private issues on is worker 0's): for probes that need the caller's stream
 // The concat matrices worker `t` wrote for the LAST request of the latest fcp_harness_run, copied out of the ring arena that
 // request was given — what the timed loop itself computed, not a recomputation.  group_shapes: int32[2 * n_groups] (rows,
-// width per group); host_out: n_groups host float buffers of rows * width elements each, or NULL for the shapes alone.
+// width per group); host_out: n_groups host buffers of rows * width elements each (float32, or the plan's 2-byte elements:
+// fcp_plan_out_dtype), or NULL for the shapes alone.
 // FCP_LAYOUT_CONCAT plans; after fcp_harness_run has returned (its streams are synchronised).
 int fcp_harness_last_output(fcp_harness *h, int t, int32_t n_groups, int32_t *group_shapes, float **host_out) {
   if (!h || t < 0 || t >= (int)h->last.size() || !group_shapes || n_groups != (int32_t)h->last[t].group_ptrs.size())
@@ -378,8 +379,11 @@ int fcp_harness_last_output(fcp_harness *h, int t, int32_t n_groups, int32_t *gr
   std::copy(l.group_shapes.begin(), l.group_shapes.end(), group_shapes);
   if (!host_out) return FCP_OK;
   OnDevice on(h->device);
+  int32_t out_kind = FCP_OUT_F32;
+  if (fcp_plan_out_dtype(h->plan, &out_kind)) return FCP_ERR_INVALID_ARGUMENT;
+  const size_t elem = out_kind == FCP_OUT_F32 ? sizeof(float) : 2;
   for (int32_t g = 0; g < n_groups; ++g) {
-    const size_t bytes = (size_t)l.group_shapes[2 * g] * (size_t)l.group_shapes[2 * g + 1] * sizeof(float);
+    const size_t bytes = (size_t)l.group_shapes[2 * g] * (size_t)l.group_shapes[2 * g + 1] * elem;
     if (bytes) H_TRY(hipMemcpy(host_out[g], l.group_ptrs[g], bytes, hipMemcpyDeviceToHost));
   }
   return FCP_OK;

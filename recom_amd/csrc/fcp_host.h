@@ -268,6 +268,9 @@ struct fcp_plan {
   // spans of the plan run the weighted ragged kernel.
   bool has_weights = false, weighted_kernel = false;
   bool wide_rows = false; // some table shard has >= 2^32 - 3 slots: FcpLaunch::store_through bit 1
+  // narrow output (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16): the element type (FCP_OUT_*) and its size in bytes — every byte
+  // quantity of the output region (group sizes, column bases, the position of the CSR scratch) is formed with out_elem
+  int out_kind = FCP_OUT_F32, out_elem = 4;
   std::vector<FcpColStatic> h_cols;
   char *d_const = nullptr;
   int32_t *d_seg_cols = nullptr;

@@ -150,6 +150,11 @@ int fcp_launch_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch
 // column (concat order) the byte offset of its float32 weights in the blob, or -1 — the tail of the request's descriptor
 // slot in plans with weighted columns, null in plans that only use sqrtn
 int fcp_launch_weighted(const FcpLaunch &L, const int64_t *wts, int vec, int grid_blocks, ihipStream_t *s);
+// (fcp_narrow.hip) the dense / ragged / hybrid bodies for bf16 / fp16 output plans (unsharded); out_kind: FCP_OUT_BF16 |
+// FCP_OUT_F16; geometry, LDS and grids as fcp_launch_fused / fcp_launch_hybrid
+int fcp_launch_narrow(const FcpLaunch &L, int vec, bool dense_kernel, int out_kind, int grid_blocks, ihipStream_t *s);
+int fcp_launch_narrow_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch &Lragged, int ragged_blocks, int vec,
+                             int out_kind, ihipStream_t *s);
 // what the next fused launch of this thread would carry (stop event, any-order flag): taken and cleared
 void fcp_take_launch_extras(void **stop_event, int *flags);
 int fcp_launch_upload(const void *host_mapped_src, void *dst, size_t bytes, ihipStream_t *s);

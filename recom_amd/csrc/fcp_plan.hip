@@ -169,6 +169,29 @@ int validate_ext(const fcp_plan_desc_t *d, const fcp_column_ext_t *ext) {
   return FCP_OK;
 }
 
+// Narrow output (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16): what the narrow kernels (fcp_narrow.hip) do not serve is refused
+// here, by name, for device and host-only plans alike.
+int validate_narrow(const fcp_plan_desc_t *d, const fcp_column_ext_t *ext) {
+  const uint32_t narrow = d->flags & (FCP_FLAG_OUT_BF16 | FCP_FLAG_OUT_F16);
+  if (!narrow) return FCP_OK;
+  if (narrow == (FCP_FLAG_OUT_BF16 | FCP_FLAG_OUT_F16))
+    return fail(FCP_ERR_INVALID_ARGUMENT, "FCP_FLAG_OUT_BF16 and FCP_FLAG_OUT_F16 exclude each other");
+  if (d->shard_world > 1)
+    return fail(FCP_ERR_UNSUPPORTED, "narrow output on a row-sharded plan (shard_world > 1): partial sums cross the exchange in float32");
+  if (d->layout == FCP_LAYOUT_PER_COLUMN)
+    return fail(FCP_ERR_UNSUPPORTED, "narrow output needs FCP_LAYOUT_CONCAT: FCP_LAYOUT_PER_COLUMN is the reference's float32 arena");
+  for (int k = 0; k < d->n_columns; ++k) {
+    const std::string where = "column " + std::to_string(k) + ": ";
+    if (d->columns[k].form == FCP_FORM_EXTERNAL)
+      return fail(FCP_ERR_UNSUPPORTED, where + "narrow output with an FCP_FORM_EXTERNAL slot: fcp_concat_outputs_host scatters float32 payloads");
+    if (ext && ext[k].weights_input1 > 0)
+      return fail(FCP_ERR_UNSUPPORTED, where + "narrow output with per-id weights: weighted plans take the float32 weighted kernel");
+    if (d->columns[k].combiner == FCP_COMBINER_SQRTN && d->columns[k].form == FCP_FORM_SEGMENT_REDUCE)
+      return fail(FCP_ERR_UNSUPPORTED, where + "narrow output with FCP_COMBINER_SQRTN: sqrtn plans take the float32 weighted kernel");
+  }
+  return FCP_OK;
+}
+
 // Run-time shapes -> per-column dynamic records, arena layout and launch
 // geometry.  Mirrors what the generated host code evaluates per call from
 // SymEngine expressions (cuda_emitter.cc:2151-2179, :2410-2455).
@@ -230,7 +253,7 @@ int compute_dyn_slow(const fcp_plan *p, const int32_t *offsets, const int32_t *s
   if (p->desc.layout == FCP_LAYOUT_CONCAT) {
     for (int g = 0; g < ng; ++g) {
       m->group_base[g] = cursor;
-      cursor += align128((int64_t)m->group_rows[g] * p->group_width[g] * 4);
+      cursor += align128((int64_t)m->group_rows[g] * p->group_width[g] * p->out_elem);
     }
   }
   m->max_seg_nnz = 0;
@@ -293,7 +316,7 @@ int compute_dyn_slow(const fcp_plan *p, const int32_t *offsets, const int32_t *s
       }
     }
     if (p->desc.layout == FCP_LAYOUT_CONCAT) {
-      d.out_base = m->group_base[c.concat_group] + (int64_t)hc.out_off * 4;
+      d.out_base = m->group_base[c.concat_group] + (int64_t)hc.out_off * p->out_elem;
       d.out_stride = p->group_width[c.concat_group];
     } else {
       d.out_base = cursor;
@@ -440,7 +463,7 @@ int compute_dyn_fast(const fcp_plan *p, const int32_t *offsets, const int32_t *s
     if (rows < 0 || rows > 0x7fffffff) return -1;
     m->group_rows[g] = (int32_t)rows;
     m->group_base[g] = cursor;
-    cursor += align128(rows * p->group_width[g] * 4);
+    cursor += align128(rows * p->group_width[g] * p->out_elem);
   }
   int32_t max_seg_nnz = 0;
   int64_t seg_pairs = 0;
@@ -812,8 +835,13 @@ int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext,
   int rc = validate_desc(desc);
   if (rc) return rc;
   if (ext && (rc = validate_ext(desc, ext))) return rc;
+  if ((rc = validate_narrow(desc, ext))) return rc;
   fcp_plan *p = new (std::nothrow) fcp_plan();
   if (!p) return fail(FCP_ERR_ALLOC, "out of host memory");
+  if (desc->flags & (FCP_FLAG_OUT_BF16 | FCP_FLAG_OUT_F16)) {
+    p->out_kind = (desc->flags & FCP_FLAG_OUT_BF16) ? FCP_OUT_BF16 : FCP_OUT_F16;
+    p->out_elem = 2;
+  }
   p->env = fcp::read_env(); // the library's shipping switches, read here and nowhere on the request path (fcp_env.h)
   p->desc = *desc;
   p->desc.columns = nullptr;
@@ -941,7 +969,7 @@ int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext,
       f.rows_arg = hc.d.rows_arg;
       f.dim = hc.d.dim;
       f.seg_stride = hc.d.seg_stride < 1 ? 1 : hc.d.seg_stride;
-      f.out_off_bytes = (int64_t)hc.out_off * 4;
+      f.out_off_bytes = (int64_t)hc.out_off * p->out_elem;
       f.form = (uint8_t)hc.d.form;
       f.rows_source = (uint8_t)hc.d.rows_source;
       f.seg_kind = (uint8_t)hc.d.seg_kind;
@@ -1008,6 +1036,7 @@ struct ParsedPlanFile {
   std::vector<int32_t> stage_rows_symbol;
   int32_t stage_symbols_input = -1;
   bool has_stage = false;
+  int out_kind = FCP_OUT_F32; // the "out_dtype" line (version 6)
 };
 
 int parse_plan_file(const char *path, ParsedPlanFile &P) {
@@ -1022,8 +1051,13 @@ int parse_plan_file(const char *path, ParsedPlanFile &P) {
   int version = 0, n_host = 0, n_cols = 0;
   fcp_plan_desc_t &d = P.d;
   std::memset(&d, 0, sizeof(d));
-  if (std::fscanf(f, "%31s %d", tag, &version) != 2 || std::strcmp(tag, "fcp_plan") || version < 1 || version > 5)
+  if (std::fscanf(f, "%31s %d", tag, &version) != 2 || std::strcmp(tag, "fcp_plan") || version < 1 || version > 6)
     return fail(FCP_ERR_INVALID_ARGUMENT, where + "bad header");
+  if (version >= 6) { // narrow-output plans: "out_dtype bf16|f16", here and nowhere else (anywhere else it is no 'layout' / section)
+    if (std::fscanf(f, "%31s %31s", tag, t2) != 2 || std::strcmp(tag, "out_dtype") || (std::strcmp(t2, "bf16") && std::strcmp(t2, "f16")))
+      return fail(FCP_ERR_INVALID_ARGUMENT, where + "expected 'out_dtype bf16' or 'out_dtype f16'");
+    P.out_kind = !std::strcmp(t2, "bf16") ? FCP_OUT_BF16 : FCP_OUT_F16;
+  }
   if (std::fscanf(f, "%31s %d", tag, &d.layout) != 2 || std::strcmp(tag, "layout"))
     return fail(FCP_ERR_INVALID_ARGUMENT, where + "expected 'layout'");
   if (std::fscanf(f, "%31s %d %31s %d %31s %d", tag, &d.n_groups, t2, &d.n_symbols, t3, &d.n_device_inputs) != 6 ||
@@ -1155,6 +1189,12 @@ int fcp_plan_create_from_file(const char *path, int32_t device, uint32_t flags, 
                                               std::to_string(P.d.n_host_inputs) + " host inputs");
   P.d.device = device;
   P.d.flags = flags;
+  if (P.out_kind != FCP_OUT_F32) { // the file names the dtype: flag bits may repeat it, not contradict it
+    const uint32_t file_bit = P.out_kind == FCP_OUT_BF16 ? FCP_FLAG_OUT_BF16 : FCP_FLAG_OUT_F16;
+    if (flags & (FCP_FLAG_OUT_BF16 | FCP_FLAG_OUT_F16) & ~file_bit)
+      return fail(FCP_ERR_INVALID_ARGUMENT, std::string("column plan ") + path + ": flags ask for another output dtype than the file's out_dtype line");
+    P.d.flags |= file_bit;
+  }
   return fcp_plan_create_ex(&P.d, P.ext.empty() ? nullptr : P.ext.data(), out);
 }
 
@@ -1194,6 +1234,12 @@ int fcp_plan_output_columns(const fcp_plan_t *p, int32_t *n, int32_t *indices, i
     ++count;
   }
   if (n) *n = count;
+  return FCP_OK;
+}
+
+int fcp_plan_out_dtype(const fcp_plan_t *p, int32_t *out) {
+  if (!p || !out) return fail(FCP_ERR_INVALID_ARGUMENT, "null argument");
+  *out = p->out_kind;
   return FCP_OK;
 }
 

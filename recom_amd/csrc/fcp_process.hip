@@ -310,8 +310,10 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
   fill_launch(p, *slot, 1, a->concated_inputs, arena, store_policy, &L);
   { // fcp_plan_last_launch (diagnostics): the dispatch below, as it will be made
     fcp_plan::LastLaunch &ll = p->last_launch;
+    const int32_t fused = (int32_t)(m.geo[0].grid_blocks > 0) | (int32_t)(m.geo[1].grid_blocks > 0) << 1;
     ll.kernel.store(p->weighted_kernel ? (m.geo[1].grid_blocks > 0 ? FCP_LAUNCH_RAGGED_WEIGHTED : FCP_LAUNCH_NONE)
-                                       : (int32_t)(m.geo[0].grid_blocks > 0) | (int32_t)(m.geo[1].grid_blocks > 0) << 1,
+                    : (p->out_elem == 2 && fused) ? fused + (FCP_LAUNCH_DENSE_NARROW - FCP_LAUNCH_DENSE) // narrow plans: fcp_narrow.hip
+                                                  : fused,
                     std::memory_order_relaxed);
     ll.rows_per_wave.store(m.geo[0].rows_per_wave, std::memory_order_relaxed);
     ll.store_policy.store(store_policy, std::memory_order_relaxed);
@@ -369,6 +371,19 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
   if (p->weighted_kernel) {
     const int e = fcp_launch_weighted(L, slot_weights(p, slot->d_dyn), p->vec, m.geo[1].grid_blocks, stream);
     if (e) return hip_fail("weighted ragged kernel launch", (hipError_t)e);
+  } else if (p->out_elem == 2) { // bf16 / fp16 output: the same three dispatches in their narrow instantiations
+    int e = 0;
+    if (m.geo[1].grid_blocks > 0 && m.geo[0].grid_blocks > 0) {
+      FcpLaunch Ld;
+      fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &Ld);
+      e = fcp_launch_narrow_hybrid(Ld, m.geo[0].grid_blocks, L, m.geo[1].grid_blocks, p->vec, p->out_kind, stream);
+    } else if (m.geo[1].grid_blocks > 0) {
+      e = fcp_launch_narrow(L, p->vec, false, p->out_kind, m.geo[1].grid_blocks, stream);
+    } else if (m.geo[0].grid_blocks > 0) {
+      fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &L);
+      e = fcp_launch_narrow(L, p->vec, true, p->out_kind, m.geo[0].grid_blocks, stream);
+    }
+    if (e) return hip_fail("narrow-output kernel launch", (hipError_t)e);
   } else if (m.geo[1].grid_blocks > 0 && m.geo[0].grid_blocks > 0) {
     FcpLaunch Ld;
     fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &Ld);

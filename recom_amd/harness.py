@@ -107,12 +107,13 @@ class ServingHarness:
         return wall.value, dev.value, it
 
     def last_output(self, worker: int = 0) -> List[np.ndarray]:
-        """The concat matrices (float32 [rows, width] per group) that worker ``worker`` wrote for the last request of the
+        """The concat matrices (float32 [rows, width] per group; uint16 bit patterns for a narrow-output plan) that worker ``worker`` wrote for the last request of the
         latest ``run`` — copied out of the ring arena that request was given, not computed again."""
         g = self.spec.n_groups
         shapes = (C.c_int32 * (2 * g))()
         _lib.check(self.H.fcp_harness_last_output(self.handle, worker, g, shapes, None), "fcp_harness_last_output")
-        out = [np.empty((shapes[2 * k], shapes[2 * k + 1]), np.float32) for k in range(g)]
+        # (a narrow-output plan: the 16-bit patterns of its bf16 / fp16 elements)
+        out = [np.empty((shapes[2 * k], shapes[2 * k + 1]), np.float32 if self.spec.out_dtype == "f32" else np.uint16) for k in range(g)]
         ptrs = (C.c_void_p * g)(*[a.ctypes.data for a in out])
         _lib.check(self.H.fcp_harness_last_output(self.handle, worker, g, shapes, ptrs), "fcp_harness_last_output")
         return out
@@ -162,17 +163,23 @@ class ServingHarness:
         pooled = [k for k in plain if spec.columns[k].form == FORM_SEGMENT_REDUCE]
         step = max(1, len(dense) // max_columns)
         dense, pooled = dense[::step][:max_columns], pooled[::max(1, len(pooled) // 8)][:8]
+        # a narrow-output plan: the same closed forms, rounded once to the plan's element type (still an exact comparison)
+        nd = {"f32": None, "bf16": torch.bfloat16, "f16": torch.float16}[spec.out_dtype]
+
+        def fl(x):
+            return x if nd is None else torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(nd).float().numpy()
+
         n_checked = 0
         for (blob, offsets, shapes), r, keep in zip(self.packed, self.requests, self._keep[1::4]):
             out = op(keep, offsets, shapes, self.tables, r.symbols)
             torch.cuda.synchronize()
-            groups = [g.cpu().numpy() for g in out.groups]
+            groups = [g.float().cpu().numpy() for g in out.groups]   # (bf16 / fp16 -> float32 is exact)
             for k in dense + pooled:
                 c = spec.columns[k]
                 got = groups[c.concat_group][:, offs[k]:offs[k] + c.dim]
                 raw = np.asarray(r.inputs[c.ids_input])
                 if c.form == FORM_PASSTHROUGH:
-                    ok = np.array_equal(got, raw.reshape(got.shape))
+                    ok = np.array_equal(got, fl(raw.reshape(got.shape)))
                 else:
                     ids = raw.reshape(-1)
                     if c.id_source == IDS_F32_BUCKETIZE:
@@ -182,7 +189,7 @@ class ServingHarness:
                     valid = (ids >= 0) & (ids < c.vocab)
                     if c.form == FORM_GATHER:
                         want = np.where(valid[:, None], synth.hash_rows(seed, np.where(valid, ids, 0), c.dim), np.float32(0))
-                        ok = np.array_equal(got, want)
+                        ok = np.array_equal(got, fl(want))
                     else:
                         seg = np.asarray(r.inputs[c.seg_input])
                         if c.seg_kind == SEG_CSR_I32:
@@ -198,7 +205,7 @@ class ServingHarness:
                                 acc = acc + synth.hash_rows(seed, np.asarray([v]), c.dim)[0]        # fp32, id order
                             if c.combiner == COMBINER_MEAN and sel.size:
                                 acc = acc / np.float32(sel.size)
-                            ok = ok and np.array_equal(got[b_], acc)
+                            ok = ok and np.array_equal(got[b_], fl(acc))
                 if not ok:
                     raise RuntimeError(f"resident request check failed: column {k} (form {c.form}) differs from the closed-form tables")
                 n_checked += 1
@@ -206,7 +213,8 @@ class ServingHarness:
                 "note": "each resident request served once and compared with closed-form table rows (exact) before the warm-up"}
 
     def algorithmic_bytes(self) -> dict:
-        """Mean algorithmic bytes per request over the resident requests."""
+        """Mean algorithmic bytes per request over the resident requests; a narrow-output plan is charged
+        2 bytes per written element (``PlanSpec.algorithmic_bytes``)."""
         acc = None
         for (blob, offsets, shapes), r in zip(self.packed, self.requests):
             b = self.spec.algorithmic_bytes(shapes, r.symbols)

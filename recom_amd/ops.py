@@ -175,7 +175,7 @@ class Plan:
         ranks = np.asarray(spec.host_input_ranks, np.int32)
         esz = np.asarray(spec.host_input_elem_sizes, np.int32)
         self._keep += [ranks, esz]
-        flags = spec.flags | (_lib.FLAG_HOST_ONLY if host_only else 0)
+        flags = spec.plan_flags() | (_lib.FLAG_HOST_ONLY if host_only else 0)
         desc = _lib.PlanDesc(
             _lib.FCP_ABI_VERSION, spec.n_columns, cols, len(ranks),
             ranks.ctypes.data_as(C.POINTER(C.c_int32)), esz.ctypes.data_as(C.POINTER(C.c_int32)),
@@ -197,9 +197,12 @@ class Plan:
         self.handle = handle
 
     @classmethod
-    def from_file(cls, path: str, device: int = 0, host_only: bool = False) -> "Plan":
+    def from_file(cls, path: str, device: int = 0, host_only: bool = False, out_dtype: Optional[str] = None) -> "Plan":
         """The plan a column-plan file describes, parsed by the library itself
-        (``fcp_plan_create_from_file`` — what the TF shim calls with the op's ``dlpath``)."""
+        (``fcp_plan_create_from_file`` — what the TF shim calls with the op's ``dlpath``).  ``out_dtype``: "bf16" / "f16"
+        select narrow output for a file that does not name a dtype (the flag bits of the call); a file that names
+        another one is refused."""
+        import dataclasses
         from .plan_io import load_plan
         self = cls.__new__(cls)
         self.device = device
@@ -207,11 +210,19 @@ class Plan:
         self._keep = []
         self.handle = None
         handle = C.c_void_p()
-        _lib.check(self._L.fcp_plan_create_from_file(path.encode(), device, _lib.FLAG_HOST_ONLY if host_only else 0,
-                                                     C.byref(handle)), "fcp_plan_create_from_file")
+        flags = (_lib.FLAG_HOST_ONLY if host_only else 0) | _lib.OUT_DTYPE_FLAGS[out_dtype or "f32"]
+        _lib.check(self._L.fcp_plan_create_from_file(path.encode(), device, flags, C.byref(handle)), "fcp_plan_create_from_file")
         self.handle = handle
         self.spec = load_plan(path)          # Python-side bookkeeping only
+        if self.out_dtype() != self.spec.out_dtype:
+            self.spec = dataclasses.replace(self.spec, out_dtype=self.out_dtype())
         return self
+
+    def out_dtype(self) -> str:
+        """``fcp_plan_out_dtype``: "f32", "bf16" or "f16" — the element type of the plan's outputs."""
+        v = C.c_int32()
+        _lib.check(self._L.fcp_plan_out_dtype(self.handle, C.byref(v)), "fcp_plan_out_dtype")
+        return _lib.OUT_DTYPES[v.value]
 
     def counts(self) -> dict:
         v = [C.c_int32() for _ in range(5)]
@@ -300,7 +311,7 @@ class Plan:
 
     def last_launch(self) -> dict:
         """``fcp_plan_last_launch``: what the plan's most recent request enqueued — kernel (``none`` / ``dense`` /
-        ``ragged`` / ``hybrid`` / ``ragged_weighted``), ``vec``, dense ``rows_per_wave``, ``store`` (``nt`` / ``sc1_nt`` / ``plain``),
+        ``ragged`` / ``hybrid`` / ``ragged_weighted`` / ``dense_narrow`` / ``ragged_narrow`` / ``hybrid_narrow``), ``vec``, dense ``rows_per_wave``, ``store`` (``nt`` / ``sc1_nt`` / ``plain``),
         ``wide_rows``, ``shard_world``, ``dense_blocks`` / ``ragged_blocks``, ``segment_offsets`` (``none`` /
         ``prepass`` / ``search``).  Read-only diagnostics: which kernel instantiation a request reached."""
         li = _lib.LaunchInfo()
@@ -328,7 +339,8 @@ class ProcessOutputs:
     output_shapes: np.ndarray    # int32[2*n_columns] host
     output_row_strides: np.ndarray
     buffer: "object"             # torch.uint8 arena (output 2)
-    groups: list                 # torch.float32 [rows, width] views per concat group (CONCAT layout)
+    groups: list                 # [rows, width] views per concat group (CONCAT layout): torch.float32, or torch.bfloat16 /
+                                 # torch.float16 for a narrow-output plan
     group_shapes: np.ndarray
 
     def wait(self, stream: Optional[int] = None) -> None:
@@ -344,9 +356,17 @@ class ProcessOutputs:
         """torch view of column k's output ([rows, dim], possibly strided)."""
         import torch
         rows, dim = int(self.output_shapes[2 * k]), int(self.output_shapes[2 * k + 1])
-        off = (int(self.output_ptrs[k]) - self.buffer.data_ptr()) // 4
-        f = self.buffer.view(torch.float32)
+        dtype = self.groups[0].dtype if self.groups else torch.float32
+        f = _typed_arena(torch, self.buffer, dtype)
+        off = (int(self.output_ptrs[k]) - self.buffer.data_ptr()) // f.element_size()
         return f.as_strided((rows, dim), (int(self.output_row_strides[k]), 1), off)
+
+
+def _typed_arena(torch, arena, dtype):
+    """The uint8 arena as elements of the plan's output type (float32 arenas as ever; a narrow plan's as 2-byte elements)."""
+    if dtype == torch.float32:
+        return arena.view(torch.float32)
+    return arena[:arena.numel() // 2 * 2].view(dtype)
 
 
 class FeatureColumnProcess:
@@ -368,6 +388,8 @@ class FeatureColumnProcess:
         self.plan = plan if plan is not None else Plan(spec, device)
         self.spec = spec
         self._L = self.plan._L
+        # the element type of the outputs as the LIBRARY holds it (a plan file, or flag bits, may have chosen it)
+        self.out_dtype = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[self.plan.out_dtype()]
 
     @classmethod
     def from_plan_file(cls, dlpath: str, device: int = 0) -> "FeatureColumnProcess":
@@ -448,11 +470,11 @@ class FeatureColumnProcess:
         arena = keep[5]["arena"]
         if getattr(self.plan, "private_streams", 0):
             _lib.check(self._L.fcp_result_wait(arena.data_ptr(), a.stream), "fcp_result_wait")
-        f = arena.view(torch.float32)
+        f = _typed_arena(torch, arena, self.out_dtype)
         out = []
         for gi in range(g):
             rows, width = _grp_shapes[2 * gi], _grp_shapes[2 * gi + 1]
-            off = ((_grp_ptrs[gi] or arena.data_ptr()) - arena.data_ptr()) // 4
+            off = ((_grp_ptrs[gi] or arena.data_ptr()) - arena.data_ptr()) // f.element_size()
             out.append(f[off:off + rows * width].view(rows, width))
         return out
 
@@ -483,10 +505,10 @@ class FeatureColumnProcess:
         gshapes = np.array(_grp_shapes[:], np.int32)
         groups = []
         if self.spec.layout == LAYOUT_CONCAT:
-            f = arena.view(torch.float32)
+            f = _typed_arena(torch, arena, self.out_dtype)
             for gi in range(g):
                 rows, width = int(gshapes[2 * gi]), int(gshapes[2 * gi + 1])
-                off = ((_grp_ptrs[gi] or arena.data_ptr()) - arena.data_ptr()) // 4
+                off = ((_grp_ptrs[gi] or arena.data_ptr()) - arena.data_ptr()) // f.element_size()
                 groups.append(f[off:off + rows * width].view(rows, width))
         return ProcessOutputs(out_ptrs, out_shapes, strides, arena, groups, gshapes)
 

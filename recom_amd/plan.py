@@ -33,6 +33,11 @@ STAGE_COPY, STAGE_NARROW_I64, STAGE_SEG_TO_CSR = 0, 1, 2  # fcp_stager_stage_ex 
 XFORM_NONE, XFORM_SELECT, XFORM_FILTER = 0, 1, 2   # id transforms (SelectValue / GatherIndiceValue family)
 LAYOUT_CONCAT, LAYOUT_PER_COLUMN = 0, 1
 FLAG_COUNT_BAD_IDS = 1
+FLAG_OUT_BF16, FLAG_OUT_F16 = 1 << 1, 1 << 2   # narrow output (PlanSpec.out_dtype sets the bit)
+
+
+class NarrowOutputUnsupported(ValueError):
+    """A plan kind the narrow-output kernels do not serve (the library answers FCP_ERR_UNSUPPORTED)."""
 
 _ID_ELEM_SIZE = {IDS_I32: 4, IDS_I64: 8, IDS_F32_BUCKETIZE: 4}
 _ID_NP_DTYPE = {IDS_I32: np.int32, IDS_I64: np.int64, IDS_F32_BUCKETIZE: np.float32}
@@ -160,6 +165,9 @@ class PlanSpec:
     shard_rank: int = 0
     shard_world: int = 1
     flags: int = 0
+    # element type of the concat groups: "f32", or — narrow output, FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16 — "bf16" / "f16":
+    # every element is the float32 value rounded once, to nearest-even, at the store
+    out_dtype: str = "f32"
 
     # ---- static layout facts ------------------------------------------------
     def validate(self) -> None:
@@ -183,6 +191,41 @@ class PlanSpec:
                 raise ValueError(f"column {k}: table_input out of range")
             if c.rows_source == ROWS_FROM_SYMBOL and not 0 <= c.rows_arg < self.n_symbols:
                 raise ValueError(f"column {k}: symbol index out of range")
+        self.validate_out_dtype()
+
+    def plan_flags(self) -> int:
+        """``fcp_plan_desc_t::flags``: ``flags`` plus the bit ``out_dtype`` stands for."""
+        return self.flags | {"f32": 0, "bf16": FLAG_OUT_BF16, "f16": FLAG_OUT_F16}.get(self.out_dtype, 0)
+
+    @property
+    def out_elem_size(self) -> int:
+        return 4 if self.out_dtype == "f32" else 2
+
+    def validate_out_dtype(self) -> None:
+        """The library's rules for narrow output (``fcp_plan_create``): one dtype, and none of the four plan kinds the narrow
+        kernels do not serve.  ``NarrowOutputUnsupported`` mirrors FCP_ERR_UNSUPPORTED, ValueError FCP_ERR_INVALID_ARGUMENT."""
+        if self.out_dtype not in ("f32", "bf16", "f16"):
+            raise ValueError(f"out_dtype must be 'f32', 'bf16' or 'f16', not {self.out_dtype!r}")
+        f = self.plan_flags()
+        if not f & (FLAG_OUT_BF16 | FLAG_OUT_F16):
+            return
+        if f & FLAG_OUT_BF16 and f & FLAG_OUT_F16:
+            raise ValueError("FCP_FLAG_OUT_BF16 and FCP_FLAG_OUT_F16 exclude each other")
+        if self.shard_world > 1:
+            raise NarrowOutputUnsupported("narrow output on a row-sharded plan (shard_world > 1): partial sums cross the exchange in float32")
+        if self.layout == LAYOUT_PER_COLUMN:
+            raise NarrowOutputUnsupported("narrow output needs FCP_LAYOUT_CONCAT: FCP_LAYOUT_PER_COLUMN is the reference's float32 arena")
+        for k, c in enumerate(self.columns):
+            if c.form == FORM_EXTERNAL:
+                raise NarrowOutputUnsupported(f"column {k}: narrow output with an FCP_FORM_EXTERNAL slot: fcp_concat_outputs_host "
+                                              "scatters float32 payloads")
+            if c.weights_input >= 0:
+                raise NarrowOutputUnsupported(f"column {k}: narrow output with per-id weights: weighted plans take the float32 weighted kernel")
+            if c.combiner == COMBINER_SQRTN and c.form == FORM_SEGMENT_REDUCE:
+                raise NarrowOutputUnsupported(f"column {k}: narrow output with FCP_COMBINER_SQRTN: sqrtn plans take the float32 weighted kernel")
+
+    def with_out_dtype(self, out_dtype: str) -> "PlanSpec":
+        return dataclasses.replace(self, out_dtype=out_dtype)
 
     @property
     def n_columns(self) -> int:
@@ -222,6 +265,8 @@ class PlanSpec:
         """Plain-dict form (what the oracle wrapper consumes; keeps oracle/ free of
         product imports)."""
         d = dataclasses.asdict(self)
+        if self.out_dtype == "f32":        # the float32 plan's dict is what it always was (the oracle sees no new key)
+            del d["out_dtype"]
         for c, src in zip(d["columns"], self.columns):
             c["boundaries"] = None if src.boundaries is None else np.asarray(src.boundaries, np.float32)
             c["xform_lo"] = [int(v) for v in src.xform_lo]
@@ -358,7 +403,7 @@ class PlanSpec:
     def algorithmic_bytes(self, shapes: Sequence[int], symbols: Optional[Sequence[int]] = None) -> dict:
         """Algorithmic bytes of one request: table rows read + ids read + CSR
         offsets / segment ids read + bucketize boundaries + pooled output written
-        once in concat layout (+ 4 bytes per id of a weighted column: key ``weights``, present only in plans that have
+        once in concat layout, 2 bytes per element in a narrow-output plan (+ 4 bytes per id of a weighted column: key ``weights``, present only in plans that have
         one).  No intermediate traffic is counted."""
         so = self.shape_offsets()
 
@@ -373,7 +418,7 @@ class PlanSpec:
             if c.form == FORM_EXTERNAL:      # written by fcp_concat_outputs_host, not by the fused kernel
                 continue
             rows = self.column_rows(c, shapes, symbols)
-            out_b += rows * c.dim * 4
+            out_b += rows * c.dim * self.out_elem_size
             if c.form == FORM_PASSTHROUGH:
                 rows_b += rows * c.dim * 4
             elif c.form == FORM_BATCH_COL_REDUCTION:

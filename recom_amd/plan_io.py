@@ -20,7 +20,10 @@ def save_plan(spec: PlanSpec, path: str, stage: "StageInfo | None" = None) -> No
         maps = [(k, c) for k, c in enumerate(spec.columns) if len(c.seg_mul)]
         weights = [(k, c) for k, c in enumerate(spec.columns) if c.weights_input >= 0]
         v5 = bool(weights) or any(c.combiner == COMBINER_SQRTN for c in spec.columns)
-        f.write(f"fcp_plan {5 if v5 else 4 if maps else 3 if stage is not None else 2}\n")
+        if spec.out_dtype != "f32":   # version 6, narrow-output plans only: the dtype is the file's second line
+            f.write(f"fcp_plan 6\nout_dtype {spec.out_dtype}\n")
+        else:
+            f.write(f"fcp_plan {5 if v5 else 4 if maps else 3 if stage is not None else 2}\n")
         f.write(f"layout {spec.layout}\n")
         f.write(f"groups {spec.n_groups} symbols {spec.n_symbols} device_inputs {spec.n_device_inputs}\n")
         f.write(f"host_inputs {spec.n_host_inputs}\n")
@@ -65,9 +68,17 @@ def load_plan(path: str) -> PlanSpec:
     if nxt() != "fcp_plan":
         raise ValueError("bad plan header")
     version = int(nxt())
-    if version not in (1, 2, 3, 4, 5):
+    if version not in (1, 2, 3, 4, 5, 6):
         raise ValueError("bad plan header")
-    assert nxt() == "layout"
+    out_dtype = "f32"
+    if version >= 6:              # "out_dtype bf16|f16": here and nowhere else, in version 6 files and no others
+        if nxt() != "out_dtype":
+            raise ValueError(f"expected 'out_dtype bf16' or 'out_dtype f16' in {path}")
+        out_dtype = nxt()
+        if out_dtype not in ("bf16", "f16"):
+            raise ValueError(f"unknown out_dtype {out_dtype!r} in {path}")
+    if nxt() != "layout":
+        raise ValueError(f"expected 'layout' in {path}")
     layout = int(nxt())
     assert nxt() == "groups"
     n_groups = int(nxt())
@@ -116,7 +127,9 @@ def load_plan(path: str) -> PlanSpec:
             v = [int(x) for x in rest[2 + 9 * j: 11 + 9 * j]]
             cols[v[0]] = dataclasses.replace(cols[v[0]], seg_mul=tuple(v[4:4 + v[1]]), seg_div=v[8], seg_sym=v[2],
                                              seg_sym_slot=v[3])
-    spec = PlanSpec(cols, ranks, esz, n_dev, n_groups=n_groups, n_symbols=n_symbols, layout=layout)
+    if tok.count("out_dtype") != (1 if version >= 6 else 0):   # anywhere but the second line, twice, or in an older file
+        raise ValueError(f"misplaced or repeated out_dtype line in {path}")
+    spec = PlanSpec(cols, ranks, esz, n_dev, n_groups=n_groups, n_symbols=n_symbols, layout=layout, out_dtype=out_dtype)
     spec.validate()
     return spec
 
