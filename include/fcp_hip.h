@@ -459,6 +459,12 @@ typedef struct fcp_launch_info {
   int32_t segment_offsets;  /* FCP_LAUNCH_SEG_*: segment-id columns took the pre-pass kernel, or the blocks searched */
 } fcp_launch_info_t;
 int fcp_plan_last_launch(const fcp_plan_t *plan, fcp_launch_info_t *out);
+/* Which front the dense kernel of the plan's most recent request had: the generic one (fcp_dense_kernel and its hybrid /
+ * narrow forms) or the plain one (fcp_dense_kernel_plain: float32 concat plans of one group whose columns are all plain
+ * gathers, requests of at least 64 rows; FCP_DIAG=dense_generic at plan creation keeps such a plan on the generic kernel).
+ * fcp_plan_last_launch reports FCP_LAUNCH_DENSE, V 4, R 4 and the same grid for both.  Relaxed stores, as there. */
+enum { FCP_DENSE_FRONT_NONE = 0, FCP_DENSE_FRONT_GENERIC = 1, FCP_DENSE_FRONT_PLAIN = 2 };
+int fcp_plan_last_dense_front(const fcp_plan_t *plan, int32_t *front);
 /* Where the plan's most recent request put its segment-offset scratch (the pre-pass's CSR offsets, or the inverse map of
  * an any-order ScatterNd column): *csr_arena_off = its byte offset in the request's arena (-1 before the first request),
  * csr_base[k] = the int32 index of column k's range inside it, or -1 for a column without one (k < capacity; either

@@ -69,6 +69,7 @@ struct DynMeta {
   int32_t max_seg_nnz = 0;
   int64_t seg_pairs = 0;   // sum of rows over the segment-id columns: cost of the in-block search
   bool seg_search = false; // this request: blocks search the segment ids (no pre-pass launch)
+  bool plain = false;      // plain dense plan and at least 64 rows: the request takes fcp_dense_kernel_plain (its span image is built)
   int64_t work_bytes = 0;  // table rows gathered + output written: what decides whether a private lane pays (fcp_plan_set_private_streams)
   // regular CSR (FcpLaunch::csr_reg): 0 = none, 1 = the arena scratch laid out by column position, 2 = CSR inputs that lie
   // one stride apart in the blob; byte offset of position 0's array in the arena / the blob; stride in int32 elements
@@ -102,6 +103,7 @@ struct DynSlot {
   int uses = 0;                  // requests that have used this content since it was installed
   bool captured = false;         // a stream capture recorded a launch that reads this slot: a graph replay will read
                                  // it at any later time, so it is never evicted (fcp_plan_release_captures)
+  bool img_built = false;        // plain dense plans: the slot holds a span image (rewritten when tables are re-bound); under the plan's mutex
   bool was_valid = false;        // reserved for installation: the previous content had readers to wait for
   DynMeta meta;
 };
@@ -267,6 +269,17 @@ struct fcp_plan {
   // without weighted columns have no such array).  weighted_kernel: has_weights, or some column's combiner is SQRTN — all
   // spans of the plan run the weighted ragged kernel.
   bool has_weights = false, weighted_kernel = false;
+  // Plain dense plan (fcp_dense_plain.hip): float32 concat output, one group, unsharded, V 4, no wide rows, no id transform,
+  // every column a gather by int32 / int64 ids or by float32 values bucketized with reproducible boundaries.  Decided at
+  // plan creation (FCP_DIAG=dense_generic keeps such a plan on the generic kernel).  Every descriptor slot then carries,
+  // behind its FcpColDyn records, the per-span image: plain_spans records of plain_stride bytes.  plain_tmpl is the image
+  // with everything that does not depend on the request or the bound tables; plain_entries names, per FcpPlainCol of the
+  // image, its byte offset there and the column (concat position) it describes.
+  bool plain_dense = false;
+  int32_t plain_stride = 0, plain_spans = 0;
+  std::vector<char> plain_tmpl;
+  std::vector<std::pair<uint32_t, int32_t>> plain_entries;
+  std::atomic<int32_t> last_dense_front{0}; // fcp_plan_last_dense_front: FCP_DENSE_FRONT_* of the last request
   bool wide_rows = false; // some table shard has >= 2^32 - 3 slots: FcpLaunch::store_through bit 1
   // narrow output (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16): the element type (FCP_OUT_*) and its size in bytes — every byte
   // quantity of the output region (group sizes, column bases, the position of the CSR scratch) is formed with out_elem
@@ -354,11 +367,15 @@ int compute_dyn(const fcp_plan *p, const int32_t *offsets, const int32_t *shapes
 int compute_weights(const fcp_plan *p, const int32_t *offsets, const int32_t *shapes, int64_t *wts);
 // bytes of one descriptor slot: the FcpColDyn records and, in plans with weighted columns, the weights' offsets behind them
 inline size_t slot_dyn_bytes(const fcp_plan *p) {
-  return p->cols.size() * sizeof(FcpColDyn) + (p->has_weights ? p->cols.size() * sizeof(int64_t) : 0);
+  return p->cols.size() * sizeof(FcpColDyn) + (p->has_weights ? p->cols.size() * sizeof(int64_t) : 0) +
+         (p->plain_dense ? p->plain_tmpl.size() : 0);
 }
+// plain dense plans (never weighted): the span image of a descriptor slot, behind its records (48-byte records: 16-byte aligned)
+inline size_t slot_image_off(const fcp_plan *p) { return p->cols.size() * sizeof(FcpColDyn); }
 inline const int64_t *slot_weights(const fcp_plan *p, const FcpColDyn *dyn) {
   return p->has_weights ? reinterpret_cast<const int64_t *>(dyn + p->cols.size()) : nullptr;
 }
+void build_plain_template(fcp_plan *p); // the gate and the image template of plain dense plans (plan creation)
 // fcp_process.hip
 bool stream_is_capturing(hipStream_t stream);
 int bind_tables(fcp_plan *p, const void *const *input_ptrs, bool capturing);

@@ -122,6 +122,39 @@ struct FcpLaunch {
   const float *zeros;          // 256 zero bytes (plan-owned): what a skipped id of a bag reads
 };
 
+// ---- plain dense plans (fcp_dense_plain.hip) -------------------------------------------------------------------------------
+// The per-span image of a plan whose columns are all plain gathers (fcp_plan::plain_dense): one fixed-stride record per
+// 64-slot span — FcpPlainSpan, then FcpPlainCol x the plan's largest column count per span — behind the FcpColDyn records
+// of a descriptor slot.  A block finds its record from its span index and the kernel arguments alone, and the record
+// holds everything the block needs: no slot map, no static / dynamic column records.  A column that straddles a span
+// boundary appears in both records.
+struct FcpPlainCol {       // 48 bytes
+  const float *table;      // device address of the table
+  int64_t ids_off;         // byte offset of the id / value stream in the blob
+  uint32_t vocab;          // rows of the table (every table of such a plan has < 2^32 - 3 slots)
+  uint32_t spr;            // slots per table row (dim / 4)
+  int32_t out_off;         // element offset of the column in the concat row
+  uint32_t kind;           // FCP_IDS_I32 | FCP_IDS_I64 | FCP_IDS_F32_BUCKETIZE (reproducible boundaries only)
+  int32_t n_boundaries;
+  float bnd_b0, bnd_inv, bnd_step;
+};
+struct FcpPlainSpan {      // 80 bytes
+  int32_t ncols;           // columns with a slot in the span
+  int32_t pad_[3];
+  uint8_t lane_col[FCP_WAVE]; // slot of the span -> index of its column among the span's FcpPlainCol
+};
+// kernel arguments: 15 dwords, passed one by one so that they can be preloaded into SGPRs
+struct FcpPlainLaunch {
+  const char *img;         // the span records
+  const char *blob;
+  float *out;              // element (0, 0) of the concat group in the arena
+  unsigned long long *bad_ids; // nullable
+  int32_t rows, nslots, nsp8, nlist; // as FcpGroupLaunch (the grid and the block mapping are the generic dense kernel's)
+  int32_t img_stride;      // bytes per span record (a multiple of 16)
+  int32_t out_stride;      // row stride of the output in elements
+  int32_t store_policy;    // FcpLaunch::store_through bits 0 and 2
+};
+
 // Segment-offset pre-pass (ComputeSegmentOffsets, cuda_emitter.cc:768-818)
 struct FcpSegLaunch {
   const int32_t *seg_cols;   // indices of the columns whose seg_kind is IDS_*
@@ -155,6 +188,8 @@ int fcp_launch_weighted(const FcpLaunch &L, const int64_t *wts, int vec, int gri
 int fcp_launch_narrow(const FcpLaunch &L, int vec, bool dense_kernel, int out_kind, int grid_blocks, ihipStream_t *s);
 int fcp_launch_narrow_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch &Lragged, int ragged_blocks, int vec,
                              int out_kind, ihipStream_t *s);
+// (fcp_dense_plain.hip) the small dense kernel of plain dense plans: V 4, R 4, the grid of fcp_launch_fused's dense kernel
+int fcp_launch_dense_plain(const FcpPlainLaunch &P, int grid_blocks, ihipStream_t *s);
 // what the next fused launch of this thread would carry (stop event, any-order flag): taken and cleared
 void fcp_take_launch_extras(void **stop_event, int *flags);
 int fcp_launch_upload(const void *host_mapped_src, void *dst, size_t bytes, ihipStream_t *s);

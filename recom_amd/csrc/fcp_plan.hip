@@ -605,6 +605,78 @@ void uniform_boundaries(const std::vector<float> &b, float *b0, float *inv, floa
   *step_out = step;
 }
 
+// Plain dense plans (fcp_dense_plain.hip): the gate, and the per-span image with everything that is known now — the
+// lane -> column maps and the columns' static facts; table addresses and id-stream offsets are filled in per descriptor
+// slot (fill_plain_image).  Called once the static records exist (their boundary constants are the image's).
+void build_plain_template(fcp_plan *p) {
+  p->plain_dense = false;
+  // FCP_DIAG=dense_generic: a qualifying plan stays on the generic kernel (the tests' seam)
+  if (fcp::diag_ll("dense_generic", 0) != 0) return;
+  const fcp_plan_desc_t &d = p->desc;
+  if (p->out_elem != 4 || d.layout != FCP_LAYOUT_CONCAT || d.n_groups != 1 || d.shard_world > 1 || p->vec != 4 || p->wide_rows ||
+      p->weighted_kernel || !p->dense_only || p->cols.empty())
+    return;
+  const int nc = (int)p->cols.size();
+  for (int pos = 0; pos < nc; ++pos) {
+    const HostColumn &hc = p->cols[p->order[pos]];
+    const FcpColStatic &s = p->h_cols[pos];
+    if (hc.d.form != FCP_FORM_GATHER || s.xform != 0 || hc.d.vocab < 0 || hc.d.vocab >= 0xFFFFFFFDLL) return;
+    if (hc.d.id_source == FCP_IDS_F32_BUCKETIZE) {
+      if (s.bnd_step == 0.0f) return; // boundaries that are read (staged in LDS or searched in L2): the generic body's
+    } else if (hc.d.id_source != FCP_IDS_I32 && hc.d.id_source != FCP_IDS_I64) {
+      return;
+    }
+  }
+  const int nslots = p->group_nslots[0];
+  const int nspans = (nslots + FCP_WAVE - 1) / FCP_WAVE;
+  if (p->list_n[0][0] != nspans) return;
+  // columns per span (concat order: a span's columns are consecutive positions)
+  std::vector<int> first(nspans, nc), last(nspans, -1);
+  for (int pos = 0; pos < nc; ++pos) {
+    const FcpColStatic &s = p->h_cols[pos];
+    const int s0 = s.out_off / 4 / FCP_WAVE, s1 = (s.out_off + s.dim - 1) / 4 / FCP_WAVE;
+    for (int sp = s0; sp <= s1; ++sp) {
+      first[sp] = std::min(first[sp], pos);
+      last[sp] = std::max(last[sp], pos);
+    }
+  }
+  int max_cols = 1;
+  for (int sp = 0; sp < nspans; ++sp) max_cols = std::max(max_cols, last[sp] - first[sp] + 1);
+  if (max_cols > FCP_WAVE) return; // (cannot happen: a column has at least one slot)
+  p->plain_stride = (int32_t)(sizeof(FcpPlainSpan) + (size_t)max_cols * sizeof(FcpPlainCol));
+  p->plain_spans = nspans;
+  p->plain_tmpl.assign((size_t)nspans * p->plain_stride, 0);
+  p->plain_entries.clear();
+  for (int sp = 0; sp < nspans; ++sp) {
+    char *rec = p->plain_tmpl.data() + (size_t)sp * p->plain_stride;
+    FcpPlainSpan head;
+    std::memset(&head, 0, sizeof(head));
+    head.ncols = last[sp] - first[sp] + 1;
+    for (int pos = first[sp]; pos <= last[sp]; ++pos) {
+      const FcpColStatic &s = p->h_cols[pos];
+      FcpPlainCol c;
+      std::memset(&c, 0, sizeof(c));
+      c.table = nullptr;
+      c.ids_off = 0;
+      c.vocab = (uint32_t)s.vocab;
+      c.spr = (uint32_t)(s.dim / 4);
+      c.out_off = s.out_off;
+      c.kind = FCP_F_IDSRC(s.flags);
+      c.n_boundaries = s.n_boundaries;
+      c.bnd_b0 = s.bnd_b0;
+      c.bnd_inv = s.bnd_inv;
+      c.bnd_step = s.bnd_step;
+      const size_t at = (size_t)sp * p->plain_stride + sizeof(FcpPlainSpan) + (size_t)(pos - first[sp]) * sizeof(FcpPlainCol);
+      std::memcpy(p->plain_tmpl.data() + at, &c, sizeof(c));
+      p->plain_entries.emplace_back((uint32_t)at, pos);
+      for (int q = std::max(s.out_off / 4, sp * FCP_WAVE); q < std::min((s.out_off + s.dim) / 4, (sp + 1) * FCP_WAVE); ++q)
+        head.lane_col[q - sp * FCP_WAVE] = (uint8_t)(pos - first[sp]);
+    }
+    std::memcpy(rec, &head, sizeof(head));
+  }
+  p->plain_dense = true;
+}
+
 void destroy_device(fcp_plan *p) {
   if (p->host_only) return;
   for (auto &s : p->slots) {
@@ -731,6 +803,7 @@ int init_device(fcp_plan *p) {
       }
     }
   }
+  build_plain_template(p); // (before the descriptor slots are sized: a plain dense plan's slots carry the span image)
   HIP_TRY(hipMalloc(&p->d_cols, nc * sizeof(FcpColStatic)));
   HIP_TRY(hipMemcpy(p->d_cols, p->h_cols.data(), nc * sizeof(FcpColStatic), hipMemcpyHostToDevice));
   if (!h_xforms.empty()) {
@@ -1442,6 +1515,12 @@ int fcp_plan_last_launch(const fcp_plan_t *p, fcp_launch_info_t *out) {
   out->dense_blocks = ll.dense_blocks.load(std::memory_order_relaxed);
   out->ragged_blocks = ll.ragged_blocks.load(std::memory_order_relaxed);
   out->segment_offsets = ll.segment_offsets.load(std::memory_order_relaxed);
+  return FCP_OK;
+}
+
+int fcp_plan_last_dense_front(const fcp_plan_t *p, int32_t *front) {
+  if (!p || !front) return fail(FCP_ERR_INVALID_ARGUMENT, "null argument");
+  *front = p->last_dense_front.load(std::memory_order_relaxed);
   return FCP_OK;
 }
 

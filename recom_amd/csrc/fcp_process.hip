@@ -12,6 +12,18 @@ bool stream_is_capturing(hipStream_t stream) {
   return false;
 }
 
+// Plain dense plans: the span image of a descriptor slot (host copy, behind the slot's FcpColDyn records) = the plan's
+// template + what the request and the bound tables decide: every column's id stream and table address.
+static void fill_plain_image(const fcp_plan *p, const FcpColStatic *cols, FcpColDyn *h_dyn) {
+  char *img = reinterpret_cast<char *>(h_dyn) + slot_image_off(p);
+  std::memcpy(img, p->plain_tmpl.data(), p->plain_tmpl.size());
+  for (const auto &e : p->plain_entries) {
+    FcpPlainCol *c = reinterpret_cast<FcpPlainCol *>(img + e.first);
+    c->table = cols[e.second].table;
+    c->ids_off = h_dyn[e.second].ids_off;
+  }
+}
+
 // Bind the table addresses (FeatureColumnProcess `inputs`).  TF variables keep their address between requests, so this
 // uploads once.  `capturing`: the caller's stream is being captured into a HIP graph — binding (or re-binding) tables copies records
 // and may synchronise the device, neither of which a capture tolerates: refused, the plan stays as it was.
@@ -39,6 +51,15 @@ int bind_tables(fcp_plan *p, const void *const *input_ptrs, bool capturing) {
   p->tables_bound = false;                               // until the upload below has succeeded
   HIP_TRY(hipMemcpy(p->d_cols, cols.data(), cols.size() * sizeof(FcpColStatic), hipMemcpyHostToDevice));
   p->h_cols.swap(cols);
+  if (p->plain_dense) { // the span images hold table addresses: rebuilt (the device has drained; the caller holds the plan's mutex)
+    for (auto &s : p->slots) {
+      if (!s.img_built) continue;
+      fill_plain_image(p, p->h_cols.data(), s.h_dyn);
+      const size_t off = slot_image_off(p);
+      HIP_TRY(hipMemcpy(reinterpret_cast<char *>(s.d_dyn) + off, reinterpret_cast<const char *>(s.h_dyn) + off, p->plain_tmpl.size(),
+                        hipMemcpyHostToDevice));
+    }
+  }
   for (int t = 0; t < nt; ++t) p->bound_tables[t] = input_ptrs[t];
   p->tables_bound = true;
   return FCP_OK;
@@ -119,6 +140,7 @@ int find_or_reserve(fcp_plan *p, const std::vector<int32_t> &key, DynSlot **out,
     return pinned == kSlots ? fail(FCP_ERR_UNSUPPORTED, "every descriptor slot belongs to a captured graph: fcp_plan_release_captures")
                             : kAllSlotsBusy; // more concurrent requests than slots: the caller retries
   victim->was_valid = victim->valid;
+  victim->img_built = false;
   victim->valid = false;
   victim->users = 1;
   *out = victim;
@@ -152,7 +174,19 @@ int install_slot(fcp_plan *p, const fcp_process_args_t *a, DynSlot &s) {
     if (rc) return rc;
   }
   p->last_work_bytes.store(s.meta.work_bytes, std::memory_order_relaxed);
-  const size_t dyn_bytes = slot_dyn_bytes(p);
+  // Plain dense plans: requests of at least 64 rows (R = 4) take fcp_dense_kernel_plain and need the slot's span image.  It
+  // holds table addresses, so it is built and handed to the device under the plan's mutex: a re-bind of the tables
+  // (bind_tables, same mutex) either sees this image and rewrites it, or has happened before.
+  s.meta.plain = p->plain_dense && s.meta.geo[0].rows_per_wave == 4 && s.meta.geo[1].grid_blocks == 0 &&
+                 s.meta.geo[0].groups[0].span_list_off < 0 && s.meta.geo[0].groups[0].nlist == p->plain_spans;
+  std::unique_lock<std::mutex> image_lock(p->mu, std::defer_lock);
+  if (s.meta.plain) {
+    image_lock.lock();
+    fill_plain_image(p, p->h_cols.data(), s.h_dyn);
+    s.img_built = true;
+  }
+  // (the image is the tail of the slot: shapes that do not take the plain kernel upload the records only)
+  const size_t dyn_bytes = s.meta.plain ? slot_dyn_bytes(p) : (slot_dyn_bytes(p) - (p->plain_dense ? p->plain_tmpl.size() : 0));
   if (p->host_writes_dyn) {
     std::memcpy(s.d_dyn, s.h_dyn, dyn_bytes); // CPU stores through the BAR into fine-grained VRAM
     __builtin_ia32_sfence();                  // posted before the launch's doorbell write
@@ -315,6 +349,10 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
                     : (p->out_elem == 2 && fused) ? fused + (FCP_LAUNCH_DENSE_NARROW - FCP_LAUNCH_DENSE) // narrow plans: fcp_narrow.hip
                                                   : fused,
                     std::memory_order_relaxed);
+    p->last_dense_front.store(m.geo[0].grid_blocks <= 0 || p->weighted_kernel ? FCP_DENSE_FRONT_NONE
+                              : m.plain                                       ? FCP_DENSE_FRONT_PLAIN
+                                                                              : FCP_DENSE_FRONT_GENERIC,
+                              std::memory_order_relaxed);
     ll.rows_per_wave.store(m.geo[0].rows_per_wave, std::memory_order_relaxed);
     ll.store_policy.store(store_policy, std::memory_order_relaxed);
     ll.dense_blocks.store(m.geo[0].grid_blocks, std::memory_order_relaxed);
@@ -392,6 +430,22 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
   } else if (m.geo[1].grid_blocks > 0) {
     const int e = fcp_launch_fused(L, p->vec, false, m.geo[1].grid_blocks, stream);
     if (e) return hip_fail("ragged kernel launch", (hipError_t)e);
+  } else if (m.geo[0].grid_blocks > 0 && m.plain) { // plain dense plan: the small dense kernel, same grid (fcp_dense_plain.hip)
+    const FcpGroupLaunch &G = m.geo[0].groups[0];
+    FcpPlainLaunch P;
+    P.img = reinterpret_cast<const char *>(slot->d_dyn) + slot_image_off(p);
+    P.blob = static_cast<const char *>(a->concated_inputs);
+    P.out = reinterpret_cast<float *>(static_cast<char *>(arena) + m.group_base[0]);
+    P.bad_ids = p->d_bad;
+    P.rows = G.rows;
+    P.nslots = G.nslots;
+    P.nsp8 = G.nsp8;
+    P.nlist = G.nlist;
+    P.img_stride = p->plain_stride;
+    P.out_stride = p->group_width[0];
+    P.store_policy = store_policy;
+    const int e = fcp_launch_dense_plain(P, m.geo[0].grid_blocks, stream);
+    if (e) return hip_fail("plain dense kernel launch", (hipError_t)e);
   } else if (m.geo[0].grid_blocks > 0) {
     fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &L);
     const int e = fcp_launch_fused(L, p->vec, true, m.geo[0].grid_blocks, stream);

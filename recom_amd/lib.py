@@ -29,6 +29,7 @@ OUT_DTYPE_FLAGS = {"f32": 0, "bf16": FLAG_OUT_BF16, "f16": FLAG_OUT_F16}
 # fcp_launch_info_t (fcp_plan_last_launch): names of the kernel, store-policy and segment-offset codes
 LAUNCH_KERNELS = {0: "none", 1: "dense", 2: "ragged", 3: "hybrid", 4: "ragged_weighted",
                   5: "dense_narrow", 6: "ragged_narrow", 7: "hybrid_narrow"}
+DENSE_FRONTS = {0: "none", 1: "generic", 2: "plain"}   # fcp_plan_last_dense_front
 LAUNCH_STORES = {0: "nt", 1: "sc1_nt", 4: "plain"}
 LAUNCH_SEGMENT_OFFSETS = {0: "none", 1: "prepass", 2: "search"}
 # fcp_aux_launch_counts: the kernels outside the fused matrix, one counter per instantiation (FCP_AUX_* order)
@@ -152,7 +153,7 @@ EXPORTS = [
     "fcp_plan_set_private_streams", "fcp_result_wait", "fcp_result_synchronize", "fcp_plan_set_request_order",
     "fcp_plan_probe_private_streams", "fcp_plan_private_streams_verdict", "fcp_plan_verify_private_streams",
     "fcp_plan_private_streams_stats", "fcp_plan_last_launch", "fcp_plan_last_csr", "fcp_aux_launch_counts",
-    "fcp_plan_out_dtype",
+    "fcp_plan_out_dtype", "fcp_plan_last_dense_front",
 ]
 
 _lib = None
@@ -298,6 +299,8 @@ def load() -> C.CDLL:
     if hasattr(L, "fcp_aux_launch_counts"):
         L.fcp_plan_last_csr.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_int32]
         L.fcp_aux_launch_counts.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    if hasattr(L, "fcp_plan_last_dense_front"):
+        L.fcp_plan_last_dense_front.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     if L.fcp_abi_version() != FCP_ABI_VERSION:
         raise ImportError("libfcp_hip.so ABI version mismatch; rebuild")
     _lib = L

@@ -321,6 +321,13 @@ class Plan:
                     dense_blocks=li.dense_blocks, ragged_blocks=li.ragged_blocks,
                     segment_offsets=_lib.LAUNCH_SEGMENT_OFFSETS[li.segment_offsets])
 
+    def last_dense_front(self) -> str:
+        """``fcp_plan_last_dense_front``: ``none`` / ``generic`` / ``plain`` — which front the dense kernel of the plan's
+        most recent request had (``plain``: fcp_dense_kernel_plain).  Read-only diagnostics."""
+        v = C.c_int32()
+        _lib.check(self._L.fcp_plan_last_dense_front(self.handle, C.byref(v)), "fcp_plan_last_dense_front")
+        return _lib.DENSE_FRONTS[v.value]
+
     def last_csr(self):
         """``fcp_plan_last_csr``: (byte offset of the most recent request's segment-offset scratch in its arena, or -1;
         int32[n_columns] index of each column's range in it, -1 for a column without one).  Read-only diagnostics."""
