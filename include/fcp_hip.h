@@ -184,10 +184,25 @@ enum {
    * reference's float32 arena), any FCP_FORM_EXTERNAL column (fcp_concat_outputs_host scatters float32 payloads), any
    * column with per-id weights or FCP_COMBINER_SQRTN. */
   FCP_FLAG_OUT_BF16 = 1u << 1,
-  FCP_FLAG_OUT_F16 = 1u << 2
+  FCP_FLAG_OUT_F16 = 1u << 2,
+  /* 16-bit tables: EVERY embedding table of the plan (every device input a GATHER / SEGMENT_REDUCE / GATHER_SCATTER
+   * column reads) is bf16 / fp16, row-major [vocab, dim], 2 bytes per element, its base 2 * V-byte aligned (V = 4 | 2 | 1:
+   * the largest of them dividing every column's dim and offset; 8 bytes always suffice).  A 16-bit element widens to
+   * float32 EXACTLY, so the plan computes, bit for bit, what the same plan without the bit computes on the widened tables:
+   * gathers, scatters, pooled sums and means in id order from +0.0, range checks, the zeros of ids outside the vocabulary.
+   * bf16 widens in integers (pattern << 16: a copied NaN keeps sign and payload); an fp16 NaN widens to some NaN.
+   * Everything else is unchanged — the geometry, the float32 output, the blob (PASSTHROUGH / BATCH_COL_REDUCTION payloads
+   * stay float32), both layouts, every id source and transform, FCP_FLAG_COUNT_BAD_IDS, 2^32 - 3 rows per table;
+   * fcp_plan_table_bytes counts 2 bytes per element.  At most one of the two bits (both: FCP_ERR_INVALID_ARGUMENT);
+   * neither: the float32-table plan and its code paths, exactly.  Refused with FCP_ERR_UNSUPPORTED: together with
+   * FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16, shard_world > 1, any column with per-id weights or FCP_COMBINER_SQRTN. */
+  FCP_FLAG_TABLES_BF16 = 1u << 3,
+  FCP_FLAG_TABLES_F16 = 1u << 4
 };
 /* element type of the plan's outputs (fcp_plan_out_dtype) */
 enum { FCP_OUT_F32 = 0, FCP_OUT_BF16 = 1, FCP_OUT_F16 = 2 };
+/* element type of the plan's embedding tables (fcp_plan_table_dtype) */
+enum { FCP_TAB_F32 = 0, FCP_TAB_BF16 = 1, FCP_TAB_F16 = 2 };
 /* A plan without device resources: layout / arena / table-byte queries and plan-file checks on a machine
  * without a GPU (offline graph tooling).  Anything that computes returns FCP_ERR_NO_DEVICE — there is no
  * CPU fallback.  (A macro: the value does not fit an int enumerator.) */
@@ -357,10 +372,14 @@ int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext,
  *   "weights M" + M lines "column input" (fcp_column_ext_t::weights_input1 - 1);
  *   version 6 files (narrow-output plans, and only those) carry "out_dtype bf16" or
  *   "out_dtype f16" as their SECOND line, between the header and "layout"; the line
- *   anywhere else, twice, with another name, or in a file of version <= 5 is malformed.
+ *   anywhere else, twice, with another name, or in a file of version <= 5 is malformed;
+ *   version 7 files (plans with 16-bit tables, and only those) carry "table_dtype bf16" or
+ *   "table_dtype f16" in the same place under the same rules (and no out_dtype line: the
+ *   two features exclude each other).
  * `flags`: fcp_plan_desc_t::flags.  FCP_FLAG_OUT_BF16 / _F16 on a file without the
  * line select the dtype; bits that name the file's dtype are fine, the other dtype is
- * FCP_ERR_INVALID_ARGUMENT.  FCP_ERR_INVALID_ARGUMENT for a missing or malformed file. */
+ * FCP_ERR_INVALID_ARGUMENT; FCP_FLAG_TABLES_BF16 / _F16 and a table_dtype line likewise.
+ * FCP_ERR_INVALID_ARGUMENT for a missing or malformed file. */
 int fcp_plan_create_from_file(const char *path, int32_t device, uint32_t flags,
                               fcp_plan_t **plan);
 int fcp_plan_destroy(fcp_plan_t *plan);
@@ -376,9 +395,12 @@ int fcp_plan_output_columns(const fcp_plan_t *plan, int32_t *n, int32_t *indices
                             int32_t capacity);
 /* FCP_OUT_*: the element type of the plan's outputs (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16). */
 int fcp_plan_out_dtype(const fcp_plan_t *plan, int32_t *out);
+/* FCP_TAB_*: the element type of the plan's embedding tables (FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16). */
+int fcp_plan_table_dtype(const fcp_plan_t *plan, int32_t *out);
 /* Bytes of embedding tables this plan reads on THIS device (its shard of every
  * table, shared tables counted once) and the largest single table's bytes
- * (unsharded) — the inputs of the placement gate, fcp_placement_decide. */
+ * (unsharded) — the inputs of the placement gate, fcp_placement_decide; 2 bytes per
+ * element in a plan with 16-bit tables. */
 int fcp_plan_table_bytes(const fcp_plan_t *plan, int64_t *shard_bytes,
                          int64_t *max_table_bytes_unsharded);
 /* ---- placement gate (replaces check_table_size, cuda_emitter.cc:1080-1094) -------- */
@@ -443,7 +465,9 @@ enum {
   /* the ragged body with per-id weights and the sqrtn combiner: every span of a plan that has a weighted or SQRTN column */
   FCP_LAUNCH_RAGGED_WEIGHTED = 4,
   /* the narrow-output instantiations of the three (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16 plans) */
-  FCP_LAUNCH_DENSE_NARROW = 5, FCP_LAUNCH_RAGGED_NARROW = 6, FCP_LAUNCH_HYBRID_NARROW = 7
+  FCP_LAUNCH_DENSE_NARROW = 5, FCP_LAUNCH_RAGGED_NARROW = 6, FCP_LAUNCH_HYBRID_NARROW = 7,
+  /* the 16-bit-table instantiations of the three (FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16 plans) */
+  FCP_LAUNCH_DENSE_TAB16 = 8, FCP_LAUNCH_RAGGED_TAB16 = 9, FCP_LAUNCH_HYBRID_TAB16 = 10
 };
 enum { FCP_LAUNCH_STORE_NT = 0, FCP_LAUNCH_STORE_SC1_NT = 1, FCP_LAUNCH_STORE_PLAIN = 4 };
 enum { FCP_LAUNCH_SEG_NONE = 0, FCP_LAUNCH_SEG_PREPASS = 1, FCP_LAUNCH_SEG_SEARCH = 2 };

@@ -208,6 +208,48 @@ template <int V> __device__ __forceinline__ VF<V> ld_slot32(const float *tb, uin
   return r;
 }
 
+// ---- 16-bit tables (fcp_tables16.hip: FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16 plans) -----------------------------------
+// A table element is 2 bytes and widens to float32 EXACTLY, so the plan computes what the float32 plan computes on the
+// widened tables.  bf16 in integers (the pattern moves to the high half: a NaN keeps sign and payload through a copy);
+// fp16 is the hardware conversion v_cvt_f32_f16 in the kernel's mode (16-bit denormals kept: subnormals widen exactly, a
+// NaN becomes some NaN).  A slot is still V elements: one load of 2 * V bytes — dwordx2 | dword | ushort (NarrowType<V>).
+// `tab_kind` (FCP_TAB_BF16 | FCP_TAB_F16) is the same for every wave of the launch (a kernel argument).
+template <int V> __device__ __forceinline__ VF<V> widen16(typename NarrowType<V>::T t, int tab_kind) {
+  uint32_t w[(V + 1) / 2];
+  if constexpr (V == 4) {
+    w[0] = t.x;
+    w[1] = t.y;
+  } else {
+    w[0] = t;
+  }
+  VF<V> r;
+  if (tab_kind == FCP_TAB_BF16) {
+#pragma unroll
+    for (int i = 0; i < V; ++i) r.v[i] = __uint_as_float((i & 1) ? (w[i / 2] & 0xFFFF0000u) : (w[i / 2] << 16));
+  } else {
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      const uint16_t b = (uint16_t)((i & 1) ? (w[i / 2] >> 16) : w[i / 2]);
+      _Float16 h;
+      __builtin_memcpy(&h, &b, 2);
+      r.v[i] = (float)h;
+    }
+  }
+  return r;
+}
+// The three loaders in their 16-bit forms.  `tb`: the lane-specific base as a BYTE address (table + 2 * element offset);
+// the slot offset is scaled by the slot's 2 * V bytes in 64 bits, as the float32 forms scale by 4 * V.
+template <int V> __device__ __forceinline__ VF<V> ld_slot16(const char *tb, uint32_t off, uint32_t spr, int tab_kind) {
+  typedef typename NarrowType<V>::T T;
+  const FCP_GLOBAL T *g = as_global(reinterpret_cast<const T *>(tb)) + (uint64_t)off * spr;
+  return widen16<V>(*g, tab_kind);
+}
+template <int V> __device__ __forceinline__ VF<V> ld_slot32_16(const char *tb, uint32_t off, int tab_kind) {
+  typedef typename NarrowType<V>::T T;
+  const FCP_GLOBAL T *g = as_global(reinterpret_cast<const T *>(tb)) + off;
+  return widen16<V>(*g, tab_kind);
+}
+
 // Blob tensors are only guaranteed 4-byte aligned (ConcatInputs packs bytes
 // back to back, concat_inputs_ops.cc:52-60): payloads are read dword by dword,
 // 8-byte ids as two dwords.
@@ -609,8 +651,11 @@ template <int R> struct DenseLds {
 // NARROW: the instantiation for bf16 / fp16 output plans (fcp_narrow.hip); `out_kind` (FCP_OUT_*) is launch-uniform.  Only the
 // output address (2 bytes per element) and the store differ, and both sit behind `if constexpr (NARROW)`: the float32
 // instantiations are the code they were.
-template <int V, int R, bool SHARDED, bool NARROW = false>
-__device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *smem, int out_kind = 0) {
+// TAB16: the instantiation for bf16 / fp16 table plans (fcp_tables16.hip); `tab_kind` (FCP_TAB_*) is launch-uniform.  Only the
+// table address (2 bytes per element) and the load differ, both behind `if constexpr (TAB16)`.  A PASSTHROUGH column's
+// "table" is its float32 payload in the blob and is read as such.
+template <int V, int R, bool SHARDED, bool NARROW = false, bool TAB16 = false>
+__device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *smem, int out_kind = 0, int tab_kind = 0) {
   constexpr int RB = DenseLds<R>::RB, IDS = DenseLds<R>::IDS, BND = DenseLds<R>::BND;
   DenseLds<R> &S = *reinterpret_cast<DenseLds<R> *>(smem);
   LdsCol *s_col = S.col;
@@ -746,6 +791,13 @@ __device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *sm
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     v[r] = vzero<V>();
+    if constexpr (TAB16) {
+      if (FCP_F_FORM(s_col[j].flags) != FCP_FORM_PASSTHROUGH) {
+        const char *tb16 = reinterpret_cast<const char *>(s_col[j].table) + 2 * (int64_t)e; // element offset x 2, in 64 bits
+        if (is_row(off[r])) v[r] = wide ? ld_slot16<V>(tb16, off[r], spr, tab_kind) : ld_slot32_16<V>(tb16, off[r], tab_kind);
+        continue;
+      }
+    }
     if (is_row(off[r])) v[r] = wide ? ld_slot<V>(tb, off[r], spr) : ld_slot32<V>(tb, off[r]);
   }
 #pragma unroll
@@ -878,47 +930,63 @@ template <int V> __device__ __forceinline__ VF<V> ld_slot_or_zero(const float *t
   return r;
 }
 
+// (16-bit tables: `tb` is a byte address; the zero line serves both widths — 2 * V of its zero bytes widen to +0.0)
+template <int V>
+__device__ __forceinline__ VF<V> ld_slot_or_zero16(const char *tb, const float *zeros, uint32_t off, uint32_t spr, int tab_kind) {
+  typedef typename NarrowType<V>::T T;
+  const FCP_GLOBAL T *g = is_row(off) ? as_global(reinterpret_cast<const T *>(tb)) + (uint64_t)off * spr : as_global(reinterpret_cast<const T *>(zeros));
+  return widen16<V>(*g, tab_kind);
+}
+
 // The walk of one bag slice for one output slot: the n table slot offsets staged at s[0..n) are added to `acc`
 // in id order (sequential fp32 adds: the order of the oracle; TF-CPU's up to 9 ids per bag), kWalk table reads in flight
 // per lane.  EVERY lane issues its first kWalk reads at once, whatever its bag length; further batches
 // only while some bag of the wave goes on.  (Round 2 walked "8, then 4" behind per-lane conditions: lanes with
 // up to 4 ids sat out the first pass and issued their reads only after it.)
-template <int V, int N>
-__device__ __forceinline__ void bag_walk_batch(const float *tb, const float *zeros, uint32_t spr, const uint32_t *s, int base, int n, VF<V> &acc) {
+// TAB16 (16-bit tables): `tb` carries the lane's base as a byte address, the reads are the 16-bit loader's.
+template <int V, int N, bool TAB16 = false>
+__device__ __forceinline__ void bag_walk_batch(const float *tb, const float *zeros, uint32_t spr, const uint32_t *s, int base, int n, VF<V> &acc,
+                                               int tab_kind = 0) {
   uint32_t off[N];
   VF<V> w[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) off[k] = base + k < n ? s[base + k] : kNoRow;
 #pragma unroll
-  for (int k = 0; k < N; ++k) w[k] = ld_slot_or_zero<V>(tb, zeros, off[k], spr);
+  for (int k = 0; k < N; ++k) {
+    if constexpr (TAB16)
+      w[k] = ld_slot_or_zero16<V>(reinterpret_cast<const char *>(tb), zeros, off[k], spr, tab_kind);
+    else
+      w[k] = ld_slot_or_zero<V>(tb, zeros, off[k], spr);
+  }
 #pragma unroll
   for (int k = 0; k < N; ++k)
 #pragma unroll
     for (int t = 0; t < V; ++t) acc.v[t] = acc.v[t] + w[k].v[t]; // id order
 }
 
-template <int V, int WALK>
-__device__ __forceinline__ void bag_walk_sum(const float *tb, const float *zeros, uint32_t spr, const uint32_t *s, int n, VF<V> &acc) {
+template <int V, int WALK, bool TAB16 = false>
+__device__ __forceinline__ void bag_walk_sum(const float *tb, const float *zeros, uint32_t spr, const uint32_t *s, int n, VF<V> &acc,
+                                             int tab_kind = 0) {
   // The first batch is as wide as the wave's longest bag needs, up to kWalkFirst reads per lane: every bag of
   // the wave in ONE round of reads whenever none is longer than that (BASELINE's RAGGED and the reference's models
   // E / F draw 0..10 / 1..10 ids per row: with 8-wide batches nearly every wave ran a second round for its one or two
   // 9- and 10-id bags; RAGGED 30.2 -> 28.9 us, profiles/r03_ragged_walk_width_ab.txt).  Wave-uniform choices.
   int base = WALK;
   if (WALK >= 8 && !__any(n > 4)) {
-    bag_walk_batch<V, 4>(tb, zeros, spr, s, 0, n, acc);
+    bag_walk_batch<V, 4, TAB16>(tb, zeros, spr, s, 0, n, acc, tab_kind);
     return;
   } else if (WALK >= 8 && kWalkFirst > WALK && __any(n > WALK)) {
-    bag_walk_batch<V, kWalkFirst>(tb, zeros, spr, s, 0, n, acc);
+    bag_walk_batch<V, kWalkFirst, TAB16>(tb, zeros, spr, s, 0, n, acc, tab_kind);
     base = kWalkFirst;
   } else {
-    bag_walk_batch<V, WALK>(tb, zeros, spr, s, 0, n, acc);
+    bag_walk_batch<V, WALK, TAB16>(tb, zeros, spr, s, 0, n, acc, tab_kind);
   }
   for (; __any(n > base);) { // wave-uniform trip count
     if (WALK > 4 && !__any(n > base + 4)) { // a short tail (bags of 9..12 ids): half a batch
-      bag_walk_batch<V, 4>(tb, zeros, spr, s, base, n, acc);
+      bag_walk_batch<V, 4, TAB16>(tb, zeros, spr, s, base, n, acc, tab_kind);
       base += 4;
     } else {
-      bag_walk_batch<V, WALK>(tb, zeros, spr, s, base, n, acc);
+      bag_walk_batch<V, WALK, TAB16>(tb, zeros, spr, s, base, n, acc, tab_kind);
       base += WALK;
     }
   }
@@ -997,8 +1065,12 @@ struct RaggedLds {
 // (concat order) the byte offset of its float32 weights in the blob, or -1.  Everything it adds sits behind
 // `if constexpr (WEIGHTED)`: the unweighted instantiations are the code they were.
 // NARROW: as in the dense body — bf16 / fp16 output plans (fcp_narrow.hip), everything behind `if constexpr (NARROW)`.
-template <int V, bool SHARDED, bool WEIGHTED = false, bool NARROW = false>
-__device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *smem, const int64_t *wts = nullptr, int out_kind = 0) {
+// TAB16: as in the dense body — bf16 / fp16 table plans (fcp_tables16.hip), everything behind `if constexpr (TAB16)`; never
+// together with WEIGHTED (such plans are refused when they are created).
+template <int V, bool SHARDED, bool WEIGHTED = false, bool NARROW = false, bool TAB16 = false>
+__device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *smem, const int64_t *wts = nullptr, int out_kind = 0,
+                                            int tab_kind = 0) {
+  static_assert(!(TAB16 && WEIGHTED), "the weighted walk reads float32 tables");
   constexpr int RB = RaggedLds::RB, CAPW = RaggedLds::CAPW;
   RaggedLds &S = *reinterpret_cast<RaggedLds *>(smem);
   LdsCol *s_col = S.col;
@@ -1146,6 +1218,8 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
     constexpr int WALK = decltype(walk_width)::value;
     const unsigned form = FCP_F_FORM(s_col[j].flags);
     const float *tb = s_col[j].table + (q * V - s_col[j].out_off);
+    if constexpr (TAB16) // the same element as a byte address: element offset x 2, in 64 bits
+      tb = reinterpret_cast<const float *>(reinterpret_cast<const char *>(s_col[j].table) + 2 * (int64_t)(q * V - s_col[j].out_off));
     const uint32_t spr = (uint32_t)(s_col[j].dim / V); // slots per table row
     if (form == FCP_FORM_SEGMENT_REDUCE) {
       if ((s_col[j].xform & 3u) == FCP_XFORM_FILTER && (FCP_F_COMBINER(s_col[j].flags) == FCP_COMBINER_MEAN ||
@@ -1163,6 +1237,8 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
         } else { // (no wider than kWalkLong: next to the weight pointer and the denominator a 10-wide batch spills at V = 4)
           bag_walk_sum<V, (WALK < kWalkLong ? WALK : kWalkLong)>(tb, H.zeros, spr, s, n, acc);
         }
+      } else if constexpr (TAB16) {
+        bag_walk_sum<V, WALK, true>(tb, H.zeros, spr, s, n, acc, tab_kind);
       } else {
         bag_walk_sum<V, WALK>(tb, H.zeros, spr, s, n, acc);
       }
@@ -1174,7 +1250,11 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
       const uint32_t off = s[k];
       if (off != kFiltered) {
         acc = vzero<V>();
-        if (is_row(off)) acc = ld_slot<V>(tb, off, spr);
+        if constexpr (TAB16) {
+          if (is_row(off)) acc = ld_slot16<V>(reinterpret_cast<const char *>(tb), off, spr, tab_kind);
+        } else {
+          if (is_row(off)) acc = ld_slot<V>(tb, off, spr);
+        }
         // the winner of a ScatterNd row is out of the vocabulary: counted once, by the lane of the column's first slot
         if (form == FCP_FORM_GATHER_SCATTER && off == kBadRow && H.bad_ids && q * V == s_col[j].out_off) atomicAdd(H.bad_ids, 1ull);
       }

@@ -284,6 +284,9 @@ struct fcp_plan {
   // narrow output (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16): the element type (FCP_OUT_*) and its size in bytes — every byte
   // quantity of the output region (group sizes, column bases, the position of the CSR scratch) is formed with out_elem
   int out_kind = FCP_OUT_F32, out_elem = 4;
+  // 16-bit tables (FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16): the element type (FCP_TAB_*) of every table and its size in
+  // bytes.  Geometry, slot offsets and wide_rows are in elements and do not depend on it; fcp_plan_table_bytes does
+  int tab_kind = FCP_TAB_F32, tab_elem = 4;
   std::vector<FcpColStatic> h_cols;
   char *d_const = nullptr;
   int32_t *d_seg_cols = nullptr;

@@ -188,6 +188,11 @@ int fcp_launch_weighted(const FcpLaunch &L, const int64_t *wts, int vec, int gri
 int fcp_launch_narrow(const FcpLaunch &L, int vec, bool dense_kernel, int out_kind, int grid_blocks, ihipStream_t *s);
 int fcp_launch_narrow_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch &Lragged, int ragged_blocks, int vec,
                              int out_kind, ihipStream_t *s);
+// (fcp_tables16.hip) the dense / ragged / hybrid bodies for plans with bf16 / fp16 tables (unsharded, float32 output);
+// tab_kind: FCP_TAB_BF16 | FCP_TAB_F16; geometry, LDS and grids as fcp_launch_fused / fcp_launch_hybrid
+int fcp_launch_tab16(const FcpLaunch &L, int vec, bool dense_kernel, int tab_kind, int grid_blocks, ihipStream_t *s);
+int fcp_launch_tab16_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch &Lragged, int ragged_blocks, int vec,
+                            int tab_kind, ihipStream_t *s);
 // (fcp_dense_plain.hip) the small dense kernel of plain dense plans: V 4, R 4, the grid of fcp_launch_fused's dense kernel
 int fcp_launch_dense_plain(const FcpPlainLaunch &P, int grid_blocks, ihipStream_t *s);
 // what the next fused launch of this thread would carry (stop event, any-order flag): taken and cleared

@@ -192,6 +192,27 @@ int validate_narrow(const fcp_plan_desc_t *d, const fcp_column_ext_t *ext) {
   return FCP_OK;
 }
 
+// 16-bit tables (FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16): what the kernels of fcp_tables16.hip do not serve is refused
+// here, by name, for device and host-only plans alike.
+int validate_tables16(const fcp_plan_desc_t *d, const fcp_column_ext_t *ext) {
+  const uint32_t tab = d->flags & (FCP_FLAG_TABLES_BF16 | FCP_FLAG_TABLES_F16);
+  if (!tab) return FCP_OK;
+  if (tab == (FCP_FLAG_TABLES_BF16 | FCP_FLAG_TABLES_F16))
+    return fail(FCP_ERR_INVALID_ARGUMENT, "FCP_FLAG_TABLES_BF16 and FCP_FLAG_TABLES_F16 exclude each other");
+  if (d->flags & (FCP_FLAG_OUT_BF16 | FCP_FLAG_OUT_F16))
+    return fail(FCP_ERR_UNSUPPORTED, "16-bit tables with narrow output (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16): the 16-bit-table kernels store float32");
+  if (d->shard_world > 1)
+    return fail(FCP_ERR_UNSUPPORTED, "16-bit tables on a row-sharded plan (shard_world > 1): the sharded kernels read float32 tables");
+  for (int k = 0; k < d->n_columns; ++k) {
+    const std::string where = "column " + std::to_string(k) + ": ";
+    if (ext && ext[k].weights_input1 > 0)
+      return fail(FCP_ERR_UNSUPPORTED, where + "16-bit tables with per-id weights: weighted plans take the float32 weighted kernel");
+    if (d->columns[k].combiner == FCP_COMBINER_SQRTN && d->columns[k].form == FCP_FORM_SEGMENT_REDUCE)
+      return fail(FCP_ERR_UNSUPPORTED, where + "16-bit tables with FCP_COMBINER_SQRTN: sqrtn plans take the float32 weighted kernel");
+  }
+  return FCP_OK;
+}
+
 // Run-time shapes -> per-column dynamic records, arena layout and launch
 // geometry.  Mirrors what the generated host code evaluates per call from
 // SymEngine expressions (cuda_emitter.cc:2151-2179, :2410-2455).
@@ -613,7 +634,7 @@ void build_plain_template(fcp_plan *p) {
   // FCP_DIAG=dense_generic: a qualifying plan stays on the generic kernel (the tests' seam)
   if (fcp::diag_ll("dense_generic", 0) != 0) return;
   const fcp_plan_desc_t &d = p->desc;
-  if (p->out_elem != 4 || d.layout != FCP_LAYOUT_CONCAT || d.n_groups != 1 || d.shard_world > 1 || p->vec != 4 || p->wide_rows ||
+  if (p->out_elem != 4 || p->tab_elem != 4 || d.layout != FCP_LAYOUT_CONCAT || d.n_groups != 1 || d.shard_world > 1 || p->vec != 4 || p->wide_rows ||
       p->weighted_kernel || !p->dense_only || p->cols.empty())
     return;
   const int nc = (int)p->cols.size();
@@ -909,11 +930,16 @@ int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext,
   if (rc) return rc;
   if (ext && (rc = validate_ext(desc, ext))) return rc;
   if ((rc = validate_narrow(desc, ext))) return rc;
+  if ((rc = validate_tables16(desc, ext))) return rc;
   fcp_plan *p = new (std::nothrow) fcp_plan();
   if (!p) return fail(FCP_ERR_ALLOC, "out of host memory");
   if (desc->flags & (FCP_FLAG_OUT_BF16 | FCP_FLAG_OUT_F16)) {
     p->out_kind = (desc->flags & FCP_FLAG_OUT_BF16) ? FCP_OUT_BF16 : FCP_OUT_F16;
     p->out_elem = 2;
+  }
+  if (desc->flags & (FCP_FLAG_TABLES_BF16 | FCP_FLAG_TABLES_F16)) {
+    p->tab_kind = (desc->flags & FCP_FLAG_TABLES_BF16) ? FCP_TAB_BF16 : FCP_TAB_F16;
+    p->tab_elem = 2;
   }
   p->env = fcp::read_env(); // the library's shipping switches, read here and nowhere on the request path (fcp_env.h)
   p->desc = *desc;
@@ -1110,6 +1136,7 @@ struct ParsedPlanFile {
   int32_t stage_symbols_input = -1;
   bool has_stage = false;
   int out_kind = FCP_OUT_F32; // the "out_dtype" line (version 6)
+  int tab_kind = FCP_TAB_F32; // the "table_dtype" line (version 7)
 };
 
 int parse_plan_file(const char *path, ParsedPlanFile &P) {
@@ -1124,9 +1151,13 @@ int parse_plan_file(const char *path, ParsedPlanFile &P) {
   int version = 0, n_host = 0, n_cols = 0;
   fcp_plan_desc_t &d = P.d;
   std::memset(&d, 0, sizeof(d));
-  if (std::fscanf(f, "%31s %d", tag, &version) != 2 || std::strcmp(tag, "fcp_plan") || version < 1 || version > 6)
+  if (std::fscanf(f, "%31s %d", tag, &version) != 2 || std::strcmp(tag, "fcp_plan") || version < 1 || version > 7)
     return fail(FCP_ERR_INVALID_ARGUMENT, where + "bad header");
-  if (version >= 6) { // narrow-output plans: "out_dtype bf16|f16", here and nowhere else (anywhere else it is no 'layout' / section)
+  if (version >= 7) { // plans with 16-bit tables: "table_dtype bf16|f16", under the rules of version 6's line, which they never carry
+    if (std::fscanf(f, "%31s %31s", tag, t2) != 2 || std::strcmp(tag, "table_dtype") || (std::strcmp(t2, "bf16") && std::strcmp(t2, "f16")))
+      return fail(FCP_ERR_INVALID_ARGUMENT, where + "expected 'table_dtype bf16' or 'table_dtype f16'");
+    P.tab_kind = !std::strcmp(t2, "bf16") ? FCP_TAB_BF16 : FCP_TAB_F16;
+  } else if (version >= 6) { // narrow-output plans: "out_dtype bf16|f16", here and nowhere else (anywhere else it is no 'layout' / section)
     if (std::fscanf(f, "%31s %31s", tag, t2) != 2 || std::strcmp(tag, "out_dtype") || (std::strcmp(t2, "bf16") && std::strcmp(t2, "f16")))
       return fail(FCP_ERR_INVALID_ARGUMENT, where + "expected 'out_dtype bf16' or 'out_dtype f16'");
     P.out_kind = !std::strcmp(t2, "bf16") ? FCP_OUT_BF16 : FCP_OUT_F16;
@@ -1268,6 +1299,12 @@ int fcp_plan_create_from_file(const char *path, int32_t device, uint32_t flags, 
       return fail(FCP_ERR_INVALID_ARGUMENT, std::string("column plan ") + path + ": flags ask for another output dtype than the file's out_dtype line");
     P.d.flags |= file_bit;
   }
+  if (P.tab_kind != FCP_TAB_F32) { // likewise for the table dtype
+    const uint32_t file_bit = P.tab_kind == FCP_TAB_BF16 ? FCP_FLAG_TABLES_BF16 : FCP_FLAG_TABLES_F16;
+    if (flags & (FCP_FLAG_TABLES_BF16 | FCP_FLAG_TABLES_F16) & ~file_bit)
+      return fail(FCP_ERR_INVALID_ARGUMENT, std::string("column plan ") + path + ": flags ask for another table dtype than the file's table_dtype line");
+    P.d.flags |= file_bit;
+  }
   return fcp_plan_create_ex(&P.d, P.ext.empty() ? nullptr : P.ext.data(), out);
 }
 
@@ -1316,6 +1353,12 @@ int fcp_plan_out_dtype(const fcp_plan_t *p, int32_t *out) {
   return FCP_OK;
 }
 
+int fcp_plan_table_dtype(const fcp_plan_t *p, int32_t *out) {
+  if (!p || !out) return fail(FCP_ERR_INVALID_ARGUMENT, "null argument");
+  *out = p->tab_kind;
+  return FCP_OK;
+}
+
 int fcp_plan_table_bytes(const fcp_plan_t *p, int64_t *shard_bytes, int64_t *max_table_bytes_unsharded) {
   if (!p) return fail(FCP_ERR_INVALID_ARGUMENT, "null plan");
   // a table input may feed several columns (shared embeddings): count each once
@@ -1325,8 +1368,8 @@ int fcp_plan_table_bytes(const fcp_plan_t *p, int64_t *shard_bytes, int64_t *max
     if (f != FCP_FORM_GATHER && f != FCP_FORM_SEGMENT_REDUCE && f != FCP_FORM_GATHER_SCATTER) continue;
     const int64_t local_vocab =
         (hc.d.vocab - p->desc.shard_rank + p->desc.shard_world - 1) / p->desc.shard_world;
-    local[hc.d.table_input] = std::max(local[hc.d.table_input], local_vocab * hc.d.dim * 4);
-    whole[hc.d.table_input] = std::max(whole[hc.d.table_input], hc.d.vocab * hc.d.dim * 4);
+    local[hc.d.table_input] = std::max(local[hc.d.table_input], local_vocab * hc.d.dim * p->tab_elem);
+    whole[hc.d.table_input] = std::max(whole[hc.d.table_input], hc.d.vocab * hc.d.dim * p->tab_elem);
   }
   int64_t sum = 0, mx = 0;
   for (int t = 0; t < p->desc.n_device_inputs; ++t) {

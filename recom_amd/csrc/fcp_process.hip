@@ -347,6 +347,7 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
     const int32_t fused = (int32_t)(m.geo[0].grid_blocks > 0) | (int32_t)(m.geo[1].grid_blocks > 0) << 1;
     ll.kernel.store(p->weighted_kernel ? (m.geo[1].grid_blocks > 0 ? FCP_LAUNCH_RAGGED_WEIGHTED : FCP_LAUNCH_NONE)
                     : (p->out_elem == 2 && fused) ? fused + (FCP_LAUNCH_DENSE_NARROW - FCP_LAUNCH_DENSE) // narrow plans: fcp_narrow.hip
+                    : (p->tab_elem == 2 && fused) ? fused + (FCP_LAUNCH_DENSE_TAB16 - FCP_LAUNCH_DENSE)  // 16-bit tables: fcp_tables16.hip
                                                   : fused,
                     std::memory_order_relaxed);
     p->last_dense_front.store(m.geo[0].grid_blocks <= 0 || p->weighted_kernel ? FCP_DENSE_FRONT_NONE
@@ -422,6 +423,19 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
       e = fcp_launch_narrow(L, p->vec, true, p->out_kind, m.geo[0].grid_blocks, stream);
     }
     if (e) return hip_fail("narrow-output kernel launch", (hipError_t)e);
+  } else if (p->tab_elem == 2) { // bf16 / fp16 tables: the same three dispatches in their 16-bit-table instantiations
+    int e = 0;
+    if (m.geo[1].grid_blocks > 0 && m.geo[0].grid_blocks > 0) {
+      FcpLaunch Ld;
+      fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &Ld);
+      e = fcp_launch_tab16_hybrid(Ld, m.geo[0].grid_blocks, L, m.geo[1].grid_blocks, p->vec, p->tab_kind, stream);
+    } else if (m.geo[1].grid_blocks > 0) {
+      e = fcp_launch_tab16(L, p->vec, false, p->tab_kind, m.geo[1].grid_blocks, stream);
+    } else if (m.geo[0].grid_blocks > 0) {
+      fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &L);
+      e = fcp_launch_tab16(L, p->vec, true, p->tab_kind, m.geo[0].grid_blocks, stream);
+    }
+    if (e) return hip_fail("16-bit-table kernel launch", (hipError_t)e);
   } else if (m.geo[1].grid_blocks > 0 && m.geo[0].grid_blocks > 0) {
     FcpLaunch Ld;
     fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &Ld);

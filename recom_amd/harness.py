@@ -165,6 +165,8 @@ class ServingHarness:
         dense, pooled = dense[::step][:max_columns], pooled[::max(1, len(pooled) // 8)][:8]
         # a narrow-output plan: the same closed forms, rounded once to the plan's element type (still an exact comparison)
         nd = {"f32": None, "bf16": torch.bfloat16, "f16": torch.float16}[spec.out_dtype]
+        # 16-bit tables: the closed form rounded once to the table dtype is what the table holds (exact from there on)
+        hash_rows = lambda seed, rows, dim: synth.round_to_table(synth.hash_rows(seed, rows, dim), spec.table_dtype)  # noqa: E731
 
         def fl(x):
             return x if nd is None else torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(nd).float().numpy()
@@ -188,7 +190,7 @@ class ServingHarness:
                     seed = self.model.tables[c.table_input].seed
                     valid = (ids >= 0) & (ids < c.vocab)
                     if c.form == FORM_GATHER:
-                        want = np.where(valid[:, None], synth.hash_rows(seed, np.where(valid, ids, 0), c.dim), np.float32(0))
+                        want = np.where(valid[:, None], hash_rows(seed, np.where(valid, ids, 0), c.dim), np.float32(0))
                         ok = np.array_equal(got, fl(want))
                     else:
                         seg = np.asarray(r.inputs[c.seg_input])
@@ -202,7 +204,7 @@ class ServingHarness:
                             acc = np.zeros(c.dim, np.float32)
                             sel = ids[csr[b_]:csr[b_ + 1]]
                             for v in sel[(sel >= 0) & (sel < c.vocab)]:
-                                acc = acc + synth.hash_rows(seed, np.asarray([v]), c.dim)[0]        # fp32, id order
+                                acc = acc + hash_rows(seed, np.asarray([v]), c.dim)[0]        # fp32, id order
                             if c.combiner == COMBINER_MEAN and sel.size:
                                 acc = acc / np.float32(sel.size)
                             ok = ok and np.array_equal(got[b_], fl(acc))
@@ -214,7 +216,7 @@ class ServingHarness:
 
     def algorithmic_bytes(self) -> dict:
         """Mean algorithmic bytes per request over the resident requests; a narrow-output plan is charged
-        2 bytes per written element (``PlanSpec.algorithmic_bytes``)."""
+        2 bytes per written element (``PlanSpec.algorithmic_bytes``), a plan with 16-bit tables 2 bytes per table element read."""
         acc = None
         for (blob, offsets, shapes), r in zip(self.packed, self.requests):
             b = self.spec.algorithmic_bytes(shapes, r.symbols)

@@ -26,9 +26,14 @@ FLAG_OUT_BF16 = 1 << 1    # narrow output: the concat groups as bf16 / fp16 (at 
 FLAG_OUT_F16 = 1 << 2
 OUT_DTYPES = {0: "f32", 1: "bf16", 2: "f16"}   # FCP_OUT_* (fcp_plan_out_dtype)
 OUT_DTYPE_FLAGS = {"f32": 0, "bf16": FLAG_OUT_BF16, "f16": FLAG_OUT_F16}
+FLAG_TABLES_BF16 = 1 << 3  # 16-bit tables: every embedding table of the plan as bf16 / fp16 (at most one of the two)
+FLAG_TABLES_F16 = 1 << 4
+TABLE_DTYPES = {0: "f32", 1: "bf16", 2: "f16"}   # FCP_TAB_* (fcp_plan_table_dtype)
+TABLE_DTYPE_FLAGS = {"f32": 0, "bf16": FLAG_TABLES_BF16, "f16": FLAG_TABLES_F16}
 # fcp_launch_info_t (fcp_plan_last_launch): names of the kernel, store-policy and segment-offset codes
 LAUNCH_KERNELS = {0: "none", 1: "dense", 2: "ragged", 3: "hybrid", 4: "ragged_weighted",
-                  5: "dense_narrow", 6: "ragged_narrow", 7: "hybrid_narrow"}
+                  5: "dense_narrow", 6: "ragged_narrow", 7: "hybrid_narrow",
+                  8: "dense_tab16", 9: "ragged_tab16", 10: "hybrid_tab16"}
 DENSE_FRONTS = {0: "none", 1: "generic", 2: "plain"}   # fcp_plan_last_dense_front
 LAUNCH_STORES = {0: "nt", 1: "sc1_nt", 4: "plain"}
 LAUNCH_SEGMENT_OFFSETS = {0: "none", 1: "prepass", 2: "search"}
@@ -153,7 +158,7 @@ EXPORTS = [
     "fcp_plan_set_private_streams", "fcp_result_wait", "fcp_result_synchronize", "fcp_plan_set_request_order",
     "fcp_plan_probe_private_streams", "fcp_plan_private_streams_verdict", "fcp_plan_verify_private_streams",
     "fcp_plan_private_streams_stats", "fcp_plan_last_launch", "fcp_plan_last_csr", "fcp_aux_launch_counts",
-    "fcp_plan_out_dtype", "fcp_plan_last_dense_front",
+    "fcp_plan_out_dtype", "fcp_plan_last_dense_front", "fcp_plan_table_dtype",
 ]
 
 _lib = None
@@ -222,6 +227,7 @@ def load() -> C.CDLL:
     L.fcp_plan_output_columns.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_int32]
     L.fcp_plan_table_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.fcp_plan_out_dtype.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    L.fcp_plan_table_dtype.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.fcp_plan_release_captures.argtypes = [C.c_void_p]
     L.fcp_placement_decide.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                        C.POINTER(Placement)]

@@ -24,7 +24,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import lib as _lib
-from .plan import (FORM_BATCH_COL_REDUCTION, FORM_PASSTHROUGH, IDS_F32_BUCKETIZE, LAYOUT_CONCAT, PlanSpec)
+from .plan import (FORM_BATCH_COL_REDUCTION, FORM_GATHER, FORM_GATHER_SCATTER, FORM_PASSTHROUGH, FORM_SEGMENT_REDUCE,
+                   IDS_F32_BUCKETIZE, LAYOUT_CONCAT, PlanSpec)
 
 
 # ----------------------------------------------------------------------------
@@ -197,11 +198,12 @@ class Plan:
         self.handle = handle
 
     @classmethod
-    def from_file(cls, path: str, device: int = 0, host_only: bool = False, out_dtype: Optional[str] = None) -> "Plan":
+    def from_file(cls, path: str, device: int = 0, host_only: bool = False, out_dtype: Optional[str] = None,
+                  table_dtype: Optional[str] = None) -> "Plan":
         """The plan a column-plan file describes, parsed by the library itself
         (``fcp_plan_create_from_file`` — what the TF shim calls with the op's ``dlpath``).  ``out_dtype``: "bf16" / "f16"
         select narrow output for a file that does not name a dtype (the flag bits of the call); a file that names
-        another one is refused."""
+        another one is refused.  ``table_dtype``: the same for 16-bit tables."""
         import dataclasses
         from .plan_io import load_plan
         self = cls.__new__(cls)
@@ -210,12 +212,15 @@ class Plan:
         self._keep = []
         self.handle = None
         handle = C.c_void_p()
-        flags = (_lib.FLAG_HOST_ONLY if host_only else 0) | _lib.OUT_DTYPE_FLAGS[out_dtype or "f32"]
+        flags = (_lib.FLAG_HOST_ONLY if host_only else 0) | _lib.OUT_DTYPE_FLAGS[out_dtype or "f32"] | \
+            _lib.TABLE_DTYPE_FLAGS[table_dtype or "f32"]
         _lib.check(self._L.fcp_plan_create_from_file(path.encode(), device, flags, C.byref(handle)), "fcp_plan_create_from_file")
         self.handle = handle
         self.spec = load_plan(path)          # Python-side bookkeeping only
         if self.out_dtype() != self.spec.out_dtype:
             self.spec = dataclasses.replace(self.spec, out_dtype=self.out_dtype())
+        if self.table_dtype() != self.spec.table_dtype:
+            self.spec = dataclasses.replace(self.spec, table_dtype=self.table_dtype())
         return self
 
     def out_dtype(self) -> str:
@@ -223,6 +228,18 @@ class Plan:
         v = C.c_int32()
         _lib.check(self._L.fcp_plan_out_dtype(self.handle, C.byref(v)), "fcp_plan_out_dtype")
         return _lib.OUT_DTYPES[v.value]
+
+    def table_dtype(self) -> str:
+        """``fcp_plan_table_dtype``: "f32", "bf16" or "f16" — the element type of every embedding table the plan reads."""
+        v = C.c_int32()
+        _lib.check(self._L.fcp_plan_table_dtype(self.handle, C.byref(v)), "fcp_plan_table_dtype")
+        return _lib.TABLE_DTYPES[v.value]
+
+    def table_bytes(self):
+        """``fcp_plan_table_bytes``: (bytes of tables this plan reads on its device, largest table unsharded)."""
+        a, b = C.c_int64(), C.c_int64()
+        _lib.check(self._L.fcp_plan_table_bytes(self.handle, C.byref(a), C.byref(b)), "fcp_plan_table_bytes")
+        return a.value, b.value
 
     def counts(self) -> dict:
         v = [C.c_int32() for _ in range(5)]
@@ -311,7 +328,7 @@ class Plan:
 
     def last_launch(self) -> dict:
         """``fcp_plan_last_launch``: what the plan's most recent request enqueued — kernel (``none`` / ``dense`` /
-        ``ragged`` / ``hybrid`` / ``ragged_weighted`` / ``dense_narrow`` / ``ragged_narrow`` / ``hybrid_narrow``), ``vec``, dense ``rows_per_wave``, ``store`` (``nt`` / ``sc1_nt`` / ``plain``),
+        ``ragged`` / ``hybrid`` / ``ragged_weighted`` / ``dense_narrow`` / ``ragged_narrow`` / ``hybrid_narrow`` / ``dense_tab16`` / ``ragged_tab16`` / ``hybrid_tab16``), ``vec``, dense ``rows_per_wave``, ``store`` (``nt`` / ``sc1_nt`` / ``plain``),
         ``wide_rows``, ``shard_world``, ``dense_blocks`` / ``ragged_blocks``, ``segment_offsets`` (``none`` /
         ``prepass`` / ``search``).  Read-only diagnostics: which kernel instantiation a request reached."""
         li = _lib.LaunchInfo()
@@ -397,6 +414,10 @@ class FeatureColumnProcess:
         self._L = self.plan._L
         # the element type of the outputs as the LIBRARY holds it (a plan file, or flag bits, may have chosen it)
         self.out_dtype = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[self.plan.out_dtype()]
+        # likewise the element type the bound tables must have (a wrong one would be read as garbage, or out of bounds)
+        self.table_dtype = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[self.plan.table_dtype()]
+        self._table_inputs = sorted({c.table_input for c in self.plan.spec.columns
+                                     if c.form in (FORM_GATHER, FORM_SEGMENT_REDUCE, FORM_GATHER_SCATTER)})
 
     @classmethod
     def from_plan_file(cls, dlpath: str, device: int = 0) -> "FeatureColumnProcess":
@@ -441,6 +462,10 @@ class FeatureColumnProcess:
         if cached is not None and cached[0] is inputs and len(inputs) == cached[3]:
             tptrs, tshapes = cached[1], cached[2]  # same table list object as last time (hundreds of tables)
         else:
+            for i in self._table_inputs:
+                if i < len(inputs) and inputs[i].dtype != self.table_dtype:
+                    raise ValueError(f"FeatureColumnProcess: table {i} is {inputs[i].dtype}, the plan reads {self.table_dtype} tables "
+                                     "(PlanSpec.table_dtype)")
             tptrs = (C.c_void_p * max(1, len(inputs)))(*[t.data_ptr() for t in inputs])
             tshapes = np.asarray([d for t in inputs for d in t.shape], np.int32)
             self._tab_cache = (inputs, tptrs, tshapes, len(inputs))

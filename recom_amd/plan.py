@@ -34,10 +34,15 @@ XFORM_NONE, XFORM_SELECT, XFORM_FILTER = 0, 1, 2   # id transforms (SelectValue 
 LAYOUT_CONCAT, LAYOUT_PER_COLUMN = 0, 1
 FLAG_COUNT_BAD_IDS = 1
 FLAG_OUT_BF16, FLAG_OUT_F16 = 1 << 1, 1 << 2   # narrow output (PlanSpec.out_dtype sets the bit)
+FLAG_TABLES_BF16, FLAG_TABLES_F16 = 1 << 3, 1 << 4   # 16-bit tables (PlanSpec.table_dtype sets the bit)
 
 
 class NarrowOutputUnsupported(ValueError):
     """A plan kind the narrow-output kernels do not serve (the library answers FCP_ERR_UNSUPPORTED)."""
+
+
+class Tables16Unsupported(ValueError):
+    """A plan kind the 16-bit-table kernels do not serve (the library answers FCP_ERR_UNSUPPORTED)."""
 
 _ID_ELEM_SIZE = {IDS_I32: 4, IDS_I64: 8, IDS_F32_BUCKETIZE: 4}
 _ID_NP_DTYPE = {IDS_I32: np.int32, IDS_I64: np.int64, IDS_F32_BUCKETIZE: np.float32}
@@ -168,6 +173,9 @@ class PlanSpec:
     # element type of the concat groups: "f32", or — narrow output, FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16 — "bf16" / "f16":
     # every element is the float32 value rounded once, to nearest-even, at the store
     out_dtype: str = "f32"
+    # element type of EVERY embedding table of the plan: "f32", or — FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16 — "bf16" /
+    # "f16": a 16-bit element widens to float32 exactly, the plan computes what the float32 plan computes on the widened tables
+    table_dtype: str = "f32"
 
     # ---- static layout facts ------------------------------------------------
     def validate(self) -> None:
@@ -192,10 +200,12 @@ class PlanSpec:
             if c.rows_source == ROWS_FROM_SYMBOL and not 0 <= c.rows_arg < self.n_symbols:
                 raise ValueError(f"column {k}: symbol index out of range")
         self.validate_out_dtype()
+        self.validate_table_dtype()
 
     def plan_flags(self) -> int:
         """``fcp_plan_desc_t::flags``: ``flags`` plus the bit ``out_dtype`` stands for."""
-        return self.flags | {"f32": 0, "bf16": FLAG_OUT_BF16, "f16": FLAG_OUT_F16}.get(self.out_dtype, 0)
+        return (self.flags | {"f32": 0, "bf16": FLAG_OUT_BF16, "f16": FLAG_OUT_F16}.get(self.out_dtype, 0)
+                | {"f32": 0, "bf16": FLAG_TABLES_BF16, "f16": FLAG_TABLES_F16}.get(self.table_dtype, 0))
 
     @property
     def out_elem_size(self) -> int:
@@ -226,6 +236,34 @@ class PlanSpec:
 
     def with_out_dtype(self, out_dtype: str) -> "PlanSpec":
         return dataclasses.replace(self, out_dtype=out_dtype)
+
+    @property
+    def table_elem_size(self) -> int:
+        return 4 if self.table_dtype == "f32" else 2
+
+    def validate_table_dtype(self) -> None:
+        """The library's rules for 16-bit tables (``fcp_plan_create``): one dtype, and none of the three plan kinds the
+        16-bit-table kernels do not serve.  ``Tables16Unsupported`` mirrors FCP_ERR_UNSUPPORTED, ValueError
+        FCP_ERR_INVALID_ARGUMENT."""
+        if self.table_dtype not in ("f32", "bf16", "f16"):
+            raise ValueError(f"table_dtype must be 'f32', 'bf16' or 'f16', not {self.table_dtype!r}")
+        f = self.plan_flags()
+        if not f & (FLAG_TABLES_BF16 | FLAG_TABLES_F16):
+            return
+        if f & FLAG_TABLES_BF16 and f & FLAG_TABLES_F16:
+            raise ValueError("FCP_FLAG_TABLES_BF16 and FCP_FLAG_TABLES_F16 exclude each other")
+        if f & (FLAG_OUT_BF16 | FLAG_OUT_F16):
+            raise Tables16Unsupported("16-bit tables with narrow output (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16): the 16-bit-table kernels store float32")
+        if self.shard_world > 1:
+            raise Tables16Unsupported("16-bit tables on a row-sharded plan (shard_world > 1): the sharded kernels read float32 tables")
+        for k, c in enumerate(self.columns):
+            if c.weights_input >= 0:
+                raise Tables16Unsupported(f"column {k}: 16-bit tables with per-id weights: weighted plans take the float32 weighted kernel")
+            if c.combiner == COMBINER_SQRTN and c.form == FORM_SEGMENT_REDUCE:
+                raise Tables16Unsupported(f"column {k}: 16-bit tables with FCP_COMBINER_SQRTN: sqrtn plans take the float32 weighted kernel")
+
+    def with_table_dtype(self, table_dtype: str) -> "PlanSpec":
+        return dataclasses.replace(self, table_dtype=table_dtype)
 
     @property
     def n_columns(self) -> int:
@@ -267,6 +305,8 @@ class PlanSpec:
         d = dataclasses.asdict(self)
         if self.out_dtype == "f32":        # the float32 plan's dict is what it always was (the oracle sees no new key)
             del d["out_dtype"]
+        if self.table_dtype == "f32":      # likewise
+            del d["table_dtype"]
         for c, src in zip(d["columns"], self.columns):
             c["boundaries"] = None if src.boundaries is None else np.asarray(src.boundaries, np.float32)
             c["xform_lo"] = [int(v) for v in src.xform_lo]
@@ -403,7 +443,8 @@ class PlanSpec:
     def algorithmic_bytes(self, shapes: Sequence[int], symbols: Optional[Sequence[int]] = None) -> dict:
         """Algorithmic bytes of one request: table rows read + ids read + CSR
         offsets / segment ids read + bucketize boundaries + pooled output written
-        once in concat layout, 2 bytes per element in a narrow-output plan (+ 4 bytes per id of a weighted column: key ``weights``, present only in plans that have
+        once in concat layout, 2 bytes per element in a narrow-output plan; a table row read is charged ``dim * 2`` bytes in a plan
+        with 16-bit tables (+ 4 bytes per id of a weighted column: key ``weights``, present only in plans that have
         one).  No intermediate traffic is counted."""
         so = self.shape_offsets()
 
@@ -425,7 +466,7 @@ class PlanSpec:
                 rows_b += numel(c.ids_input) * 4
             else:
                 nnz = numel(c.ids_input)
-                rows_b += nnz * c.dim * 4
+                rows_b += nnz * c.dim * self.table_elem_size
                 ids_b += nnz * _ID_ELEM_SIZE[c.id_source]
                 if c.seg_kind == SEG_CSR_I32:
                     seg_b += (rows + 1) * 4

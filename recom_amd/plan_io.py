@@ -20,7 +20,9 @@ def save_plan(spec: PlanSpec, path: str, stage: "StageInfo | None" = None) -> No
         maps = [(k, c) for k, c in enumerate(spec.columns) if len(c.seg_mul)]
         weights = [(k, c) for k, c in enumerate(spec.columns) if c.weights_input >= 0]
         v5 = bool(weights) or any(c.combiner == COMBINER_SQRTN for c in spec.columns)
-        if spec.out_dtype != "f32":   # version 6, narrow-output plans only: the dtype is the file's second line
+        if spec.table_dtype != "f32":   # version 7, plans with 16-bit tables only (never narrow output as well): likewise
+            f.write(f"fcp_plan 7\ntable_dtype {spec.table_dtype}\n")
+        elif spec.out_dtype != "f32":   # version 6, narrow-output plans only: the dtype is the file's second line
             f.write(f"fcp_plan 6\nout_dtype {spec.out_dtype}\n")
         else:
             f.write(f"fcp_plan {5 if v5 else 4 if maps else 3 if stage is not None else 2}\n")
@@ -68,10 +70,16 @@ def load_plan(path: str) -> PlanSpec:
     if nxt() != "fcp_plan":
         raise ValueError("bad plan header")
     version = int(nxt())
-    if version not in (1, 2, 3, 4, 5, 6):
+    if version not in (1, 2, 3, 4, 5, 6, 7):
         raise ValueError("bad plan header")
-    out_dtype = "f32"
-    if version >= 6:              # "out_dtype bf16|f16": here and nowhere else, in version 6 files and no others
+    out_dtype = table_dtype = "f32"
+    if version >= 7:              # "table_dtype bf16|f16": the same place and rules, in version 7 files and no others
+        if nxt() != "table_dtype":
+            raise ValueError(f"expected 'table_dtype bf16' or 'table_dtype f16' in {path}")
+        table_dtype = nxt()
+        if table_dtype not in ("bf16", "f16"):
+            raise ValueError(f"unknown table_dtype {table_dtype!r} in {path}")
+    elif version >= 6:            # "out_dtype bf16|f16": here and nowhere else, in version 6 files and no others
         if nxt() != "out_dtype":
             raise ValueError(f"expected 'out_dtype bf16' or 'out_dtype f16' in {path}")
         out_dtype = nxt()
@@ -127,9 +135,12 @@ def load_plan(path: str) -> PlanSpec:
             v = [int(x) for x in rest[2 + 9 * j: 11 + 9 * j]]
             cols[v[0]] = dataclasses.replace(cols[v[0]], seg_mul=tuple(v[4:4 + v[1]]), seg_div=v[8], seg_sym=v[2],
                                              seg_sym_slot=v[3])
-    if tok.count("out_dtype") != (1 if version >= 6 else 0):   # anywhere but the second line, twice, or in an older file
+    if tok.count("table_dtype") != (1 if version >= 7 else 0):
+        raise ValueError(f"misplaced or repeated table_dtype line in {path}")
+    if tok.count("out_dtype") != (1 if version == 6 else 0):   # anywhere but the second line, twice, or in an older file
         raise ValueError(f"misplaced or repeated out_dtype line in {path}")
-    spec = PlanSpec(cols, ranks, esz, n_dev, n_groups=n_groups, n_symbols=n_symbols, layout=layout, out_dtype=out_dtype)
+    spec = PlanSpec(cols, ranks, esz, n_dev, n_groups=n_groups, n_symbols=n_symbols, layout=layout, out_dtype=out_dtype,
+                    table_dtype=table_dtype)
     spec.validate()
     return spec
 

@@ -84,6 +84,32 @@ def hash_table_torch(seed: int, vocab: int, dim: int, device, row_begin: int = 0
 
 
 # ---------------------------------------------------------------------------
+# 16-bit tables (PlanSpec.table_dtype): the closed-form float32 value rounded once, to nearest-even, to bf16 / fp16
+# ---------------------------------------------------------------------------
+def table_patterns(x: np.ndarray, table_dtype: str) -> np.ndarray:
+    """uint16 bit patterns of the float32 array ``x`` rounded to ``table_dtype`` ("bf16" | "f16").  The closed form lies in
+    [-1, 1): no NaN, nothing overflows."""
+    x = np.ascontiguousarray(x, np.float32)
+    if table_dtype == "f16":
+        return x.astype(np.float16).view(np.uint16)
+    u = x.view(np.uint32).astype(np.uint64)
+    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+
+
+def table_values(bits: np.ndarray, table_dtype: str) -> np.ndarray:
+    """float32 values of 16-bit table patterns (exact)."""
+    bits = np.ascontiguousarray(bits, np.uint16)
+    if table_dtype == "f16":
+        return bits.view(np.float16).astype(np.float32)
+    return (bits.astype(np.uint32) << 16).view(np.float32)
+
+
+def round_to_table(x: np.ndarray, table_dtype: str) -> np.ndarray:
+    """What a table of ``table_dtype`` holds where the float32 table holds ``x``, as float32 (the identity for "f32")."""
+    return np.asarray(x, np.float32) if table_dtype == "f32" else table_values(table_patterns(x, table_dtype), table_dtype)
+
+
+# ---------------------------------------------------------------------------
 @dataclass
 class TableSpec:
     vocab: int
@@ -108,13 +134,24 @@ class SynthModel:
     description: str = ""
 
     def numpy_tables(self) -> List[np.ndarray]:
-        return [hash_table_numpy(t.seed, t.vocab, t.dim) for t in self.tables]
+        """float32 tables; uint16 bit patterns for a plan with 16-bit tables (``spec.table_dtype``)."""
+        dt = self.spec.table_dtype
+        tabs = [hash_table_numpy(t.seed, t.vocab, t.dim) for t in self.tables]
+        return tabs if dt == "f32" else [table_patterns(t, dt) for t in tabs]
 
     def torch_tables(self, device, shard_rank: int = 0, shard_world: int = 1):
-        return [hash_table_torch(t.seed, t.vocab, t.dim, device, shard_rank, shard_world) for t in self.tables]
+        """The tables on a torch device, in the plan's table dtype (torch's cast rounds to nearest-even, as
+        ``table_patterns`` does); converted one table at a time, so a 16-bit model never holds its float32 form whole."""
+        import torch
+        td = {"f32": None, "bf16": torch.bfloat16, "f16": torch.float16}[self.spec.table_dtype]
+        out = []
+        for t in self.tables:
+            x = hash_table_torch(t.seed, t.vocab, t.dim, device, shard_rank, shard_world)
+            out.append(x if td is None else x.to(td))
+        return out
 
     def table_bytes(self) -> int:
-        return sum(t.vocab * t.dim * 4 for t in self.tables)
+        return sum(t.vocab * t.dim * self.spec.table_elem_size for t in self.tables)
 
 
 def submodel(model: SynthModel, keep: Sequence[int], name: Optional[str] = None) -> SynthModel:
@@ -291,10 +328,13 @@ def _add_ragged(b: _Builder, vocab: int, dim: int, slot: int, combiner: int, seg
 
 
 def _finish(name: str, b: _Builder, batch: int, n_groups: int = 1, n_symbols: int = 0, description: str = "",
-            symbol_values: Optional[Callable[[int], np.ndarray]] = None, out_dtype: str = "f32") -> SynthModel:
+            symbol_values: Optional[Callable[[int], np.ndarray]] = None, out_dtype: str = "f32",
+            table_dtype: str = "f32") -> SynthModel:
     spec = b.spec(n_groups, n_symbols)
     if out_dtype != "f32":   # narrow output: the concat groups as bf16 / fp16
         spec = spec.with_out_dtype(out_dtype)
+    if table_dtype != "f32":   # 16-bit tables: numpy_tables / torch_tables then produce 16-bit patterns
+        spec = spec.with_table_dtype(table_dtype)
     spec.validate()
     gens = list(b.gens)
 
@@ -314,7 +354,7 @@ def _finish(name: str, b: _Builder, batch: int, n_groups: int = 1, n_symbols: in
 # ---------------------------------------------------------------------------
 # BASELINE.json configurations
 # ---------------------------------------------------------------------------
-def model_s1(columns: int = 100, dim: int = 16, vocab: int = 10_000, batch: int = 128, out_dtype: str = "f32") -> SynthModel:
+def model_s1(columns: int = 100, dim: int = 16, vocab: int = 10_000, batch: int = 128, out_dtype: str = "f32", table_dtype: str = "f32") -> SynthModel:
     """S1: 100 columns, dim 16, vocab 10k, batch 128, one id per row.  Even
     columns arrive as form 1 (dense GatherV2), odd columns as form 2 with
     SparseTensor indices (mean over exactly one id) — both rewrites the
@@ -336,12 +376,12 @@ def model_s1(columns: int = 100, dim: int = 16, vocab: int = 10_000, batch: int 
             b.gens.append(gen)
             b.columns.append(ColumnSpec(FORM_SEGMENT_REDUCE, dim, vocab, COMBINER_MEAN, IDS_I64, t, ids_in,
                                         seg_in, SEG_IDS_I64, 2, ROWS_FROM_SYMBOL, 0, None, 0, c))
-    return _finish("S1", b, batch, n_symbols=1, out_dtype=out_dtype,
+    return _finish("S1", b, batch, n_symbols=1, out_dtype=out_dtype, table_dtype=table_dtype,
                    description=f"{columns} cols, dim {dim}, vocab {vocab}, B {batch}, 1 id/row")
 
 
 def model_s2(columns: int = 1000, vocab: int = 1_000_000, batch: int = 512, dist: str = "uniform",
-             dims: Sequence[int] = (8, 16, 32, 64), vocab_of: Optional[dict] = None, out_dtype: str = "f32") -> SynthModel:
+             dims: Sequence[int] = (8, 16, 32, 64), vocab_of: Optional[dict] = None, out_dtype: str = "f32", table_dtype: str = "f32") -> SynthModel:
     """S2 (headline): 1000 columns, dims cycling 8/16/32/64, vocab 1M (120 GB of
     tables), batch 512, one id per row (form 1); every 10th column is sourced by
     a float feature bucketized with 100 boundaries (the reference's dominant
@@ -355,13 +395,13 @@ def model_s2(columns: int = 1000, vocab: int = 1_000_000, batch: int = 512, dist
             _add_dense(b, v, d, slot=c, id_source=IDS_F32_BUCKETIZE, boundaries=MICROBENCH_BOUNDARIES)
         else:
             _add_dense(b, v, d, slot=c, dist=dist)
-    return _finish("S2", b, batch, out_dtype=out_dtype,
+    return _finish("S2", b, batch, out_dtype=out_dtype, table_dtype=table_dtype,
                    description=f"{columns} cols, dims {'/'.join(map(str, dims))}, vocab {vocab}, B {batch}, "
                                f"1 id/row, 10% bucketize-f32, ids {dist}")
 
 
 def model_dlrm(batch: int = 2048, dim: int = 16, cardinalities: Sequence[int] = tuple(CRITEO_KAGGLE_CARDINALITIES),
-               n_dense: int = 13, out_dtype: str = "f32") -> SynthModel:
+               n_dense: int = 13, out_dtype: str = "f32", table_dtype: str = "f32") -> SynthModel:
     """DLRM-style: 26 categorical (Criteo-Kaggle cardinalities, dim 16, one id
     per row) + 13 dense features passed through into one concat slot."""
     b = _Builder()
@@ -371,12 +411,12 @@ def model_dlrm(batch: int = 2048, dim: int = 16, cardinalities: Sequence[int] = 
     b.gens.append(lambda rng, B: [rng.uniform(0, 100, size=(B, n_dense)).astype(np.float32)])
     b.columns.append(ColumnSpec(FORM_PASSTHROUGH, n_dense, 0, COMBINER_NONE, IDS_I32, -1, i, -1, SEG_NONE, 1,
                                 ROWS_FROM_INPUT_DIM0, i, None, 0, len(cardinalities)))
-    return _finish("DLRM", b, batch, out_dtype=out_dtype, description=f"26 categorical dim {dim} + {n_dense} dense, B {batch}")
+    return _finish("DLRM", b, batch, out_dtype=out_dtype, table_dtype=table_dtype, description=f"26 categorical dim {dim} + {n_dense} dense, B {batch}")
 
 
 def model_ragged(columns: int = 512, vocab: int = 100_000, batch: int = 256, seg: str = "csr",
                  max_len: int = 10, dims: Sequence[int] = (8, 16, 32, 64), dist: str = "uniform",
-                 weighted: bool = False, out_dtype: str = "f32") -> SynthModel:
+                 weighted: bool = False, out_dtype: str = "f32", table_dtype: str = "f32") -> SynthModel:
     """RAGGED: 512 multi-hot columns, ids/row ~ U{0..10}, sum/mean alternating,
     nnz re-drawn per request (dynamic shapes).  ``weighted``: every column with per-id weights (what weights cost:
     scripts/weighted_bags_cost.py)."""
@@ -384,7 +424,7 @@ def model_ragged(columns: int = 512, vocab: int = 100_000, batch: int = 256, seg
     for c in range(columns):
         comb = COMBINER_SUM if c % 2 == 0 else COMBINER_MEAN
         _add_ragged(b, vocab, dims[c % len(dims)], slot=c, combiner=comb, seg=seg, max_len=max_len, dist=dist, weighted=weighted)
-    return _finish("RAGGED", b, batch, n_symbols=1, out_dtype=out_dtype,
+    return _finish("RAGGED", b, batch, n_symbols=1, out_dtype=out_dtype, table_dtype=table_dtype,
                    description=f"{columns} cols multi-hot U{{0..{max_len}}}, vocab {vocab}, B {batch}, seg={seg}")
 
 
@@ -437,7 +477,7 @@ def model_mixed(batch: int = 33, vocab: int = 997, seed_dims: Sequence[int] = (4
     return m
 
 
-def model_ae(which: str = "E", batch: int = 512, large_rows: int = 1 << 23, out_dtype: str = "f32") -> SynthModel:
+def model_ae(which: str = "E", batch: int = 512, large_rows: int = 1 << 23, out_dtype: str = "f32", table_dtype: str = "f32") -> SynthModel:
     """The reference's own AE models E / F (``examples/python/dlrm.py:140-203``) in
     post-rewrite form: E = (880, 50, 50, 15, 5), F = (1000, 90, 100, 7, 3) columns of
     {bucketize(100 boundaries 0,5,..,495 -> 101 rows, dim 8, mean, 1 value/row),
@@ -485,7 +525,7 @@ def model_ae(which: str = "E", batch: int = 512, large_rows: int = 1 << 23, out_
             b.columns.append(ColumnSpec(FORM_SEGMENT_REDUCE, dim, rows, COMBINER_SUM, IDS_I64, t, ids_in, seg_in,
                                         SEG_IDS_I64, 2, ROWS_FROM_SYMBOL, 0, None, 0, slot))
             slot += 1
-    return _finish(f"AE-{which.upper()}", b, batch, n_symbols=1, out_dtype=out_dtype,
+    return _finish(f"AE-{which.upper()}", b, batch, n_symbols=1, out_dtype=out_dtype, table_dtype=table_dtype,
                    description=f"reference model {which.upper()}: {counts} columns of bucketize/hash-int/hash-str/sparse/"
                                f"large-sparse, B {batch}")
 
