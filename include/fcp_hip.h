@@ -197,12 +197,30 @@ enum {
    * neither: the float32-table plan and its code paths, exactly.  Refused with FCP_ERR_UNSUPPORTED: together with
    * FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16, shard_world > 1, any column with per-id weights or FCP_COMBINER_SQRTN. */
   FCP_FLAG_TABLES_BF16 = 1u << 3,
-  FCP_FLAG_TABLES_F16 = 1u << 4
+  FCP_FLAG_TABLES_F16 = 1u << 4,
+  /* 8-bit row-quantised tables (the "fused 8-bit rowwise" format of FBGEMM / TorchRec, the tensor PyTorch's
+   * quantized::embedding_bag_byte_prepack returns): EVERY embedding table of the plan (every device input a GATHER /
+   * SEGMENT_REDUCE / GATHER_SCATTER column reads) is row-major uint8 [vocab, dim + 8], its base 4-byte aligned, no padding
+   * between rows: row r starts at byte r * (dim + 8); bytes [0, dim) are the codes, [dim, dim + 4) the float32 scale,
+   * [dim + 4, dim + 8) the float32 bias, both little-endian and read correctly at ANY byte alignment (a dim that is no
+   * multiple of 4 misaligns them in most rows).  An element dequantises to the float32 value fma(float(code), scale, bias):
+   * the product exact, the sum rounded ONCE to nearest-even (what quantized::embedding_bag_byte_unpack computes; NaN and
+   * infinity follow IEEE); the plan then computes, bit for bit, what the same plan without the bit computes on the
+   * dequantised float32 tables: gathers, scatters, pooled sums and means in id order from +0.0, range checks, the +0.0 rows
+   * of ids outside the vocabulary.  Everything else is unchanged — the geometry, the float32 output, the blob (PASSTHROUGH /
+   * BATCH_COL_REDUCTION payloads stay float32), both layouts, every id source and transform, FCP_FLAG_COUNT_BAD_IDS,
+   * 2^32 - 3 rows per table; fcp_plan_table_bytes counts vocab * (dim + 8).  The library does not quantise: it reads what it
+   * is given.  Together with FCP_FLAG_TABLES_BF16 / _F16: FCP_ERR_INVALID_ARGUMENT.  Refused with FCP_ERR_UNSUPPORTED:
+   * together with FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16, shard_world > 1, any column with per-id weights or
+   * FCP_COMBINER_SQRTN. */
+  FCP_FLAG_TABLES_Q8 = 1u << 5
 };
 /* element type of the plan's outputs (fcp_plan_out_dtype) */
 enum { FCP_OUT_F32 = 0, FCP_OUT_BF16 = 1, FCP_OUT_F16 = 2 };
 /* element type of the plan's embedding tables (fcp_plan_table_dtype) */
 enum { FCP_TAB_F32 = 0, FCP_TAB_BF16 = 1, FCP_TAB_F16 = 2 };
+/* (FCP_FLAG_TABLES_Q8: uint8 codes with a float32 scale and bias behind every row) */
+enum { FCP_TAB_Q8 = 3 };
 /* A plan without device resources: layout / arena / table-byte queries and plan-file checks on a machine
  * without a GPU (offline graph tooling).  Anything that computes returns FCP_ERR_NO_DEVICE — there is no
  * CPU fallback.  (A macro: the value does not fit an int enumerator.) */
@@ -375,10 +393,11 @@ int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext,
  *   anywhere else, twice, with another name, or in a file of version <= 5 is malformed;
  *   version 7 files (plans with 16-bit tables, and only those) carry "table_dtype bf16" or
  *   "table_dtype f16" in the same place under the same rules (and no out_dtype line: the
- *   two features exclude each other).
+ *   two features exclude each other); plans with 8-bit row-quantised tables are version 7
+ *   files too and carry "table_dtype q8".
  * `flags`: fcp_plan_desc_t::flags.  FCP_FLAG_OUT_BF16 / _F16 on a file without the
  * line select the dtype; bits that name the file's dtype are fine, the other dtype is
- * FCP_ERR_INVALID_ARGUMENT; FCP_FLAG_TABLES_BF16 / _F16 and a table_dtype line likewise.
+ * FCP_ERR_INVALID_ARGUMENT; FCP_FLAG_TABLES_BF16 / _F16 / _Q8 and a table_dtype line likewise.
  * FCP_ERR_INVALID_ARGUMENT for a missing or malformed file. */
 int fcp_plan_create_from_file(const char *path, int32_t device, uint32_t flags,
                               fcp_plan_t **plan);
@@ -395,12 +414,14 @@ int fcp_plan_output_columns(const fcp_plan_t *plan, int32_t *n, int32_t *indices
                             int32_t capacity);
 /* FCP_OUT_*: the element type of the plan's outputs (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16). */
 int fcp_plan_out_dtype(const fcp_plan_t *plan, int32_t *out);
-/* FCP_TAB_*: the element type of the plan's embedding tables (FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16). */
+/* FCP_TAB_*: the element type of the plan's embedding tables (FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16 /
+ * FCP_FLAG_TABLES_Q8). */
 int fcp_plan_table_dtype(const fcp_plan_t *plan, int32_t *out);
 /* Bytes of embedding tables this plan reads on THIS device (its shard of every
  * table, shared tables counted once) and the largest single table's bytes
  * (unsharded) — the inputs of the placement gate, fcp_placement_decide; 2 bytes per
- * element in a plan with 16-bit tables. */
+ * element in a plan with 16-bit tables, dim + 8 bytes per row in a plan with 8-bit
+ * row-quantised tables. */
 int fcp_plan_table_bytes(const fcp_plan_t *plan, int64_t *shard_bytes,
                          int64_t *max_table_bytes_unsharded);
 /* ---- placement gate (replaces check_table_size, cuda_emitter.cc:1080-1094) -------- */
@@ -467,7 +488,9 @@ enum {
   /* the narrow-output instantiations of the three (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16 plans) */
   FCP_LAUNCH_DENSE_NARROW = 5, FCP_LAUNCH_RAGGED_NARROW = 6, FCP_LAUNCH_HYBRID_NARROW = 7,
   /* the 16-bit-table instantiations of the three (FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16 plans) */
-  FCP_LAUNCH_DENSE_TAB16 = 8, FCP_LAUNCH_RAGGED_TAB16 = 9, FCP_LAUNCH_HYBRID_TAB16 = 10
+  FCP_LAUNCH_DENSE_TAB16 = 8, FCP_LAUNCH_RAGGED_TAB16 = 9, FCP_LAUNCH_HYBRID_TAB16 = 10,
+  /* the 8-bit row-quantised-table instantiations of the three (FCP_FLAG_TABLES_Q8 plans) */
+  FCP_LAUNCH_DENSE_TABQ8 = 11, FCP_LAUNCH_RAGGED_TABQ8 = 12, FCP_LAUNCH_HYBRID_TABQ8 = 13
 };
 enum { FCP_LAUNCH_STORE_NT = 0, FCP_LAUNCH_STORE_SC1_NT = 1, FCP_LAUNCH_STORE_PLAIN = 4 };
 enum { FCP_LAUNCH_SEG_NONE = 0, FCP_LAUNCH_SEG_PREPASS = 1, FCP_LAUNCH_SEG_SEARCH = 2 };

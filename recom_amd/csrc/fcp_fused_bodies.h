@@ -250,6 +250,60 @@ template <int V> __device__ __forceinline__ VF<V> ld_slot32_16(const char *tb, u
   return widen16<V>(*g, tab_kind);
 }
 
+// ---- 8-bit row-quantised tables (fcp_tables_q8.hip: FCP_FLAG_TABLES_Q8 plans) -----------------------------------------------
+// A table row is dim uint8 codes, then a float32 scale, then a float32 bias, rows back to back: dim + 8 bytes.  An element is
+// the float32 value fma(float(code), scale, bias) — the product exact (8 x 24 bits), the sum rounded once: one v_fma_f32,
+// written out, not left to contraction.  A slot is still V elements: one load of V code bytes —
+// dword | ushort | ubyte — plus the row's scale and bias, which lie at a multiple of V bytes (V divides dim and 8) and of no
+// more: the pair is declared with that alignment and the compiler forms the loads this target allows for it.
+template <int V> struct Q8Pair;
+template <> struct Q8Pair<4> { typedef uint64_t T __attribute__((aligned(4))); };
+template <> struct Q8Pair<2> { typedef uint64_t T __attribute__((aligned(2))); };
+template <> struct Q8Pair<1> { typedef uint64_t T __attribute__((aligned(1))); };
+template <int V> struct Q8Codes;
+template <> struct Q8Codes<4> { typedef uint32_t T; };
+template <> struct Q8Codes<2> { typedef uint16_t T; };
+template <> struct Q8Codes<1> { typedef uint8_t T; };
+struct Q8Raw {
+  uint32_t codes; // V code bytes, element i in byte i
+  uint64_t pair;  // scale in the low dword, bias in the high one
+};
+// codes: BYTE address of the lane's V codes (row base + element offset); sb: byte address of the row's scale (row base + dim)
+template <int V> __device__ __forceinline__ Q8Raw ld_q8_raw(const char *codes, const char *sb) {
+  typedef typename Q8Codes<V>::T T;
+  Q8Raw r;
+  r.codes = *as_global(reinterpret_cast<const T *>(codes));
+  r.pair = *(const FCP_GLOBAL typename Q8Pair<V>::T *)(sb);
+  return r;
+}
+// element i: one v_fma_f32, by name — neither contraction nor the vectoriser has a say in how this value is rounded.
+// What that costs: the compiler may not pair two elements into a v_pk_fma_f32 (as fused, half the issue slots), and it
+// schedules the statement without seeing inside it.  These kernels wait on table reads, not on the VALU.
+__device__ __forceinline__ float dequant_q8(const Q8Raw &w, int i) {
+  const float code = (float)((w.codes >> (8 * i)) & 0xFFu);
+  float x;
+  asm("v_fma_f32 %0, %1, %2, %3" : "=v"(x) : "v"(code), "v"(__uint_as_float((uint32_t)w.pair)), "v"(__uint_as_float((uint32_t)(w.pair >> 32))));
+  return x;
+}
+template <int V> __device__ __forceinline__ VF<V> ld_q8(const char *codes, const char *sb) {
+  const Q8Raw w = ld_q8_raw<V>(codes, sb);
+  VF<V> r;
+#pragma unroll
+  for (int i = 0; i < V; ++i) r.v[i] = dequant_q8(w, i);
+  return r;
+}
+// The loaders in their 8-bit forms.  `tb`: the lane-specific base as a BYTE address (table + element offset e); `tail`:
+// dim - e, the distance from the lane's codes to the row's scale; `row_bytes`: dim + 8 (one v_mad_u64_u32 forms the row's
+// byte offset from a parked row index).  A PRE-SCALED offset is row x the row stride in slots, (dim + 8) / V: offset x V
+// is the row's byte offset, as in the float32 forms a slot offset x 4 * V is.
+template <int V> __device__ __forceinline__ VF<V> ld_slot_q8(const char *tb, int tail, uint32_t off, uint32_t row_bytes) {
+  const char *codes = tb + (uint64_t)off * row_bytes;
+  return ld_q8<V>(codes, codes + tail);
+}
+template <int V> __device__ __forceinline__ VF<V> ld_slot32_q8(const char *tb, int tail, uint32_t off) {
+  const char *codes = tb + (uint64_t)off * V;
+  return ld_q8<V>(codes, codes + tail);
+}
 // Blob tensors are only guaranteed 4-byte aligned (ConcatInputs packs bytes
 // back to back, concat_inputs_ops.cc:52-60): payloads are read dword by dword,
 // 8-byte ids as two dwords.
@@ -654,7 +708,10 @@ template <int R> struct DenseLds {
 // TAB16: the instantiation for bf16 / fp16 table plans (fcp_tables16.hip); `tab_kind` (FCP_TAB_*) is launch-uniform.  Only the
 // table address (2 bytes per element) and the load differ, both behind `if constexpr (TAB16)`.  A PASSTHROUGH column's
 // "table" is its float32 payload in the blob and is read as such.
-template <int V, int R, bool SHARDED, bool NARROW = false, bool TAB16 = false>
+// TABQ8: the instantiation for 8-bit row-quantised table plans (fcp_tables_q8.hip).  The table address and the load differ,
+// and a row index is scaled by the row stride in slots, (dim + 8) / V, where the float32 plan scales by dim / V; all behind
+// `if constexpr (TABQ8)`.
+template <int V, int R, bool SHARDED, bool NARROW = false, bool TAB16 = false, bool TABQ8 = false>
 __device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *smem, int out_kind = 0, int tab_kind = 0) {
   constexpr int RB = DenseLds<R>::RB, IDS = DenseLds<R>::IDS, BND = DenseLds<R>::BND;
   DenseLds<R> &S = *reinterpret_cast<DenseLds<R> *>(smem);
@@ -763,7 +820,11 @@ __device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *sm
         off = slot_offset_from_raw<V, SHARDED>(c, L.xforms + B.first_col + j, raw_lo[h], raw_hi[h],
                                                c.bnd_off >= 0 ? s_bnd + c.bnd_off : nullptr,
                                                rank, world, bad);
-        if (!wide && is_row(off)) off *= (uint32_t)(c.dim / V); // every table of the plan has < 2^32 - 3 slots: pre-scaled
+        if constexpr (TABQ8) {
+          if (!wide && is_row(off)) off *= (uint32_t)((c.dim + 8) / V); // the row STRIDE in slots: offset x V = the row's byte offset
+        } else {
+          if (!wide && is_row(off)) off *= (uint32_t)(c.dim / V); // every table of the plan has < 2^32 - 3 slots: pre-scaled
+        }
         // a column that straddles two spans is staged by two blocks: the one holding its first slot counts
         if (bad && H.bad_ids && c.out_off >= B.q0 * V) atomicAdd(H.bad_ids, 1ull);
       } // FCP_FORM_EXTERNAL: nothing to fetch, nothing to write
@@ -795,6 +856,14 @@ __device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *sm
       if (FCP_F_FORM(s_col[j].flags) != FCP_FORM_PASSTHROUGH) {
         const char *tb16 = reinterpret_cast<const char *>(s_col[j].table) + 2 * (int64_t)e; // element offset x 2, in 64 bits
         if (is_row(off[r])) v[r] = wide ? ld_slot16<V>(tb16, off[r], spr, tab_kind) : ld_slot32_16<V>(tb16, off[r], tab_kind);
+        continue;
+      }
+    }
+    if constexpr (TABQ8) {
+      if (FCP_F_FORM(s_col[j].flags) != FCP_FORM_PASSTHROUGH) {
+        const char *tb8 = reinterpret_cast<const char *>(s_col[j].table) + e; // the lane's codes in row 0; the scale dim - e behind
+        const int tail = s_col[j].dim - e;
+        if (is_row(off[r])) v[r] = wide ? ld_slot_q8<V>(tb8, tail, off[r], (uint32_t)s_col[j].dim + 8u) : ld_slot32_q8<V>(tb8, tail, off[r]);
         continue;
       }
     }
@@ -938,19 +1007,44 @@ __device__ __forceinline__ VF<V> ld_slot_or_zero16(const char *tb, const float *
   return widen16<V>(*g, tab_kind);
 }
 
+// (8-bit row-quantised tables; the zero line: zero codes with a zero scale and a zero bias dequantise to fma(0, +0, +0) = +0.0)
+template <int V>
+__device__ __forceinline__ Q8Raw ld_slot_or_zero_q8(const char *tb, const float *zeros, int tail, uint32_t off, uint32_t row_bytes) {
+  // (both candidates are formed first: the choice is a v_cndmask pair, never a branch around the multiply — a branch per
+  // read would cut the batch of reads into dependent pieces.  The zero line of a q8 plan is as long as its longest row, so
+  // the scale and bias are read `tail` bytes behind the codes there too: zeros.)
+  const char *in_table = tb + (uint64_t)off * row_bytes, *in_zeros = reinterpret_cast<const char *>(zeros);
+  const char *codes = is_row(off) ? in_table : in_zeros;
+  return ld_q8_raw<V>(codes, codes + tail);
+}
+
 // The walk of one bag slice for one output slot: the n table slot offsets staged at s[0..n) are added to `acc`
 // in id order (sequential fp32 adds: the order of the oracle; TF-CPU's up to 9 ids per bag), kWalk table reads in flight
 // per lane.  EVERY lane issues its first kWalk reads at once, whatever its bag length; further batches
 // only while some bag of the wave goes on.  (Round 2 walked "8, then 4" behind per-lane conditions: lanes with
 // up to 4 ids sat out the first pass and issued their reads only after it.)
 // TAB16 (16-bit tables): `tb` carries the lane's base as a byte address, the reads are the 16-bit loader's.
-template <int V, int N, bool TAB16 = false>
+// TABQ8 (8-bit row-quantised tables): `tb` carries the lane's base as a byte address, `q8_tail` the distance from the lane's
+// codes to the row's scale; `spr` is the row's size in BYTES, dim + 8.
+template <int V, int N, bool TAB16 = false, bool TABQ8 = false>
 __device__ __forceinline__ void bag_walk_batch(const float *tb, const float *zeros, uint32_t spr, const uint32_t *s, int base, int n, VF<V> &acc,
-                                               int tab_kind = 0) {
+                                               int tab_kind = 0, int q8_tail = 0) {
   uint32_t off[N];
-  VF<V> w[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) off[k] = base + k < n ? s[base + k] : kNoRow;
+  if constexpr (TABQ8) {
+    // the reads stay in flight as they arrived (three dwords per row, not V floats); an element is dequantised where it
+    // is added, in id order
+    Q8Raw raw[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) raw[k] = ld_slot_or_zero_q8<V>(reinterpret_cast<const char *>(tb), zeros, q8_tail, off[k], spr);
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+#pragma unroll
+      for (int t = 0; t < V; ++t) acc.v[t] = acc.v[t] + dequant_q8(raw[k], t);
+    return;
+  }
+  VF<V> w[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) {
     if constexpr (TAB16)
@@ -964,29 +1058,29 @@ __device__ __forceinline__ void bag_walk_batch(const float *tb, const float *zer
     for (int t = 0; t < V; ++t) acc.v[t] = acc.v[t] + w[k].v[t]; // id order
 }
 
-template <int V, int WALK, bool TAB16 = false>
+template <int V, int WALK, bool TAB16 = false, bool TABQ8 = false>
 __device__ __forceinline__ void bag_walk_sum(const float *tb, const float *zeros, uint32_t spr, const uint32_t *s, int n, VF<V> &acc,
-                                             int tab_kind = 0) {
+                                             int tab_kind = 0, int q8_tail = 0) {
   // The first batch is as wide as the wave's longest bag needs, up to kWalkFirst reads per lane: every bag of
   // the wave in ONE round of reads whenever none is longer than that (BASELINE's RAGGED and the reference's models
   // E / F draw 0..10 / 1..10 ids per row: with 8-wide batches nearly every wave ran a second round for its one or two
   // 9- and 10-id bags; RAGGED 30.2 -> 28.9 us, profiles/r03_ragged_walk_width_ab.txt).  Wave-uniform choices.
   int base = WALK;
   if (WALK >= 8 && !__any(n > 4)) {
-    bag_walk_batch<V, 4, TAB16>(tb, zeros, spr, s, 0, n, acc, tab_kind);
+    bag_walk_batch<V, 4, TAB16, TABQ8>(tb, zeros, spr, s, 0, n, acc, tab_kind, q8_tail);
     return;
   } else if (WALK >= 8 && kWalkFirst > WALK && __any(n > WALK)) {
-    bag_walk_batch<V, kWalkFirst, TAB16>(tb, zeros, spr, s, 0, n, acc, tab_kind);
+    bag_walk_batch<V, kWalkFirst, TAB16, TABQ8>(tb, zeros, spr, s, 0, n, acc, tab_kind, q8_tail);
     base = kWalkFirst;
   } else {
-    bag_walk_batch<V, WALK, TAB16>(tb, zeros, spr, s, 0, n, acc, tab_kind);
+    bag_walk_batch<V, WALK, TAB16, TABQ8>(tb, zeros, spr, s, 0, n, acc, tab_kind, q8_tail);
   }
   for (; __any(n > base);) { // wave-uniform trip count
     if (WALK > 4 && !__any(n > base + 4)) { // a short tail (bags of 9..12 ids): half a batch
-      bag_walk_batch<V, 4, TAB16>(tb, zeros, spr, s, base, n, acc, tab_kind);
+      bag_walk_batch<V, 4, TAB16, TABQ8>(tb, zeros, spr, s, base, n, acc, tab_kind, q8_tail);
       base += 4;
     } else {
-      bag_walk_batch<V, WALK, TAB16>(tb, zeros, spr, s, base, n, acc, tab_kind);
+      bag_walk_batch<V, WALK, TAB16, TABQ8>(tb, zeros, spr, s, base, n, acc, tab_kind, q8_tail);
       base += WALK;
     }
   }
@@ -1067,10 +1161,13 @@ struct RaggedLds {
 // NARROW: as in the dense body — bf16 / fp16 output plans (fcp_narrow.hip), everything behind `if constexpr (NARROW)`.
 // TAB16: as in the dense body — bf16 / fp16 table plans (fcp_tables16.hip), everything behind `if constexpr (TAB16)`; never
 // together with WEIGHTED (such plans are refused when they are created).
-template <int V, bool SHARDED, bool WEIGHTED = false, bool NARROW = false, bool TAB16 = false>
+// TABQ8: as in the dense body — 8-bit row-quantised table plans (fcp_tables_q8.hip), everything behind `if constexpr (TABQ8)`;
+// never together with WEIGHTED either.
+template <int V, bool SHARDED, bool WEIGHTED = false, bool NARROW = false, bool TAB16 = false, bool TABQ8 = false>
 __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *smem, const int64_t *wts = nullptr, int out_kind = 0,
                                             int tab_kind = 0) {
   static_assert(!(TAB16 && WEIGHTED), "the weighted walk reads float32 tables");
+  static_assert(!(TABQ8 && (WEIGHTED || TAB16)), "one table format per instantiation; the weighted walk reads float32 tables");
   constexpr int RB = RaggedLds::RB, CAPW = RaggedLds::CAPW;
   RaggedLds &S = *reinterpret_cast<RaggedLds *>(smem);
   LdsCol *s_col = S.col;
@@ -1220,7 +1317,14 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
     const float *tb = s_col[j].table + (q * V - s_col[j].out_off);
     if constexpr (TAB16) // the same element as a byte address: element offset x 2, in 64 bits
       tb = reinterpret_cast<const float *>(reinterpret_cast<const char *>(s_col[j].table) + 2 * (int64_t)(q * V - s_col[j].out_off));
-    const uint32_t spr = (uint32_t)(s_col[j].dim / V); // slots per table row
+    uint32_t spr = (uint32_t)(s_col[j].dim / V); // slots per table row
+    int q8_tail = 0;
+    if constexpr (TABQ8) { // the lane's codes in row 0 as a byte address, their distance to the row's scale, the row's bytes
+      const int e = q * V - s_col[j].out_off;
+      tb = reinterpret_cast<const float *>(reinterpret_cast<const char *>(s_col[j].table) + e);
+      q8_tail = s_col[j].dim - e;
+      spr = (uint32_t)s_col[j].dim + 8u;
+    }
     if (form == FCP_FORM_SEGMENT_REDUCE) {
       if ((s_col[j].xform & 3u) == FCP_XFORM_FILTER && (FCP_F_COMBINER(s_col[j].flags) == FCP_COMBINER_MEAN ||
                                                         (WEIGHTED && FCP_F_COMBINER(s_col[j].flags) == FCP_COMBINER_SQRTN))) {
@@ -1237,6 +1341,8 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
         } else { // (no wider than kWalkLong: next to the weight pointer and the denominator a 10-wide batch spills at V = 4)
           bag_walk_sum<V, (WALK < kWalkLong ? WALK : kWalkLong)>(tb, H.zeros, spr, s, n, acc);
         }
+      } else if constexpr (TABQ8) {
+        bag_walk_sum<V, WALK, false, true>(tb, H.zeros, spr, s, n, acc, 0, q8_tail);
       } else if constexpr (TAB16) {
         bag_walk_sum<V, WALK, true>(tb, H.zeros, spr, s, n, acc, tab_kind);
       } else {
@@ -1250,7 +1356,9 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
       const uint32_t off = s[k];
       if (off != kFiltered) {
         acc = vzero<V>();
-        if constexpr (TAB16) {
+        if constexpr (TABQ8) {
+          if (is_row(off)) acc = ld_slot_q8<V>(reinterpret_cast<const char *>(tb), q8_tail, off, spr);
+        } else if constexpr (TAB16) {
           if (is_row(off)) acc = ld_slot16<V>(reinterpret_cast<const char *>(tb), off, spr, tab_kind);
         } else {
           if (is_row(off)) acc = ld_slot<V>(tb, off, spr);

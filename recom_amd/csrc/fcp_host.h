@@ -287,11 +287,15 @@ struct fcp_plan {
   // 16-bit tables (FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16): the element type (FCP_TAB_*) of every table and its size in
   // bytes.  Geometry, slot offsets and wide_rows are in elements and do not depend on it; fcp_plan_table_bytes does
   int tab_kind = FCP_TAB_F32, tab_elem = 4;
+  // 8-bit row-quantised tables (FCP_FLAG_TABLES_Q8): tab_kind FCP_TAB_Q8, tab_elem 1, and 8 bytes of scale and bias behind
+  // every row.  Geometry stays in elements; the row STRIDE in slots, (dim + 8) / vec, is what scales a row index and what
+  // wide_rows is decided from
+  int tab_row_tail = 0;
   std::vector<FcpColStatic> h_cols;
   char *d_const = nullptr;
   int32_t *d_seg_cols = nullptr;
   unsigned long long *d_bad = nullptr;
-  float *d_zeros = nullptr;     // 256 zero bytes: the row a skipped id of a bag reads (ld_slot_or_zero)
+  float *d_zeros = nullptr;     // 256 zero bytes (a q8 plan: its longest row, rounded up): the row a skipped id of a bag reads (ld_slot_or_zero)
   std::vector<const void *> bound_tables;
   bool tables_bound = false;
 

@@ -193,6 +193,10 @@ int fcp_launch_narrow_hybrid(const FcpLaunch &Ldense, int dense_blocks, const Fc
 int fcp_launch_tab16(const FcpLaunch &L, int vec, bool dense_kernel, int tab_kind, int grid_blocks, ihipStream_t *s);
 int fcp_launch_tab16_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch &Lragged, int ragged_blocks, int vec,
                             int tab_kind, ihipStream_t *s);
+// (fcp_tables_q8.hip) the same for plans with 8-bit row-quantised tables (FCP_FLAG_TABLES_Q8)
+int fcp_launch_tabq8(const FcpLaunch &L, int vec, bool dense_kernel, int grid_blocks, ihipStream_t *s);
+int fcp_launch_tabq8_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch &Lragged, int ragged_blocks, int vec,
+                            ihipStream_t *s);
 // (fcp_dense_plain.hip) the small dense kernel of plain dense plans: V 4, R 4, the grid of fcp_launch_fused's dense kernel
 int fcp_launch_dense_plain(const FcpPlainLaunch &P, int grid_blocks, ihipStream_t *s);
 // what the next fused launch of this thread would carry (stop event, any-order flag): taken and cleared

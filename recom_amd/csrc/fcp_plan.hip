@@ -213,6 +213,25 @@ int validate_tables16(const fcp_plan_desc_t *d, const fcp_column_ext_t *ext) {
   return FCP_OK;
 }
 
+// 8-bit row-quantised tables (FCP_FLAG_TABLES_Q8): the same refusals, by name, for the kernels of fcp_tables_q8.hip.
+int validate_tables_q8(const fcp_plan_desc_t *d, const fcp_column_ext_t *ext) {
+  if (!(d->flags & FCP_FLAG_TABLES_Q8)) return FCP_OK;
+  if (d->flags & (FCP_FLAG_TABLES_BF16 | FCP_FLAG_TABLES_F16))
+    return fail(FCP_ERR_INVALID_ARGUMENT, "FCP_FLAG_TABLES_Q8 and FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16 exclude each other");
+  if (d->flags & (FCP_FLAG_OUT_BF16 | FCP_FLAG_OUT_F16))
+    return fail(FCP_ERR_UNSUPPORTED, "8-bit tables with narrow output (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16): the 8-bit-table kernels store float32");
+  if (d->shard_world > 1)
+    return fail(FCP_ERR_UNSUPPORTED, "8-bit tables on a row-sharded plan (shard_world > 1): the sharded kernels read float32 tables");
+  for (int k = 0; k < d->n_columns; ++k) {
+    const std::string where = "column " + std::to_string(k) + ": ";
+    if (ext && ext[k].weights_input1 > 0)
+      return fail(FCP_ERR_UNSUPPORTED, where + "8-bit tables with per-id weights: weighted plans take the float32 weighted kernel");
+    if (d->columns[k].combiner == FCP_COMBINER_SQRTN && d->columns[k].form == FCP_FORM_SEGMENT_REDUCE)
+      return fail(FCP_ERR_UNSUPPORTED, where + "8-bit tables with FCP_COMBINER_SQRTN: sqrtn plans take the float32 weighted kernel");
+  }
+  return FCP_OK;
+}
+
 // Run-time shapes -> per-column dynamic records, arena layout and launch
 // geometry.  Mirrors what the generated host code evaluates per call from
 // SymEngine expressions (cuda_emitter.cc:2151-2179, :2410-2455).
@@ -850,8 +869,13 @@ int init_device(fcp_plan *p) {
     HIP_TRY(hipMalloc(&p->d_seg_cols, seg_pos.size() * sizeof(int32_t)));
     HIP_TRY(hipMemcpy(p->d_seg_cols, seg_pos.data(), seg_pos.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   }
-  HIP_TRY(hipMalloc(&p->d_zeros, 256));
-  HIP_TRY(hipMemset(p->d_zeros, 0, 256));
+  // (8-bit row-quantised tables: a skipped id reads zero codes AND, dim - e bytes behind them, a zero scale and bias: the
+  // line is as long as the plan's longest row)
+  size_t zero_bytes = 256;
+  if (p->tab_row_tail)
+    for (const auto &hc : p->cols) zero_bytes = std::max(zero_bytes, (size_t)((hc.d.dim + p->tab_row_tail + 255) / 256 * 256));
+  HIP_TRY(hipMalloc(&p->d_zeros, zero_bytes));
+  HIP_TRY(hipMemset(p->d_zeros, 0, zero_bytes));
   if (p->desc.flags & FCP_FLAG_COUNT_BAD_IDS) {
     HIP_TRY(hipMalloc(&p->d_bad, sizeof(unsigned long long)));
     HIP_TRY(hipMemset(p->d_bad, 0, sizeof(unsigned long long)));
@@ -930,6 +954,7 @@ int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext,
   if (rc) return rc;
   if (ext && (rc = validate_ext(desc, ext))) return rc;
   if ((rc = validate_narrow(desc, ext))) return rc;
+  if ((rc = validate_tables_q8(desc, ext))) return rc;
   if ((rc = validate_tables16(desc, ext))) return rc;
   fcp_plan *p = new (std::nothrow) fcp_plan();
   if (!p) return fail(FCP_ERR_ALLOC, "out of host memory");
@@ -940,6 +965,11 @@ int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext,
   if (desc->flags & (FCP_FLAG_TABLES_BF16 | FCP_FLAG_TABLES_F16)) {
     p->tab_kind = (desc->flags & FCP_FLAG_TABLES_BF16) ? FCP_TAB_BF16 : FCP_TAB_F16;
     p->tab_elem = 2;
+  }
+  if (desc->flags & FCP_FLAG_TABLES_Q8) {
+    p->tab_kind = FCP_TAB_Q8;
+    p->tab_elem = 1;
+    p->tab_row_tail = 8;
   }
   p->env = fcp::read_env(); // the library's shipping switches, read here and nowhere on the request path (fcp_env.h)
   p->desc = *desc;
@@ -1028,7 +1058,8 @@ int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext,
       delete p;
       return fail(FCP_ERR_UNSUPPORTED, "column " + std::to_string(k) + ": table shard exceeds 2^32 - 3 rows");
     }
-    if (local_vocab * (c.dim / p->vec) >= 0xFFFFFFFDLL || wide_rows_forced) p->wide_rows = true;
+    // (8-bit row-quantised tables: a row index is scaled by the row STRIDE in slots, (dim + 8) / vec — vec divides 8)
+    if (local_vocab * ((c.dim + p->tab_row_tail) / p->vec) >= 0xFFFFFFFDLL || wide_rows_forced) p->wide_rows = true;
   }
   // concat layout: offsets = prefix sums of dims in slot order
   // (concat_outputs_op_gpu.cu.cc:74-79)
@@ -1154,9 +1185,10 @@ int parse_plan_file(const char *path, ParsedPlanFile &P) {
   if (std::fscanf(f, "%31s %d", tag, &version) != 2 || std::strcmp(tag, "fcp_plan") || version < 1 || version > 7)
     return fail(FCP_ERR_INVALID_ARGUMENT, where + "bad header");
   if (version >= 7) { // plans with 16-bit tables: "table_dtype bf16|f16", under the rules of version 6's line, which they never carry
-    if (std::fscanf(f, "%31s %31s", tag, t2) != 2 || std::strcmp(tag, "table_dtype") || (std::strcmp(t2, "bf16") && std::strcmp(t2, "f16")))
-      return fail(FCP_ERR_INVALID_ARGUMENT, where + "expected 'table_dtype bf16' or 'table_dtype f16'");
-    P.tab_kind = !std::strcmp(t2, "bf16") ? FCP_TAB_BF16 : FCP_TAB_F16;
+    if (std::fscanf(f, "%31s %31s", tag, t2) != 2 || std::strcmp(tag, "table_dtype") ||
+        (std::strcmp(t2, "bf16") && std::strcmp(t2, "f16") && std::strcmp(t2, "q8")))
+      return fail(FCP_ERR_INVALID_ARGUMENT, where + "expected 'table_dtype bf16', 'table_dtype f16' or 'table_dtype q8'");
+    P.tab_kind = !std::strcmp(t2, "bf16") ? FCP_TAB_BF16 : !std::strcmp(t2, "f16") ? FCP_TAB_F16 : FCP_TAB_Q8;
   } else if (version >= 6) { // narrow-output plans: "out_dtype bf16|f16", here and nowhere else (anywhere else it is no 'layout' / section)
     if (std::fscanf(f, "%31s %31s", tag, t2) != 2 || std::strcmp(tag, "out_dtype") || (std::strcmp(t2, "bf16") && std::strcmp(t2, "f16")))
       return fail(FCP_ERR_INVALID_ARGUMENT, where + "expected 'out_dtype bf16' or 'out_dtype f16'");
@@ -1300,8 +1332,8 @@ int fcp_plan_create_from_file(const char *path, int32_t device, uint32_t flags, 
     P.d.flags |= file_bit;
   }
   if (P.tab_kind != FCP_TAB_F32) { // likewise for the table dtype
-    const uint32_t file_bit = P.tab_kind == FCP_TAB_BF16 ? FCP_FLAG_TABLES_BF16 : FCP_FLAG_TABLES_F16;
-    if (flags & (FCP_FLAG_TABLES_BF16 | FCP_FLAG_TABLES_F16) & ~file_bit)
+    const uint32_t file_bit = P.tab_kind == FCP_TAB_BF16 ? FCP_FLAG_TABLES_BF16 : P.tab_kind == FCP_TAB_F16 ? FCP_FLAG_TABLES_F16 : FCP_FLAG_TABLES_Q8;
+    if (flags & (FCP_FLAG_TABLES_BF16 | FCP_FLAG_TABLES_F16 | FCP_FLAG_TABLES_Q8) & ~file_bit)
       return fail(FCP_ERR_INVALID_ARGUMENT, std::string("column plan ") + path + ": flags ask for another table dtype than the file's table_dtype line");
     P.d.flags |= file_bit;
   }
@@ -1368,8 +1400,8 @@ int fcp_plan_table_bytes(const fcp_plan_t *p, int64_t *shard_bytes, int64_t *max
     if (f != FCP_FORM_GATHER && f != FCP_FORM_SEGMENT_REDUCE && f != FCP_FORM_GATHER_SCATTER) continue;
     const int64_t local_vocab =
         (hc.d.vocab - p->desc.shard_rank + p->desc.shard_world - 1) / p->desc.shard_world;
-    local[hc.d.table_input] = std::max(local[hc.d.table_input], local_vocab * hc.d.dim * p->tab_elem);
-    whole[hc.d.table_input] = std::max(whole[hc.d.table_input], hc.d.vocab * hc.d.dim * p->tab_elem);
+    local[hc.d.table_input] = std::max(local[hc.d.table_input], local_vocab * (hc.d.dim * p->tab_elem + p->tab_row_tail));
+    whole[hc.d.table_input] = std::max(whole[hc.d.table_input], hc.d.vocab * (hc.d.dim * p->tab_elem + p->tab_row_tail));
   }
   int64_t sum = 0, mx = 0;
   for (int t = 0; t < p->desc.n_device_inputs; ++t) {

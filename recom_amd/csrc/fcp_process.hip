@@ -281,7 +281,8 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
       const int64_t local_vocab = p->desc.shard_world > 1
                                       ? (hc.d.vocab - p->desc.shard_rank + p->desc.shard_world - 1) / p->desc.shard_world
                                       : hc.d.vocab;
-      if (s[0] != local_vocab || s[1] != hc.d.dim)
+      // (8-bit row-quantised tables: a row is dim codes and 8 bytes of scale and bias)
+      if (s[0] != local_vocab || s[1] != hc.d.dim + p->tab_row_tail)
         return fail(FCP_ERR_SHAPE_MISMATCH, "table shape does not match the plan");
     }
   }
@@ -348,6 +349,7 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
     ll.kernel.store(p->weighted_kernel ? (m.geo[1].grid_blocks > 0 ? FCP_LAUNCH_RAGGED_WEIGHTED : FCP_LAUNCH_NONE)
                     : (p->out_elem == 2 && fused) ? fused + (FCP_LAUNCH_DENSE_NARROW - FCP_LAUNCH_DENSE) // narrow plans: fcp_narrow.hip
                     : (p->tab_elem == 2 && fused) ? fused + (FCP_LAUNCH_DENSE_TAB16 - FCP_LAUNCH_DENSE)  // 16-bit tables: fcp_tables16.hip
+                    : (p->tab_elem == 1 && fused) ? fused + (FCP_LAUNCH_DENSE_TABQ8 - FCP_LAUNCH_DENSE)  // 8-bit tables: fcp_tables_q8.hip
                                                   : fused,
                     std::memory_order_relaxed);
     p->last_dense_front.store(m.geo[0].grid_blocks <= 0 || p->weighted_kernel ? FCP_DENSE_FRONT_NONE
@@ -436,6 +438,19 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
       e = fcp_launch_tab16(L, p->vec, true, p->tab_kind, m.geo[0].grid_blocks, stream);
     }
     if (e) return hip_fail("16-bit-table kernel launch", (hipError_t)e);
+  } else if (p->tab_elem == 1) { // 8-bit row-quantised tables: likewise
+    int e = 0;
+    if (m.geo[1].grid_blocks > 0 && m.geo[0].grid_blocks > 0) {
+      FcpLaunch Ld;
+      fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &Ld);
+      e = fcp_launch_tabq8_hybrid(Ld, m.geo[0].grid_blocks, L, m.geo[1].grid_blocks, p->vec, stream);
+    } else if (m.geo[1].grid_blocks > 0) {
+      e = fcp_launch_tabq8(L, p->vec, false, m.geo[1].grid_blocks, stream);
+    } else if (m.geo[0].grid_blocks > 0) {
+      fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &L);
+      e = fcp_launch_tabq8(L, p->vec, true, m.geo[0].grid_blocks, stream);
+    }
+    if (e) return hip_fail("8-bit-table kernel launch", (hipError_t)e);
   } else if (m.geo[1].grid_blocks > 0 && m.geo[0].grid_blocks > 0) {
     FcpLaunch Ld;
     fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &Ld);

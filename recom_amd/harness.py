@@ -61,8 +61,11 @@ class ServingHarness:
     native loop.  Inputs are already in HBM when a timed region starts."""
 
     def __init__(self, model: SynthModel, device: int = 0, n_requests: int = 16, arena_ring: int = 6,
-                 n_threads: int = 1, tables=None, spec=None, seed0: int = 0) -> None:
+                 n_threads: int = 1, tables=None, spec=None, seed0: int = 0, expected_rows=None) -> None:
+        """``expected_rows``: with ``tables=``, the closed form of what those tables hold where it is not the model's own —
+        ``expected_rows(seed, rows, dim) -> float32 [len(rows), dim]``, which ``verify_resident`` then checks against."""
         import torch
+        self.expected_rows = expected_rows
         self.torch = torch
         self.model = model
         self.dev = torch.device("cuda", device)
@@ -167,6 +170,10 @@ class ServingHarness:
         nd = {"f32": None, "bf16": torch.bfloat16, "f16": torch.float16}[spec.out_dtype]
         # 16-bit tables: the closed form rounded once to the table dtype is what the table holds (exact from there on)
         hash_rows = lambda seed, rows, dim: synth.round_to_table(synth.hash_rows(seed, rows, dim), spec.table_dtype)  # noqa: E731
+        if spec.table_dtype == "q8":   # q8 tables: their own closed form (codes, scale, bias), dequantised as the kernels do
+            hash_rows = lambda seed, rows, dim: synth.dequantize_q8(synth.q8_rows(seed, rows, dim))  # noqa: E731
+        if self.expected_rows is not None:   # caller-bound tables with a closed form of their own
+            hash_rows = self.expected_rows
 
         def fl(x):
             return x if nd is None else torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(nd).float().numpy()
@@ -216,7 +223,8 @@ class ServingHarness:
 
     def algorithmic_bytes(self) -> dict:
         """Mean algorithmic bytes per request over the resident requests; a narrow-output plan is charged
-        2 bytes per written element (``PlanSpec.algorithmic_bytes``), a plan with 16-bit tables 2 bytes per table element read."""
+        2 bytes per written element (``PlanSpec.algorithmic_bytes``), a plan with 16-bit tables 2 bytes per table element read,
+        a plan with q8 tables dim + 8 bytes per table row read."""
         acc = None
         for (blob, offsets, shapes), r in zip(self.packed, self.requests):
             b = self.spec.algorithmic_bytes(shapes, r.symbols)

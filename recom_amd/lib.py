@@ -30,10 +30,16 @@ FLAG_TABLES_BF16 = 1 << 3  # 16-bit tables: every embedding table of the plan as
 FLAG_TABLES_F16 = 1 << 4
 TABLE_DTYPES = {0: "f32", 1: "bf16", 2: "f16"}   # FCP_TAB_* (fcp_plan_table_dtype)
 TABLE_DTYPE_FLAGS = {"f32": 0, "bf16": FLAG_TABLES_BF16, "f16": FLAG_TABLES_F16}
+FLAG_TABLES_Q8 = 1 << 5    # 8-bit row-quantised tables: uint8 [vocab, dim + 8], a float32 scale and bias behind every row
+TAB_Q8 = 3                 # FCP_TAB_Q8
+# every table dtype the library knows (the two dicts above are the 16-bit feature's, these add "q8")
+ALL_TABLE_DTYPES = {**TABLE_DTYPES, TAB_Q8: "q8"}
+ALL_TABLE_DTYPE_FLAGS = {**TABLE_DTYPE_FLAGS, "q8": FLAG_TABLES_Q8}
 # fcp_launch_info_t (fcp_plan_last_launch): names of the kernel, store-policy and segment-offset codes
 LAUNCH_KERNELS = {0: "none", 1: "dense", 2: "ragged", 3: "hybrid", 4: "ragged_weighted",
                   5: "dense_narrow", 6: "ragged_narrow", 7: "hybrid_narrow",
-                  8: "dense_tab16", 9: "ragged_tab16", 10: "hybrid_tab16"}
+                  8: "dense_tab16", 9: "ragged_tab16", 10: "hybrid_tab16",
+                  11: "dense_tabq8", 12: "ragged_tabq8", 13: "hybrid_tabq8"}
 DENSE_FRONTS = {0: "none", 1: "generic", 2: "plain"}   # fcp_plan_last_dense_front
 LAUNCH_STORES = {0: "nt", 1: "sc1_nt", 4: "plain"}
 LAUNCH_SEGMENT_OFFSETS = {0: "none", 1: "prepass", 2: "search"}

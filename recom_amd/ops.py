@@ -203,7 +203,7 @@ class Plan:
         """The plan a column-plan file describes, parsed by the library itself
         (``fcp_plan_create_from_file`` — what the TF shim calls with the op's ``dlpath``).  ``out_dtype``: "bf16" / "f16"
         select narrow output for a file that does not name a dtype (the flag bits of the call); a file that names
-        another one is refused.  ``table_dtype``: the same for 16-bit tables."""
+        another one is refused.  ``table_dtype``: the same for 16-bit ("bf16" / "f16") and 8-bit row-quantised ("q8") tables."""
         import dataclasses
         from .plan_io import load_plan
         self = cls.__new__(cls)
@@ -213,7 +213,7 @@ class Plan:
         self.handle = None
         handle = C.c_void_p()
         flags = (_lib.FLAG_HOST_ONLY if host_only else 0) | _lib.OUT_DTYPE_FLAGS[out_dtype or "f32"] | \
-            _lib.TABLE_DTYPE_FLAGS[table_dtype or "f32"]
+            _lib.ALL_TABLE_DTYPE_FLAGS[table_dtype or "f32"]
         _lib.check(self._L.fcp_plan_create_from_file(path.encode(), device, flags, C.byref(handle)), "fcp_plan_create_from_file")
         self.handle = handle
         self.spec = load_plan(path)          # Python-side bookkeeping only
@@ -230,10 +230,10 @@ class Plan:
         return _lib.OUT_DTYPES[v.value]
 
     def table_dtype(self) -> str:
-        """``fcp_plan_table_dtype``: "f32", "bf16" or "f16" — the element type of every embedding table the plan reads."""
+        """``fcp_plan_table_dtype``: "f32", "bf16", "f16" or "q8" — the element type of every embedding table the plan reads."""
         v = C.c_int32()
         _lib.check(self._L.fcp_plan_table_dtype(self.handle, C.byref(v)), "fcp_plan_table_dtype")
-        return _lib.TABLE_DTYPES[v.value]
+        return _lib.ALL_TABLE_DTYPES[v.value]
 
     def table_bytes(self):
         """``fcp_plan_table_bytes``: (bytes of tables this plan reads on its device, largest table unsharded)."""
@@ -328,7 +328,7 @@ class Plan:
 
     def last_launch(self) -> dict:
         """``fcp_plan_last_launch``: what the plan's most recent request enqueued — kernel (``none`` / ``dense`` /
-        ``ragged`` / ``hybrid`` / ``ragged_weighted`` / ``dense_narrow`` / ``ragged_narrow`` / ``hybrid_narrow`` / ``dense_tab16`` / ``ragged_tab16`` / ``hybrid_tab16``), ``vec``, dense ``rows_per_wave``, ``store`` (``nt`` / ``sc1_nt`` / ``plain``),
+        ``ragged`` / ``hybrid`` / ``ragged_weighted`` / ``dense_narrow`` / ``ragged_narrow`` / ``hybrid_narrow`` / ``dense_tab16`` / ``ragged_tab16`` / ``hybrid_tab16`` / ``dense_tabq8`` / ``ragged_tabq8`` / ``hybrid_tabq8``), ``vec``, dense ``rows_per_wave``, ``store`` (``nt`` / ``sc1_nt`` / ``plain``),
         ``wide_rows``, ``shard_world``, ``dense_blocks`` / ``ragged_blocks``, ``segment_offsets`` (``none`` /
         ``prepass`` / ``search``).  Read-only diagnostics: which kernel instantiation a request reached."""
         li = _lib.LaunchInfo()
@@ -415,7 +415,12 @@ class FeatureColumnProcess:
         # the element type of the outputs as the LIBRARY holds it (a plan file, or flag bits, may have chosen it)
         self.out_dtype = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[self.plan.out_dtype()]
         # likewise the element type the bound tables must have (a wrong one would be read as garbage, or out of bounds)
-        self.table_dtype = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[self.plan.table_dtype()]
+        # (q8: torch.uint8 [vocab, dim + 8] — what quantized::embedding_bag_byte_prepack returns)
+        self.table_dtype = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "q8": torch.uint8}[self.plan.table_dtype()]
+        self._q8_shapes = {}
+        if self.plan.table_dtype() == "q8":
+            self._q8_shapes = {c.table_input: (int(c.vocab), int(c.dim) + 8) for c in self.plan.spec.columns
+                               if c.form in (FORM_GATHER, FORM_SEGMENT_REDUCE, FORM_GATHER_SCATTER)}
         self._table_inputs = sorted({c.table_input for c in self.plan.spec.columns
                                      if c.form in (FORM_GATHER, FORM_SEGMENT_REDUCE, FORM_GATHER_SCATTER)})
 
@@ -466,6 +471,9 @@ class FeatureColumnProcess:
                 if i < len(inputs) and inputs[i].dtype != self.table_dtype:
                     raise ValueError(f"FeatureColumnProcess: table {i} is {inputs[i].dtype}, the plan reads {self.table_dtype} tables "
                                      "(PlanSpec.table_dtype)")
+                if i < len(inputs) and i in self._q8_shapes and (tuple(inputs[i].shape) != self._q8_shapes[i] or not inputs[i].is_contiguous()):
+                    raise ValueError(f"FeatureColumnProcess: table {i} has shape {tuple(inputs[i].shape)}, the plan reads a contiguous "
+                                     f"torch.uint8 table of shape {self._q8_shapes[i]}: [vocab, dim + 8] (codes, float32 scale, float32 bias)")
             tptrs = (C.c_void_p * max(1, len(inputs)))(*[t.data_ptr() for t in inputs])
             tshapes = np.asarray([d for t in inputs for d in t.shape], np.int32)
             self._tab_cache = (inputs, tptrs, tshapes, len(inputs))

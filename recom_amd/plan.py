@@ -35,6 +35,8 @@ LAYOUT_CONCAT, LAYOUT_PER_COLUMN = 0, 1
 FLAG_COUNT_BAD_IDS = 1
 FLAG_OUT_BF16, FLAG_OUT_F16 = 1 << 1, 1 << 2   # narrow output (PlanSpec.out_dtype sets the bit)
 FLAG_TABLES_BF16, FLAG_TABLES_F16 = 1 << 3, 1 << 4   # 16-bit tables (PlanSpec.table_dtype sets the bit)
+FLAG_TABLES_Q8 = 1 << 5   # 8-bit row-quantised tables (PlanSpec.table_dtype "q8" sets the bit)
+Q8_ROW_TAIL = 8           # bytes behind the codes of a q8 row: float32 scale, float32 bias
 
 
 class NarrowOutputUnsupported(ValueError):
@@ -43,6 +45,10 @@ class NarrowOutputUnsupported(ValueError):
 
 class Tables16Unsupported(ValueError):
     """A plan kind the 16-bit-table kernels do not serve (the library answers FCP_ERR_UNSUPPORTED)."""
+
+
+class TablesQ8Unsupported(ValueError):
+    """A plan kind the 8-bit-table kernels do not serve (the library answers FCP_ERR_UNSUPPORTED)."""
 
 _ID_ELEM_SIZE = {IDS_I32: 4, IDS_I64: 8, IDS_F32_BUCKETIZE: 4}
 _ID_NP_DTYPE = {IDS_I32: np.int32, IDS_I64: np.int64, IDS_F32_BUCKETIZE: np.float32}
@@ -174,7 +180,9 @@ class PlanSpec:
     # every element is the float32 value rounded once, to nearest-even, at the store
     out_dtype: str = "f32"
     # element type of EVERY embedding table of the plan: "f32", or — FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16 — "bf16" /
-    # "f16": a 16-bit element widens to float32 exactly, the plan computes what the float32 plan computes on the widened tables
+    # "f16": a 16-bit element widens to float32 exactly, the plan computes what the float32 plan computes on the widened tables;
+    # or — FCP_FLAG_TABLES_Q8 — "q8": uint8 [vocab, dim + 8] rows of codes, float32 scale, float32 bias; an element is
+    # fma(code, scale, bias) rounded once, the plan computes what the float32 plan computes on the dequantised tables
     table_dtype: str = "f32"
 
     # ---- static layout facts ------------------------------------------------
@@ -205,7 +213,7 @@ class PlanSpec:
     def plan_flags(self) -> int:
         """``fcp_plan_desc_t::flags``: ``flags`` plus the bit ``out_dtype`` stands for."""
         return (self.flags | {"f32": 0, "bf16": FLAG_OUT_BF16, "f16": FLAG_OUT_F16}.get(self.out_dtype, 0)
-                | {"f32": 0, "bf16": FLAG_TABLES_BF16, "f16": FLAG_TABLES_F16}.get(self.table_dtype, 0))
+                | {"f32": 0, "bf16": FLAG_TABLES_BF16, "f16": FLAG_TABLES_F16, "q8": FLAG_TABLES_Q8}.get(self.table_dtype, 0))
 
     @property
     def out_elem_size(self) -> int:
@@ -239,15 +247,32 @@ class PlanSpec:
 
     @property
     def table_elem_size(self) -> int:
-        return 4 if self.table_dtype == "f32" else 2
+        return 1 if self.plan_flags() & FLAG_TABLES_Q8 else 4 if self.table_dtype == "f32" else 2
+
+    def table_row_bytes(self, dim: int) -> int:
+        """Bytes of one table row of ``dim`` elements: ``dim`` x the element size, plus scale and bias in a q8 table."""
+        return dim * self.table_elem_size + (Q8_ROW_TAIL if self.plan_flags() & FLAG_TABLES_Q8 else 0)
 
     def validate_table_dtype(self) -> None:
         """The library's rules for 16-bit tables (``fcp_plan_create``): one dtype, and none of the three plan kinds the
         16-bit-table kernels do not serve.  ``Tables16Unsupported`` mirrors FCP_ERR_UNSUPPORTED, ValueError
         FCP_ERR_INVALID_ARGUMENT."""
-        if self.table_dtype not in ("f32", "bf16", "f16"):
-            raise ValueError(f"table_dtype must be 'f32', 'bf16' or 'f16', not {self.table_dtype!r}")
+        if self.table_dtype not in ("f32", "bf16", "f16", "q8"):
+            raise ValueError(f"table_dtype must be 'f32', 'bf16', 'f16' or 'q8', not {self.table_dtype!r}")
         f = self.plan_flags()
+        if f & FLAG_TABLES_Q8:   # 8-bit row-quantised tables: the same rules, by their own name
+            if f & (FLAG_TABLES_BF16 | FLAG_TABLES_F16):
+                raise ValueError("FCP_FLAG_TABLES_Q8 and FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16 exclude each other")
+            if f & (FLAG_OUT_BF16 | FLAG_OUT_F16):
+                raise TablesQ8Unsupported("8-bit tables with narrow output (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16): the 8-bit-table kernels store float32")
+            if self.shard_world > 1:
+                raise TablesQ8Unsupported("8-bit tables on a row-sharded plan (shard_world > 1): the sharded kernels read float32 tables")
+            for k, c in enumerate(self.columns):
+                if c.weights_input >= 0:
+                    raise TablesQ8Unsupported(f"column {k}: 8-bit tables with per-id weights: weighted plans take the float32 weighted kernel")
+                if c.combiner == COMBINER_SQRTN and c.form == FORM_SEGMENT_REDUCE:
+                    raise TablesQ8Unsupported(f"column {k}: 8-bit tables with FCP_COMBINER_SQRTN: sqrtn plans take the float32 weighted kernel")
+            return
         if not f & (FLAG_TABLES_BF16 | FLAG_TABLES_F16):
             return
         if f & FLAG_TABLES_BF16 and f & FLAG_TABLES_F16:
@@ -444,7 +469,7 @@ class PlanSpec:
         """Algorithmic bytes of one request: table rows read + ids read + CSR
         offsets / segment ids read + bucketize boundaries + pooled output written
         once in concat layout, 2 bytes per element in a narrow-output plan; a table row read is charged ``dim * 2`` bytes in a plan
-        with 16-bit tables (+ 4 bytes per id of a weighted column: key ``weights``, present only in plans that have
+        with 16-bit tables, ``dim + 8`` in a plan with 8-bit row-quantised tables (+ 4 bytes per id of a weighted column: key ``weights``, present only in plans that have
         one).  No intermediate traffic is counted."""
         so = self.shape_offsets()
 
@@ -466,7 +491,7 @@ class PlanSpec:
                 rows_b += numel(c.ids_input) * 4
             else:
                 nnz = numel(c.ids_input)
-                rows_b += nnz * c.dim * self.table_elem_size
+                rows_b += nnz * self.table_row_bytes(c.dim)
                 ids_b += nnz * _ID_ELEM_SIZE[c.id_source]
                 if c.seg_kind == SEG_CSR_I32:
                     seg_b += (rows + 1) * 4

@@ -20,7 +20,7 @@ def save_plan(spec: PlanSpec, path: str, stage: "StageInfo | None" = None) -> No
         maps = [(k, c) for k, c in enumerate(spec.columns) if len(c.seg_mul)]
         weights = [(k, c) for k, c in enumerate(spec.columns) if c.weights_input >= 0]
         v5 = bool(weights) or any(c.combiner == COMBINER_SQRTN for c in spec.columns)
-        if spec.table_dtype != "f32":   # version 7, plans with 16-bit tables only (never narrow output as well): likewise
+        if spec.table_dtype != "f32":   # version 7, plans with 16-bit or 8-bit tables only (never narrow output as well): likewise
             f.write(f"fcp_plan 7\ntable_dtype {spec.table_dtype}\n")
         elif spec.out_dtype != "f32":   # version 6, narrow-output plans only: the dtype is the file's second line
             f.write(f"fcp_plan 6\nout_dtype {spec.out_dtype}\n")
@@ -73,11 +73,11 @@ def load_plan(path: str) -> PlanSpec:
     if version not in (1, 2, 3, 4, 5, 6, 7):
         raise ValueError("bad plan header")
     out_dtype = table_dtype = "f32"
-    if version >= 7:              # "table_dtype bf16|f16": the same place and rules, in version 7 files and no others
+    if version >= 7:              # "table_dtype bf16|f16|q8": the same place and rules, in version 7 files and no others
         if nxt() != "table_dtype":
-            raise ValueError(f"expected 'table_dtype bf16' or 'table_dtype f16' in {path}")
+            raise ValueError(f"expected 'table_dtype bf16', 'table_dtype f16' or 'table_dtype q8' in {path}")
         table_dtype = nxt()
-        if table_dtype not in ("bf16", "f16"):
+        if table_dtype not in ("bf16", "f16", "q8"):
             raise ValueError(f"unknown table_dtype {table_dtype!r} in {path}")
     elif version >= 6:            # "out_dtype bf16|f16": here and nowhere else, in version 6 files and no others
         if nxt() != "out_dtype":

@@ -110,6 +110,124 @@ def round_to_table(x: np.ndarray, table_dtype: str) -> np.ndarray:
 
 
 # ---------------------------------------------------------------------------
+# 8-bit row-quantised tables (PlanSpec.table_dtype "q8"): uint8 [vocab, dim + 8] — dim codes, a float32 scale, a float32 bias
+# ---------------------------------------------------------------------------
+def _q8_row_hash(seed: int, r: np.ndarray) -> np.ndarray:
+    return _mix(r * np.uint64(2654435761) + np.uint64(0x9E3779B9) + np.uint64((seed * 7919 + 12345) & 0xFFFFFFFF))
+
+
+def q8_rows(seed: int, rows: np.ndarray, dim: int) -> np.ndarray:
+    """uint8 [len(rows), dim + 8] = the rows ``rows`` of the q8 table ``seed``, in closed form: element e of row r has the
+    code bits 8..15 of the float32 table's hash of (r, e); the row's scale is (the low 24 bits of a row hash, made odd) *
+    2^-31, in (0, 2^-7), its bias -(the high 16 bits) * 2^-16, in (-1, 0].  Both are exact float32 values; a dequantised
+    element needs the fma's rounding (a product of up to 32 bits), and a rounded product would give another value."""
+    r = np.asarray(rows, np.int64).astype(np.uint64)[:, None]
+    e = np.arange(dim, dtype=np.uint64)[None, :]
+    u = _mix(r * np.uint64(2654435761) + e * np.uint64(40503) + np.uint64((seed * 7919 + 12345) & 0xFFFFFFFF))
+    h = _q8_row_hash(seed, r)
+    scale = (((h & np.uint64(0xFFFFFF)) | np.uint64(1)).astype(np.float32) * np.float32(2.0 ** -31)).astype("<f4")
+    bias = (-((h >> np.uint64(16)) & np.uint64(0xFFFF)).astype(np.float32) * np.float32(2.0 ** -16)).astype("<f4")
+    out = np.empty((r.shape[0], dim + 8), np.uint8)
+    out[:, :dim] = ((u >> np.uint64(8)) & np.uint64(0xFF)).astype(np.uint8)
+    out[:, dim:dim + 4] = np.ascontiguousarray(scale).view(np.uint8).reshape(-1, 4)
+    out[:, dim + 4:] = np.ascontiguousarray(bias).view(np.uint8).reshape(-1, 4)
+    return out
+
+
+def q8_table_numpy(seed: int, vocab: int, dim: int) -> np.ndarray:
+    return q8_rows(seed, np.arange(vocab, dtype=np.int64), dim)
+
+
+def q8_table_torch(seed: int, vocab: int, dim: int, device):
+    """The same table on a torch device (int64 arithmetic, exact), built in chunks."""
+    import torch
+    out = torch.empty((vocab, dim + 8), dtype=torch.uint8, device=device)
+    chunk = max(1, (1 << 24) // max(dim, 1))
+    e = torch.arange(dim, device=device, dtype=torch.int64)[None, :]
+    M = 0xFFFFFFFF
+    base = (seed * 7919 + 12345) & M
+
+    def mix(u):
+        u = u & M
+        u = u ^ (u >> 15)
+        u = (u * 0x2C1B3C6D) & M
+        u = u ^ (u >> 12)
+        u = (u * 0x297A2D39) & M
+        return u ^ (u >> 15)
+
+    for s in range(0, vocab, chunk):
+        m = min(chunk, vocab - s)
+        r = torch.arange(s, s + m, device=device, dtype=torch.int64)[:, None]
+        # (r * 2654435761 stays below 2^63 for every row index the library takes: r < 2^32)
+        u = mix(r * 2654435761 + e * 40503 + base)
+        h = mix(r * 2654435761 + 0x9E3779B9 + base)
+        scale = (((h & 0xFFFFFF) | 1).to(torch.float32) * (2.0 ** -31)).contiguous()
+        bias = (-((h >> 16) & 0xFFFF).to(torch.float32) * (2.0 ** -16)).contiguous()
+        out[s:s + m, :dim] = ((u >> 8) & 0xFF).to(torch.uint8)
+        out[s:s + m, dim:dim + 4] = scale.view(torch.uint8).reshape(m, 4)
+        out[s:s + m, dim + 4:] = bias.view(torch.uint8).reshape(m, 4)
+    return out
+
+
+def q8_fields(table: np.ndarray):
+    """(codes uint8 [vocab, dim], scale float32 [vocab], bias float32 [vocab]) of a q8 table uint8 [vocab, dim + 8]."""
+    t = np.ascontiguousarray(table, np.uint8)
+    dim = t.shape[1] - 8
+    tail = np.ascontiguousarray(t[:, dim:])
+    return t[:, :dim], tail[:, :4].copy().view("<f4")[:, 0], tail[:, 4:].copy().view("<f4")[:, 0]
+
+
+def fma_f32(code: np.ndarray, scale: np.ndarray, bias: np.ndarray) -> np.ndarray:
+    """float32 fma(code, scale, bias) for integer codes 0..255, elementwise with broadcasting: the exact product plus the
+    bias, rounded ONCE to nearest-even.  The product is exact in float64 (8 x 24 bits).  The float64 sum is rounded to ODD
+    (its error term is known exactly — TwoSum — and where the sum is inexact and its last bit even, the neighbour on the
+    error's side is taken): a 53-bit round-to-odd value rounds to 24 bits exactly as the infinitely precise sum does, so the
+    final cast cannot round twice.  NaN and infinity follow IEEE through the float64 operations and the cast."""
+    with np.errstate(all="ignore"):
+        p = np.asarray(code, np.float64) * np.asarray(scale, np.float32).astype(np.float64)
+        b = np.broadcast_to(np.asarray(bias, np.float32).astype(np.float64), p.shape)
+        s = p + b
+        bb = s - p
+        err = (p - (s - bb)) + (b - bb)
+        bits = np.ascontiguousarray(s).view(np.int64).copy()
+        fix = np.isfinite(s) & np.isfinite(err) & (err != 0) & ((bits & 1) == 0)
+        away = (err > 0) == (s > 0)                      # the exact sum lies beyond s in magnitude
+        bits = np.where(fix, np.where(away, bits + 1, bits - 1), bits)
+        return bits.view(np.float64).astype(np.float32)
+
+
+def dequantize_q8_torch(table):
+    """``dequantize_q8`` on a torch device, in chunks: float32 [vocab, dim] of a torch.uint8 [vocab, dim + 8] table — the same
+    arithmetic (exact float64 product, float64 sum rounded to odd, one cast)."""
+    import torch
+    vocab, dim = table.shape[0], table.shape[1] - 8
+    out = torch.empty((vocab, dim), dtype=torch.float32, device=table.device)
+    chunk = max(1, (1 << 23) // max(dim, 1))
+    for s0 in range(0, vocab, chunk):
+        t = table[s0:s0 + chunk]
+        tail = t[:, dim:].contiguous()
+        scale = tail[:, :4].contiguous().view(torch.float32).double()
+        bias = tail[:, 4:].contiguous().view(torch.float32).double().expand(-1, dim)
+        p = t[:, :dim].double() * scale
+        s = p + bias
+        bb = s - p
+        err = (p - (s - bb)) + (bias - bb)
+        bits = s.contiguous().view(torch.int64)
+        fix = torch.isfinite(s) & torch.isfinite(err) & (err != 0) & ((bits & 1) == 0)
+        away = (err > 0) == (s > 0)
+        bits = torch.where(fix, torch.where(away, bits + 1, bits - 1), bits)
+        out[s0:s0 + chunk] = bits.view(torch.float64).float()
+    return out
+
+
+def dequantize_q8(table: np.ndarray) -> np.ndarray:
+    """float32 [vocab, dim]: the values a plan with q8 tables reads from ``table`` (uint8 [vocab, dim + 8]) — element by
+    element fma(float(code), scale, bias), rounded once (``fma_f32``)."""
+    codes, scale, bias = q8_fields(table)
+    return fma_f32(codes, scale[:, None], bias[:, None])
+
+
+# ---------------------------------------------------------------------------
 @dataclass
 class TableSpec:
     vocab: int
@@ -134,8 +252,11 @@ class SynthModel:
     description: str = ""
 
     def numpy_tables(self) -> List[np.ndarray]:
-        """float32 tables; uint16 bit patterns for a plan with 16-bit tables (``spec.table_dtype``)."""
+        """float32 tables; uint16 bit patterns for a plan with 16-bit tables (``spec.table_dtype``); uint8 [vocab, dim + 8]
+        rows for a plan with q8 tables (their own closed form, ``q8_rows``)."""
         dt = self.spec.table_dtype
+        if dt == "q8":
+            return [q8_table_numpy(t.seed, t.vocab, t.dim) for t in self.tables]
         tabs = [hash_table_numpy(t.seed, t.vocab, t.dim) for t in self.tables]
         return tabs if dt == "f32" else [table_patterns(t, dt) for t in tabs]
 
@@ -143,6 +264,8 @@ class SynthModel:
         """The tables on a torch device, in the plan's table dtype (torch's cast rounds to nearest-even, as
         ``table_patterns`` does); converted one table at a time, so a 16-bit model never holds its float32 form whole."""
         import torch
+        if self.spec.table_dtype == "q8":   # (never sharded: such plans are refused)
+            return [q8_table_torch(t.seed, t.vocab, t.dim, device) for t in self.tables]
         td = {"f32": None, "bf16": torch.bfloat16, "f16": torch.float16}[self.spec.table_dtype]
         out = []
         for t in self.tables:
@@ -151,7 +274,7 @@ class SynthModel:
         return out
 
     def table_bytes(self) -> int:
-        return sum(t.vocab * t.dim * self.spec.table_elem_size for t in self.tables)
+        return sum(t.vocab * self.spec.table_row_bytes(t.dim) for t in self.tables)
 
 
 def submodel(model: SynthModel, keep: Sequence[int], name: Optional[str] = None) -> SynthModel:
@@ -333,7 +456,7 @@ def _finish(name: str, b: _Builder, batch: int, n_groups: int = 1, n_symbols: in
     spec = b.spec(n_groups, n_symbols)
     if out_dtype != "f32":   # narrow output: the concat groups as bf16 / fp16
         spec = spec.with_out_dtype(out_dtype)
-    if table_dtype != "f32":   # 16-bit tables: numpy_tables / torch_tables then produce 16-bit patterns
+    if table_dtype != "f32":   # 16-bit / q8 tables: numpy_tables / torch_tables then produce 16-bit patterns / q8 rows
         spec = spec.with_table_dtype(table_dtype)
     spec.validate()
     gens = list(b.gens)
