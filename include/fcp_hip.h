@@ -209,8 +209,8 @@ enum {
    * dequantised float32 tables: gathers, scatters, pooled sums and means in id order from +0.0, range checks, the +0.0 rows
    * of ids outside the vocabulary.  Everything else is unchanged — the geometry, the float32 output, the blob (PASSTHROUGH /
    * BATCH_COL_REDUCTION payloads stay float32), both layouts, every id source and transform, FCP_FLAG_COUNT_BAD_IDS,
-   * 2^32 - 3 rows per table; fcp_plan_table_bytes counts vocab * (dim + 8).  The library does not quantise: it reads what it
-   * is given.  Together with FCP_FLAG_TABLES_BF16 / _F16: FCP_ERR_INVALID_ARGUMENT.  Refused with FCP_ERR_UNSUPPORTED:
+   * 2^32 - 3 rows per table; fcp_plan_table_bytes counts vocab * (dim + 8).  Plans do not quantise: they read what they
+   * are given; fcp_table_convert does, once, at load time.  Together with FCP_FLAG_TABLES_BF16 / _F16: FCP_ERR_INVALID_ARGUMENT.  Refused with FCP_ERR_UNSUPPORTED:
    * together with FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16, shard_world > 1, any column with per-id weights or
    * FCP_COMBINER_SQRTN. */
   FCP_FLAG_TABLES_Q8 = 1u << 5
@@ -424,6 +424,48 @@ int fcp_plan_table_dtype(const fcp_plan_t *plan, int32_t *out);
  * row-quantised tables. */
 int fcp_plan_table_bytes(const fcp_plan_t *plan, int64_t *shard_bytes,
                          int64_t *max_table_bytes_unsharded);
+
+/* ---- table conversion: writing the formats the plans read, on the device, at load time ---------------------------------- */
+/* Bytes of one row of a table of `kind` (FCP_TAB_*) and width `dim`: 4 * dim | 2 * dim | 2 * dim | dim + 8 for
+ * FCP_TAB_F32 | _BF16 | _F16 | _Q8; -1 for any other kind or dim <= 0.  Rows lie back to back in every format. */
+int64_t fcp_table_row_bytes(int32_t kind, int32_t dim);
+/* Convert `rows` rows of width `dim` between float32 and one of the compact table formats, in either direction.  `src` points
+ * at the FIRST of the rows, in format src_kind; `dst` is the BASE of the destination table in format dst_kind, and the rows
+ * are written at row index dst_row0 .. dst_row0 + rows - 1 (byte offset dst_row0 * fcp_table_row_bytes(dst_kind, dim), formed
+ * in 64 bits).  dst_row0 lets a loader stream a checkpoint through a bounce buffer into the full compact table without forming
+ * destination pointers itself: a q8 row is dim + 8 bytes, and most row addresses of a q8 table are not 4-byte aligned.
+ * Device to device on `device`, asynchronous on `stream` (a hipStream_t), no allocation, no synchronisation; a plan — or any
+ * other work — on the same stream sees the result.  Plans do not quantise; this entry does, once, at load time.
+ *
+ * Exactly one of the two kinds is FCP_TAB_F32.  Value model, so that a plan on the converted tables can be predicted bit for
+ * bit:
+ *   float32 -> q8    exactly the row quantized::embedding_bag_byte_prepack writes.  For a row x[0 .. dim) of finite values,
+ *                    all in float32, every operation rounded once (nothing contracted): mn = min(x), mx = max(x), R = mx - mn,
+ *                    scale = R / 255.0f, inv = 255.0f / (R + 1e-8f), code[i] = rint((x[i] - mn) * inv) with ties to even,
+ *                    stored as a uint8; the row is the dim codes, then scale, then mn (the bias), little-endian float32.  A
+ *                    constant row (R = 0) has scale 0 and codes 0.  For R > 0 the dequantised element lies within
+ *                    0.5 * scale + 1e-8 + 2^-22 * max(|mn|, |mx|) of x[i].  UNSPECIFIED (but never a fault): a row with a
+ *                    NaN or an infinity, a row whose R overflows float32, the sign of a zero mn in a row that holds zeros
+ *                    of both signs.
+ *   q8 -> float32    fma(float(code), scale, bias), rounded once: the value the plans read (FCP_FLAG_TABLES_Q8).
+ *   float32 -> bf16 / fp16   fl16(x) of FCP_FLAG_OUT_BF16 / _F16: nearest-even, rounded once; overflow goes to +-inf,
+ *                    underflow is gradual, -0.0 stays -0.0, NaN stays NaN (sign and payload unspecified).
+ *   bf16 / fp16 -> float32   the exact widening of FCP_FLAG_TABLES_BF16 / _F16.
+ * Alignment is the plan's for the same table.  With V the largest of 4 | 2 | 1 that divides dim: a float32 base is
+ * 4 * V-byte aligned, a bf16 / fp16 base 2 * V-byte aligned, a q8 base 4-byte aligned; `src` obeys the rule of its own kind.
+ * dst_row0 + rows stays below 2^32 - 3, the row limit of a plan's table.  The rows read and the rows written must NOT overlap;
+ * this is not checked.
+ *
+ * Status, decided in this order (the first four need no device):
+ *   FCP_ERR_INVALID_ARGUMENT  rows < 0, dst_row0 < 0, dim <= 0, a kind that is no FCP_TAB_* value, a null pointer with
+ *                             rows > 0, dst_row0 + rows beyond the row limit, a misaligned dst or src, dst_kind == src_kind
+ *                             (both float32, or the same compact format twice); fcp_last_error names the argument;
+ *   FCP_ERR_UNSUPPORTED       two different compact formats (bf16 <-> fp16, 16-bit <-> q8): convert through float32;
+ *   FCP_OK                    rows == 0: nothing is launched and no device is touched;
+ *   FCP_ERR_NO_DEVICE         no usable gfx950 device;
+ *   FCP_ERR_HIP               a kernel launch failed. */
+int fcp_table_convert(void *dst, int32_t dst_kind, int64_t dst_row0, const void *src, int32_t src_kind, int64_t rows,
+                      int32_t dim, int32_t device, void *stream);
 /* ---- placement gate (replaces check_table_size, cuda_emitter.cc:1080-1094) -------- */
 /* The reference keeps a column on the CPU when its table exceeds max_table_size =
  * 256 MiB (fc_optimize_pass.cc:71, RECOM_CPU_GPU_CO_RUN).  On MI355X the question is

@@ -1,0 +1,268 @@
+// fcp_convert.hip — fcp_table_convert / fcp_table_row_bytes: the formats the plans READ (FCP_FLAG_TABLES_BF16 / _F16 / _Q8),
+// WRITTEN on the device, once, at load time, from the float32 table a checkpoint holds — and back.  Plans do not quantise;
+// this does.  The reference reads float32 tables only and has no counterpart.
+//
+// Four directions, one of the two kinds always float32:
+//   float32 -> q8     fcp_quantize_q8_kernel<V, G>: the real kernel.  Bit for bit what quantized::embedding_bag_byte_prepack
+//                     writes (fcp_hip.h spells the arithmetic out).  A row is handled by a power-of-two group of G <= 64
+//                     lanes, every lane owning V-element slots (V = 4 | 2 | 1, as on the read side): dim 64 is 16 lanes x
+//                     global_load_dwordx4 and four rows per wave, dims <= 4 are one row per lane.  The row stays in registers
+//                     between the min / max pass and the encode pass — up to kQSlots slots per lane, dim <= 64 * kQSlots * V;
+//                     what lies beyond is read a second time.  The group's min and max are __shfl_xor butterflies (no LDS);
+//                     min and max are order-free, so the lane layout cannot change a bit.  Codes leave V bytes at a time
+//                     (dword | ushort | ubyte), scale and bias as one pair at the alignment the format allows (Q8Pair<V>),
+//                     from the group's first lane.  Reads 4 * dim, writes dim + 8 bytes per row: memory-bound.
+//   q8 -> float32     ld_q8<V> of the read side: one v_fma_f32 per element.
+//   float32 -> 16     st_out_narrow<V> of the narrow-output store: fl16, rounded once.
+//   16 -> float32     widen16<V> of the 16-bit table loaders: exact.
+// The last three are streaming kernels, one slot per lane.  The host chunks every direction into launches of at most 2^30
+// threads, so an in-launch index fits 32 bits; byte offsets are formed in 64 bits.
+//
+// No scratch, no LDS; the default modes of the other units (denormals kept, IEEE).  Contraction is off from here to the end of
+// the file: every operation of the quantiser rounds once, by itself.  The divisions are the correctly rounded ones.
+#include "fcp_fused_bodies.h"
+#include "fcp_host.h"
+
+#pragma clang fp contract(off)
+
+static_assert(FCP_TAB_BF16 == FCP_OUT_BF16 && FCP_TAB_F16 == FCP_OUT_F16, "st_out_narrow takes the table kind as its output kind");
+
+namespace {
+
+constexpr int kQSlots = 4;                          // slots of a row a lane of a 64-lane group keeps in registers
+constexpr int64_t kMaxLaunchThreads = 1ll << 30;    // per launch: in-launch indices fit 32 bits, grid x block < 2^32
+
+template <int V> __device__ __forceinline__ VF<V> ld_f32(const float *p) {
+  typedef typename VecType<V>::T T;
+  const T t = *as_global(reinterpret_cast<const T *>(p));
+  VF<V> r;
+  __builtin_memcpy(&r, &t, sizeof(T));
+  return r;
+}
+template <int V> __device__ __forceinline__ void st_f32(float *p, const VF<V> &v) {
+  typedef typename VecType<V>::T T;
+  T t;
+  __builtin_memcpy(&t, &v, sizeof(T));
+  *as_global(reinterpret_cast<T *>(p)) = t;
+}
+
+template <int V> __device__ __forceinline__ void minmax(const VF<V> &x, float &mn, float &mx) {
+#pragma unroll
+  for (int i = 0; i < V; ++i) {
+    mn = fminf(mn, x.v[i]);
+    mx = fmaxf(mx, x.v[i]);
+  }
+}
+
+// rint((x - mn) * inv), round-half-even (v_rndne_f32), each operation rounded once; element i in byte i
+template <int V> __device__ __forceinline__ void st_codes(char *p, const VF<V> &x, float mn, float inv) {
+  uint32_t c = 0;
+#pragma unroll
+  for (int i = 0; i < V; ++i) {
+    const float d = x.v[i] - mn;
+    const float q = __builtin_rintf(d * inv);
+    c |= ((uint32_t)(int32_t)q & 0xFFu) << (8 * i);
+  }
+  *as_global(reinterpret_cast<typename Q8Codes<V>::T *>(p)) = (typename Q8Codes<V>::T)c;
+}
+
+// dst / src: the first row of this launch; rows: of this launch (< 2^30).  Block = 256 / G rows; a group never straddles a
+// wave, and it is live or not as a whole — lanes of rows beyond the end take part in the butterflies and touch no memory.
+template <int V, int G>
+__global__ void __launch_bounds__(FCP_BLOCK_THREADS) fcp_quantize_q8_kernel(char *dst, const float *src, int32_t rows, int32_t dim) {
+  constexpr int S = G == 64 ? kQSlots : (G == 1 ? 3 : 1); // G == 1: dim 3 is three one-element slots of one lane
+  const int tid = threadIdx.x;
+  const int lane = tid & (G - 1);
+  const int64_t row = (int64_t)blockIdx.x * (FCP_BLOCK_THREADS / G) + tid / G;
+  const bool live = row < rows;
+  const int nslots = dim / V;
+  const float *srow = src + row * dim;
+  char *drow = dst + row * ((int64_t)dim + 8);
+
+  VF<V> x[S];
+  float mn = __builtin_inff(), mx = -__builtin_inff();
+#pragma unroll
+  for (int k = 0; k < S; ++k) {
+    x[k] = vzero<V>();
+    const int slot = lane + k * G;
+    if (live && slot < nslots) {
+      x[k] = ld_f32<V>(srow + (int64_t)slot * V);
+      minmax<V>(x[k], mn, mx);
+    }
+  }
+  if constexpr (G == 64) {
+    if (live)
+      for (int slot = lane + S * G; slot < nslots; slot += G) {
+        const VF<V> t = ld_f32<V>(srow + (int64_t)slot * V);
+        minmax<V>(t, mn, mx);
+      }
+  }
+#pragma unroll
+  for (int m = G / 2; m >= 1; m >>= 1) {
+    mn = fminf(mn, __shfl_xor(mn, m, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, m, 64));
+  }
+  const float range = mx - mn;
+  const float scale = range / 255.0f;
+  const float inv = 255.0f / (range + 1e-8f);
+  if (!live) return;
+#pragma unroll
+  for (int k = 0; k < S; ++k) {
+    const int slot = lane + k * G;
+    if (slot < nslots) st_codes<V>(drow + (int64_t)slot * V, x[k], mn, inv);
+  }
+  if constexpr (G == 64) {
+    for (int slot = lane + S * G; slot < nslots; slot += G) // beyond the register cap: the row's tail is read again
+      st_codes<V>(drow + (int64_t)slot * V, ld_f32<V>(srow + (int64_t)slot * V), mn, inv);
+  }
+  if (lane == 0) {
+    const uint64_t pair = (uint64_t)__float_as_uint(scale) | ((uint64_t)__float_as_uint(mn) << 32);
+    *(FCP_GLOBAL typename Q8Pair<V>::T *)(drow + dim) = pair;
+  }
+}
+
+// n: slots of this launch (<= 2^30); src: the first row, its stride dim + 8 bytes; spr: slots per row, dim / V
+template <int V>
+__global__ void __launch_bounds__(FCP_BLOCK_THREADS) fcp_dequantize_q8_kernel(float *dst, const char *src, uint32_t n, uint32_t spr, int32_t dim) {
+  const uint32_t i = blockIdx.x * FCP_BLOCK_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t r = i / spr;
+  const uint32_t e = (i - r * spr) * V;
+  const char *row = src + (uint64_t)r * ((uint64_t)dim + 8);
+  st_f32<V>(dst + (uint64_t)i * V, ld_q8<V>(row + e, row + dim));
+}
+
+template <int V>
+__global__ void __launch_bounds__(FCP_BLOCK_THREADS) fcp_narrow16_kernel(char *dst, const float *src, uint32_t n, int32_t kind) {
+  const uint32_t i = blockIdx.x * FCP_BLOCK_THREADS + threadIdx.x;
+  if (i >= n) return;
+  st_out_narrow<V>(dst + (uint64_t)i * (2 * V), ld_f32<V>(src + (uint64_t)i * V), FCP_ST_PLAIN, kind);
+}
+
+template <int V>
+__global__ void __launch_bounds__(FCP_BLOCK_THREADS) fcp_widen16_kernel(float *dst, const char *src, uint32_t n, int32_t kind) {
+  const uint32_t i = blockIdx.x * FCP_BLOCK_THREADS + threadIdx.x;
+  if (i >= n) return;
+  typedef typename NarrowType<V>::T T;
+  const T t = *as_global(reinterpret_cast<const T *>(src + (uint64_t)i * (2 * V)));
+  st_f32<V>(dst + (uint64_t)i * V, widen16<V>(t, kind));
+}
+
+inline dim3 blocks_for(int64_t threads) { return dim3((uint32_t)((threads + FCP_BLOCK_THREADS - 1) / FCP_BLOCK_THREADS)); }
+
+template <int V, int G> void quantize_rows(char *dst, const float *src, int64_t rows, int dim, hipStream_t s) {
+  const int64_t per_launch = kMaxLaunchThreads / G;
+  for (int64_t r0 = 0; r0 < rows; r0 += per_launch) {
+    const int64_t n = std::min(rows - r0, per_launch);
+    hipLaunchKernelGGL((fcp_quantize_q8_kernel<V, G>), blocks_for(n * G), dim3(FCP_BLOCK_THREADS), 0, s,
+                       dst + r0 * ((int64_t)dim + 8), src + r0 * dim, (int32_t)n, (int32_t)dim);
+  }
+}
+
+// G: 1 for dims <= 4, else the power of two that holds the row's slots, at most 64
+template <int V> void quantize(char *dst, const float *src, int64_t rows, int dim, hipStream_t s) {
+  const int nslots = dim / V;
+  int g = 1;
+  if (dim > 4)
+    while (g < nslots && g < 64) g <<= 1;
+  switch (g) {
+  case 1: quantize_rows<V, 1>(dst, src, rows, dim, s); break;
+  case 2: quantize_rows<V, 2>(dst, src, rows, dim, s); break;
+  case 4: quantize_rows<V, 4>(dst, src, rows, dim, s); break;
+  case 8: quantize_rows<V, 8>(dst, src, rows, dim, s); break;
+  case 16: quantize_rows<V, 16>(dst, src, rows, dim, s); break;
+  case 32: quantize_rows<V, 32>(dst, src, rows, dim, s); break;
+  default: quantize_rows<V, 64>(dst, src, rows, dim, s); break;
+  }
+}
+
+template <int V> void dequantize(float *dst, const char *src, int64_t rows, int dim, hipStream_t s) {
+  const int64_t spr = dim / V;
+  const int64_t per_launch = std::max<int64_t>(1, kMaxLaunchThreads / spr); // (one row of 2^31 - 1 elements: 2^31 threads)
+  for (int64_t r0 = 0; r0 < rows; r0 += per_launch) {
+    const int64_t n = std::min(rows - r0, per_launch) * spr;
+    hipLaunchKernelGGL(fcp_dequantize_q8_kernel<V>, blocks_for(n), dim3(FCP_BLOCK_THREADS), 0, s, dst + r0 * dim,
+                       src + r0 * ((int64_t)dim + 8), (uint32_t)n, (uint32_t)spr, (int32_t)dim);
+  }
+}
+
+// the 16-bit directions: the rows are one contiguous run of rows * dim / V slots on both sides
+template <int V> void stream16(void *dst, const void *src, int64_t slots, bool narrow, int kind, hipStream_t s) {
+  for (int64_t i0 = 0; i0 < slots; i0 += kMaxLaunchThreads) {
+    const int64_t n = std::min(slots - i0, kMaxLaunchThreads);
+    if (narrow)
+      hipLaunchKernelGGL(fcp_narrow16_kernel<V>, blocks_for(n), dim3(FCP_BLOCK_THREADS), 0, s, static_cast<char *>(dst) + i0 * 2 * V,
+                         static_cast<const float *>(src) + i0 * V, (uint32_t)n, (int32_t)kind);
+    else
+      hipLaunchKernelGGL(fcp_widen16_kernel<V>, blocks_for(n), dim3(FCP_BLOCK_THREADS), 0, s, static_cast<float *>(dst) + i0 * V,
+                         static_cast<const char *>(src) + i0 * 2 * V, (uint32_t)n, (int32_t)kind);
+  }
+}
+
+template <int V> void convert(void *dst, int dst_kind, const void *src, int src_kind, int64_t rows, int dim, hipStream_t s) {
+  if (dst_kind == FCP_TAB_Q8)
+    quantize<V>(static_cast<char *>(dst), static_cast<const float *>(src), rows, dim, s);
+  else if (src_kind == FCP_TAB_Q8)
+    dequantize<V>(static_cast<float *>(dst), static_cast<const char *>(src), rows, dim, s);
+  else
+    stream16<V>(dst, src, rows * (dim / V), src_kind == FCP_TAB_F32, src_kind == FCP_TAB_F32 ? dst_kind : src_kind, s);
+}
+
+bool known_kind(int32_t k) { return k == FCP_TAB_F32 || k == FCP_TAB_BF16 || k == FCP_TAB_F16 || k == FCP_TAB_Q8; }
+int vec_of(int32_t dim) { return dim % 4 == 0 ? 4 : dim % 2 == 0 ? 2 : 1; }
+// the base alignment of a table of `kind`: what a plan asks of the same table
+int base_alignment(int32_t kind, int vec) { return kind == FCP_TAB_F32 ? 4 * vec : kind == FCP_TAB_Q8 ? 4 : 2 * vec; }
+const char *kind_name(int32_t k) { return k == FCP_TAB_F32 ? "float32" : k == FCP_TAB_BF16 ? "bf16" : k == FCP_TAB_F16 ? "fp16" : "q8"; }
+
+} // namespace
+
+extern "C" int64_t fcp_table_row_bytes(int32_t kind, int32_t dim) {
+  if (dim <= 0) return -1;
+  switch (kind) {
+  case FCP_TAB_F32: return 4 * (int64_t)dim;
+  case FCP_TAB_BF16:
+  case FCP_TAB_F16: return 2 * (int64_t)dim;
+  case FCP_TAB_Q8: return (int64_t)dim + 8;
+  default: return -1;
+  }
+}
+
+extern "C" int fcp_table_convert(void *dst, int32_t dst_kind, int64_t dst_row0, const void *src, int32_t src_kind, int64_t rows,
+                                 int32_t dim, int32_t device, void *stream) {
+  if (rows < 0) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: rows is negative");
+  if (dst_row0 < 0) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: dst_row0 is negative");
+  if (dim <= 0) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: dim must be positive");
+  if (!known_kind(dst_kind)) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: dst_kind is no FCP_TAB_* value");
+  if (!known_kind(src_kind)) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: src_kind is no FCP_TAB_* value");
+  if (rows > 0 && !dst) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: dst is null");
+  if (rows > 0 && !src) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: src is null");
+  if (rows + dst_row0 >= (1ll << 32) - 3 || rows >= (1ll << 32) - 3)
+    return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: dst_row0 + rows must stay below 2^32 - 3, a plan's row limit");
+  const int vec = vec_of(dim);
+  if ((uintptr_t)dst % base_alignment(dst_kind, vec))
+    return fail(FCP_ERR_INVALID_ARGUMENT, std::string("fcp_table_convert: dst is not ") + std::to_string(base_alignment(dst_kind, vec)) +
+                                              "-byte aligned (a " + kind_name(dst_kind) + " table of this dim)");
+  if ((uintptr_t)src % base_alignment(src_kind, vec))
+    return fail(FCP_ERR_INVALID_ARGUMENT, std::string("fcp_table_convert: src is not ") + std::to_string(base_alignment(src_kind, vec)) +
+                                              "-byte aligned (a " + kind_name(src_kind) + " table of this dim)");
+  if (dst_kind == src_kind)
+    return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: dst_kind equals src_kind; exactly one of the two is FCP_TAB_F32");
+  if (dst_kind != FCP_TAB_F32 && src_kind != FCP_TAB_F32)
+    return fail(FCP_ERR_UNSUPPORTED, std::string("fcp_table_convert: ") + kind_name(src_kind) + " -> " + kind_name(dst_kind) +
+                                         " is not implemented; convert through float32");
+  if (rows == 0) return FCP_OK;
+  DeviceGuard guard;
+  const int rc = guard.enter(device);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  void *first = static_cast<char *>(dst) + dst_row0 * fcp_table_row_bytes(dst_kind, dim);
+  if (vec == 4)
+    convert<4>(first, dst_kind, src, src_kind, rows, dim, s);
+  else if (vec == 2)
+    convert<2>(first, dst_kind, src, src_kind, rows, dim, s);
+  else
+    convert<1>(first, dst_kind, src, src_kind, rows, dim, s);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail("fcp_table_convert: kernel launch", e);
+  return FCP_OK;
+}

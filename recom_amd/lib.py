@@ -35,6 +35,7 @@ TAB_Q8 = 3                 # FCP_TAB_Q8
 # every table dtype the library knows (the two dicts above are the 16-bit feature's, these add "q8")
 ALL_TABLE_DTYPES = {**TABLE_DTYPES, TAB_Q8: "q8"}
 ALL_TABLE_DTYPE_FLAGS = {**TABLE_DTYPE_FLAGS, "q8": FLAG_TABLES_Q8}
+TABLE_KINDS = {name: kind for kind, name in ALL_TABLE_DTYPES.items()}   # name -> FCP_TAB_* (fcp_table_convert)
 # fcp_launch_info_t (fcp_plan_last_launch): names of the kernel, store-policy and segment-offset codes
 LAUNCH_KERNELS = {0: "none", 1: "dense", 2: "ragged", 3: "hybrid", 4: "ragged_weighted",
                   5: "dense_narrow", 6: "ragged_narrow", 7: "hybrid_narrow",
@@ -165,6 +166,7 @@ EXPORTS = [
     "fcp_plan_probe_private_streams", "fcp_plan_private_streams_verdict", "fcp_plan_verify_private_streams",
     "fcp_plan_private_streams_stats", "fcp_plan_last_launch", "fcp_plan_last_csr", "fcp_aux_launch_counts",
     "fcp_plan_out_dtype", "fcp_plan_last_dense_front", "fcp_plan_table_dtype",
+    "fcp_table_row_bytes", "fcp_table_convert",
 ]
 
 _lib = None
@@ -313,6 +315,11 @@ def load() -> C.CDLL:
         L.fcp_aux_launch_counts.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     if hasattr(L, "fcp_plan_last_dense_front"):
         L.fcp_plan_last_dense_front.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    if hasattr(L, "fcp_table_convert"):
+        L.fcp_table_row_bytes.restype = C.c_int64
+        L.fcp_table_row_bytes.argtypes = [C.c_int32, C.c_int32]
+        L.fcp_table_convert.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                        C.c_void_p]
     if L.fcp_abi_version() != FCP_ABI_VERSION:
         raise ImportError("libfcp_hip.so ABI version mismatch; rebuild")
     _lib = L

@@ -227,6 +227,28 @@ def dequantize_q8(table: np.ndarray) -> np.ndarray:
     return fma_f32(codes, scale[:, None], bias[:, None])
 
 
+def quantize_q8(x: np.ndarray) -> np.ndarray:
+    """uint8 [rows, dim + 8]: the q8 rows ``fcp_table_convert`` (and ``quantized::embedding_bag_byte_prepack``) writes for the
+    float32 rows ``x`` [rows, dim], restated in NumPy: per row, all in float32 with every operation rounded once,
+    mn = min, mx = max, R = mx - mn, scale = R / 255, inv = 255 / (R + 1e-8), code = rint((x - mn) * inv) with ties to even;
+    the codes, then scale, then mn (the bias).  Rows are finite and R does not overflow (anything else is unspecified)."""
+    x = np.ascontiguousarray(x, np.float32)
+    rows, dim = x.shape
+    with np.errstate(all="ignore"):
+        mn = x.min(axis=1)
+        mx = x.max(axis=1)
+        rng = (mx - mn).astype(np.float32)
+        scale = (rng / np.float32(255.0)).astype(np.float32)
+        inv = (np.float32(255.0) / (rng + np.float32(1e-8)).astype(np.float32)).astype(np.float32)
+        d = (x - mn[:, None]).astype(np.float32)
+        q = np.rint((d * inv[:, None]).astype(np.float32))
+    out = np.empty((rows, dim + 8), np.uint8)
+    out[:, :dim] = q.astype(np.int64).astype(np.uint8)
+    out[:, dim:dim + 4] = np.ascontiguousarray(scale, "<f4").view(np.uint8).reshape(rows, 4)
+    out[:, dim + 4:] = np.ascontiguousarray(mn, "<f4").view(np.uint8).reshape(rows, 4)
+    return out
+
+
 # ---------------------------------------------------------------------------
 @dataclass
 class TableSpec:
