@@ -8,6 +8,7 @@
 //
 //   fcp_bench [--columns 1000] [--batch 512] [--vocab 1000000] [--steps 300]
 //             [--warmup 50] [--threads 1] [--requests 16] [--ring 6] [--verify 1]
+//   fcp_bench --mix-probe 1|2 [--steps 300] [--warmup 50]   the dense kernel's loads and stores without a front
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,6 +24,7 @@
 #include <vector>
 
 #include "../../include/fcp_hip.h"
+#include "fcp_fused_bodies.h" // (--mix-probe: the product's table loads and its three output stores)
 #include "numa_util.h"
 
 struct fcp_harness;
@@ -72,6 +74,47 @@ __global__ void fill_table(float *t, uint32_t seed, uint64_t vocab, uint32_t dim
     t[i] = hash_elem(seed, i / dim, (uint32_t)(i % dim));
 }
 
+// --mix-probe: the access mix of fcp_dense_kernel_plain<4> with no front at all.  Grid, block mapping, the four table
+// loads and then four output stores of a lane are the product's; what the product works out in its front — the lane's
+// table address and the pre-scaled slot offsets of its four rows — is read from two precomputed arrays by loads that
+// depend on nothing: tptr[q] per 16-byte slot of the concat row, roff[row][q] per output slot.  That is 4 bytes of coalesced
+// reads per output slot (S2: 15.4 MB against the 3.9 MB of ids the product reads).  --mix-probe 2 (col_of != null) reads
+// the offsets per (row, column) instead — fewer bytes than the ids, but behind one dependent hop (slot -> column).
+__global__ void __launch_bounds__(FCP_BLOCK_THREADS)
+mix_probe_kernel(const float *const *tptr, const uint32_t *roff, const int32_t *col_of, int roff_stride, float *out, int rows, int nslots,
+                 int nsp8, int nlist, int out_stride, int policy) {
+  constexpr int V = 4, R = 4, RB = FCP_WAVES_PER_BLOCK * R;
+  const int lane = threadIdx.x & (FCP_WAVE - 1), wave = threadIdx.x >> 6;
+  const int bid = blockIdx.x;
+  int idx, tile;
+  if (nsp8 > 0) {
+    const int xcd = bid & 7, j8 = bid >> 3;
+    idx = (j8 % nsp8) * 8 + xcd;
+    tile = j8 / nsp8;
+  } else {
+    idx = bid % (-nsp8);
+    tile = bid / (-nsp8);
+  }
+  if (idx >= nlist) return;
+  const int q = idx * FCP_WAVE + lane, row0 = tile * RB + wave * R;
+  if (q >= nslots || row0 >= rows) return;
+  const float *tb = *as_global(tptr + q);
+  uint32_t off[R];
+  const int at = col_of ? *as_global(col_of + q) : q;
+#pragma unroll
+  for (int r = 0; r < R; ++r) off[r] = row0 + r < rows ? *as_global(roff + (int64_t)(row0 + r) * roff_stride + at) : kNoRow;
+  VF<V> v[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    v[r] = vzero<V>();
+    if (is_row(off[r])) v[r] = ld_slot32<V>(tb, off[r]);
+  }
+  float *outp = out + q * V;
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+    if (row0 + r < rows) st_out<V>(outp + (int64_t)(row0 + r) * out_stride, v[r], policy);
+}
+
 static uint64_t splitmix(uint64_t &s) {
   uint64_t z = (s += 0x9E3779B97F4A7C15ull);
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -105,6 +148,7 @@ int main(int argc, char **argv) {
   int pack_threads = 8;
   int stager_depth = 4;     // with --h2d: slots of the stager's pinned ring
   int copy_kernel = 1;      // with --h2d: the stager's copies are kernels reading the pinned ring (the default); 0: hipMemcpyAsync (SDMA)
+  int mix_probe = 0;        // 1 | 2: time S2's access mix without a front (mix_probe_kernel) instead of the plan
   long vocab = 1000000;
   for (int i = 1; i + 1 < argc; i += 2) {
     std::string k = argv[i];
@@ -127,6 +171,7 @@ int main(int argc, char **argv) {
     else if (k == "--pack-threads") pack_threads = (int)v;
     else if (k == "--stager-depth") stager_depth = (int)v;
     else if (k == "--copy-kernel") copy_kernel = (int)v;
+    else if (k == "--mix-probe") mix_probe = (int)v;
     else if (k == "--bw-probe") {
       const char *names[4] = {"read", "write", "write-nt", "chunked-write-nt"};
       for (int kind = 0; kind < 4; ++kind) {
@@ -358,6 +403,119 @@ int main(int argc, char **argv) {
     std::printf("verify: %zu mismatching elements of %zu\n", bad, out.size());
     CHECK_HIP(hipFree(arena));
     if (bad) return 3;
+  }
+
+  // ---- --mix-probe 1: the dense kernel's loads and stores with zero front ---------------------------------------------
+  // One (table pointer per slot, slot offset per output slot) image per resident request, built here on the host; the
+  // requests rotate as in the timed run (one request alone would find its 86 MB of table lines in the Infinity Cache).
+  // Every store policy into a ring of one arena and a ring of six, launched back to back in stream order.
+  if (mix_probe) {
+    int width = 0;
+    std::vector<int> out_off(columns);
+    for (int c = 0; c < columns; ++c) {
+      out_off[c] = width;
+      width += cols[c].dim;
+    }
+    const int nslots = width / 4, nspans = (nslots + FCP_WAVE - 1) / FCP_WAVE;
+    const int nsp8 = nspans >= 8 ? (nspans + 7) / 8 : -nspans, ntiles = (batch + 15) / 16;
+    const int grid = (nsp8 > 0 ? 8 * nsp8 : nspans) * ntiles;
+    std::vector<const float *> h_tptr(nslots);
+    std::vector<int> col_of(nslots);
+    for (int c = 0; c < columns; ++c)
+      for (int q = out_off[c] / 4; q < (out_off[c] + cols[c].dim) / 4; ++q) {
+        col_of[q] = c;
+        h_tptr[q] = static_cast<const float *>(tables[c]) + (q * 4 - out_off[c]);
+      }
+    const float **d_tptr = nullptr;
+    CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&d_tptr), nslots * sizeof(float *)));
+    CHECK_HIP(hipMemcpy(d_tptr, h_tptr.data(), nslots * sizeof(float *), hipMemcpyHostToDevice));
+    std::vector<uint32_t *> d_roff(requests);
+    const bool compact = mix_probe == 2; // offsets per (row, column) behind a slot -> column array
+    const int roff_stride = compact ? columns : nslots;
+    int32_t *d_col_of = nullptr;
+    if (compact) {
+      CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&d_col_of), nslots * sizeof(int32_t)));
+      CHECK_HIP(hipMemcpy(d_col_of, col_of.data(), nslots * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    std::vector<uint32_t> h_roff((size_t)batch * roff_stride), col_row(columns);
+    for (int v = 0; v < requests; ++v) {
+      for (int b = 0; b < batch; ++b) {
+        for (int c = 0; c < columns; ++c) {
+          const char *p = blobs[v].data() + offs[v][c];
+          int64_t id;
+          if (esz[c] == 4) {
+            float x;
+            std::memcpy(&x, p + 4 * b, 4);
+            id = bucketize_host(boundaries, x);
+          } else {
+            std::memcpy(&id, p + 8 * b, 8);
+          }
+          col_row[c] = (uint32_t)id * (uint32_t)(cols[c].dim / 4);
+        }
+        for (int k = 0; k < roff_stride; ++k) h_roff[(size_t)b * roff_stride + k] = col_row[compact ? k : col_of[k]];
+      }
+      CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&d_roff[v]), h_roff.size() * 4));
+      CHECK_HIP(hipMemcpy(d_roff[v], h_roff.data(), h_roff.size() * 4, hipMemcpyHostToDevice));
+    }
+    const size_t out_bytes = (size_t)batch * width * 4;
+    std::vector<float *> arenas(6);
+    for (auto &a : arenas) CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&a), out_bytes));
+    hipStream_t st;
+    hipEvent_t e0, e1;
+    CHECK_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    CHECK_HIP(hipEventCreate(&e0));
+    CHECK_HIP(hipEventCreate(&e1));
+    if (verify) { // the probe writes what the plan writes
+      hipLaunchKernelGGL(mix_probe_kernel, dim3(grid), dim3(FCP_BLOCK_THREADS), 0, st, d_tptr, d_roff[0], d_col_of, roff_stride, arenas[0], batch,
+                         nslots, nsp8, nspans, width, 0);
+      CHECK_HIP(hipStreamSynchronize(st));
+      std::vector<float> out((size_t)batch * width);
+      CHECK_HIP(hipMemcpy(out.data(), arenas[0], out_bytes, hipMemcpyDeviceToHost));
+      size_t bad = 0;
+      for (int b = 0; b < batch; ++b)
+        for (int q = 0; q < nslots; ++q) {
+          const int c = col_of[q];
+          const char *p = blobs[0].data() + offs[0][c];
+          int64_t id;
+          if (esz[c] == 4) {
+            float x;
+            std::memcpy(&x, p + 4 * b, 4);
+            id = bucketize_host(boundaries, x);
+          } else {
+            std::memcpy(&id, p + 8 * b, 8);
+          }
+          for (int e = 0; e < 4; ++e)
+            if (out[(size_t)b * width + q * 4 + e] != hash_elem(1000 + c, (uint64_t)id, q * 4 - out_off[c] + e)) ++bad;
+        }
+      std::printf("mix probe verify: %zu mismatching elements of %zu\n", bad, out.size());
+      if (bad) return 3;
+    }
+    double line_bytes = 0; // a table row is fetched in whole 128-byte lines
+    for (int c = 0; c < columns; ++c) line_bytes += (double)batch * ((cols[c].dim * 4 + 127) / 128 * 128);
+    std::printf("mix probe %d: grid %d x %d, %d slots, %d rows; per launch %.1f MB of table lines + %.1f MB of output + %.1f MB of offsets\n",
+                mix_probe, grid, FCP_BLOCK_THREADS, nslots, batch, line_bytes / 1e6, (double)batch * width * 4 / 1e6,
+                (double)batch * roff_stride * 4 / 1e6);
+    const char *names[3] = {"nt", "sc1 nt", "plain"};
+    const int policies[3] = {0, FCP_ST_THROUGH, FCP_ST_PLAIN};
+    for (int pass = 0; pass < 2; ++pass) // (every cell twice: the second pass shows the run-to-run spread)
+      for (int nring : {1, 6})
+        for (int k = 0; k < 3; ++k) {
+          auto run = [&](int n) {
+            for (int i = 0; i < n; ++i)
+              hipLaunchKernelGGL(mix_probe_kernel, dim3(grid), dim3(FCP_BLOCK_THREADS), 0, st, d_tptr, d_roff[i % requests],
+                                 d_col_of, roff_stride, arenas[i % nring], batch, nslots, nsp8, nspans, width, policies[k]);
+          };
+          run(warmup > 0 ? warmup : 1);
+          CHECK_HIP(hipEventRecord(e0, st));
+          run(steps);
+          CHECK_HIP(hipEventRecord(e1, st));
+          CHECK_HIP(hipEventSynchronize(e1));
+          CHECK_HIP(hipGetLastError());
+          float ms = 0;
+          CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));
+          std::printf("mix probe %d pass %d ring %d stores %-6s  %.3f us per launch\n", mix_probe, pass, nring, names[k], ms * 1e3 / steps);
+        }
+    return 0;
   }
 
   // ---- PCIe-inclusive loop: host tensors -> pinned ring -> H2D -> kernel ----

@@ -276,7 +276,7 @@ struct fcp_plan {
   // with everything that does not depend on the request or the bound tables; plain_entries names, per FcpPlainCol of the
   // image, its byte offset there and the column (concat position) it describes.
   bool plain_dense = false;
-  int32_t plain_stride = 0, plain_spans = 0;
+  int32_t plain_stride = 0, plain_spans = 0, plain_cols_off = 0; // (plain_cols_off: FcpPlainSpan::cols_off of every record)
   std::vector<char> plain_tmpl;
   std::vector<std::pair<uint32_t, int32_t>> plain_entries;
   std::atomic<int32_t> last_dense_front{0}; // fcp_plan_last_dense_front: FCP_DENSE_FRONT_* of the last request

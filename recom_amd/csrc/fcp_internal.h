@@ -124,10 +124,15 @@ struct FcpLaunch {
 
 // ---- plain dense plans (fcp_dense_plain.hip) -------------------------------------------------------------------------------
 // The per-span image of a plan whose columns are all plain gathers (fcp_plan::plain_dense): one fixed-stride record per
-// 64-slot span — FcpPlainSpan, then FcpPlainCol x the plan's largest column count per span — behind the FcpColDyn records
-// of a descriptor slot.  A block finds its record from its span index and the kernel arguments alone, and the record
-// holds everything the block needs: no slot map, no static / dynamic column records.  A column that straddles a span
-// boundary appears in both records.
+// 64-slot span — FcpPlainSpan, the span's id facts, then FcpPlainCol x the plan's largest column count per span — behind
+// the FcpColDyn records of a descriptor slot.  A block finds its record from its span index and the kernel arguments
+// alone, and the record holds everything the block needs: no slot map, no static / dynamic column records.  A column that
+// straddles a span boundary appears in both records.
+//
+// Id facts: one dword per column of the span at byte FCP_PLAIN_FACTS_OFF of the record, all a pair thread needs before
+// its id load — the blob byte offset of the column's id stream / 4 in bits 0..29 and FCP_PLAIN_FACT_* in bits 30..31.
+// The array is padded with FCP_PLAIN_FACT_NONE to whole passes of the pair loop (16 columns): a wave reads the four
+// facts of its columns with one 16-byte scalar load before the record has arrived, and a padding fact loads nothing.
 struct FcpPlainCol {       // 48 bytes
   const float *table;      // device address of the table
   int64_t ids_off;         // byte offset of the id / value stream in the blob
@@ -138,9 +143,17 @@ struct FcpPlainCol {       // 48 bytes
   int32_t n_boundaries;
   float bnd_b0, bnd_inv, bnd_step;
 };
+constexpr uint32_t FCP_PLAIN_FACT_NONE = 0, FCP_PLAIN_FACT_I32 = 1, FCP_PLAIN_FACT_I64 = 2, FCP_PLAIN_FACT_F32 = 3;
+constexpr int FCP_PLAIN_FACTS_OFF = 80;      // = sizeof(FcpPlainSpan)
+constexpr int FCP_PLAIN_FACTS_PER_PASS = 16; // columns per pass of the pair loop (256 threads, 16 rows per block)
+// bytes of the id facts of records with up to max_cols columns
+constexpr int fcp_plain_facts_bytes(int max_cols) {
+  return (max_cols + FCP_PLAIN_FACTS_PER_PASS - 1) / FCP_PLAIN_FACTS_PER_PASS * FCP_PLAIN_FACTS_PER_PASS * 4;
+}
 struct FcpPlainSpan {      // 80 bytes
   int32_t ncols;           // columns with a slot in the span
-  int32_t pad_[3];
+  int32_t cols_off;        // byte offset of the FcpPlainCol array in the record (behind the id facts)
+  int32_t pad_[2];
   uint8_t lane_col[FCP_WAVE]; // slot of the span -> index of its column among the span's FcpPlainCol
 };
 // kernel arguments: 15 dwords, passed one by one so that they can be preloaded into SGPRs

@@ -646,8 +646,8 @@ void uniform_boundaries(const std::vector<float> &b, float *b0, float *inv, floa
 }
 
 // Plain dense plans (fcp_dense_plain.hip): the gate, and the per-span image with everything that is known now — the
-// lane -> column maps and the columns' static facts; table addresses and id-stream offsets are filled in per descriptor
-// slot (fill_plain_image).  Called once the static records exist (their boundary constants are the image's).
+// lane -> column maps and the columns' static facts; table addresses, id-stream offsets and the id facts (all
+// FCP_PLAIN_FACT_NONE here) are filled in per descriptor slot (fill_plain_image).  Called once the static records exist (their boundary constants are the image's).
 void build_plain_template(fcp_plan *p) {
   p->plain_dense = false;
   // FCP_DIAG=dense_generic: a qualifying plan stays on the generic kernel (the tests' seam)
@@ -683,7 +683,8 @@ void build_plain_template(fcp_plan *p) {
   int max_cols = 1;
   for (int sp = 0; sp < nspans; ++sp) max_cols = std::max(max_cols, last[sp] - first[sp] + 1);
   if (max_cols > FCP_WAVE) return; // (cannot happen: a column has at least one slot)
-  p->plain_stride = (int32_t)(sizeof(FcpPlainSpan) + (size_t)max_cols * sizeof(FcpPlainCol));
+  p->plain_cols_off = FCP_PLAIN_FACTS_OFF + fcp_plain_facts_bytes(max_cols);
+  p->plain_stride = (int32_t)(p->plain_cols_off + (size_t)max_cols * sizeof(FcpPlainCol));
   p->plain_spans = nspans;
   p->plain_tmpl.assign((size_t)nspans * p->plain_stride, 0);
   p->plain_entries.clear();
@@ -692,6 +693,7 @@ void build_plain_template(fcp_plan *p) {
     FcpPlainSpan head;
     std::memset(&head, 0, sizeof(head));
     head.ncols = last[sp] - first[sp] + 1;
+    head.cols_off = p->plain_cols_off;
     for (int pos = first[sp]; pos <= last[sp]; ++pos) {
       const FcpColStatic &s = p->h_cols[pos];
       FcpPlainCol c;
@@ -706,7 +708,7 @@ void build_plain_template(fcp_plan *p) {
       c.bnd_b0 = s.bnd_b0;
       c.bnd_inv = s.bnd_inv;
       c.bnd_step = s.bnd_step;
-      const size_t at = (size_t)sp * p->plain_stride + sizeof(FcpPlainSpan) + (size_t)(pos - first[sp]) * sizeof(FcpPlainCol);
+      const size_t at = (size_t)sp * p->plain_stride + p->plain_cols_off + (size_t)(pos - first[sp]) * sizeof(FcpPlainCol);
       std::memcpy(p->plain_tmpl.data() + at, &c, sizeof(c));
       p->plain_entries.emplace_back((uint32_t)at, pos);
       for (int q = std::max(s.out_off / 4, sp * FCP_WAVE); q < std::min((s.out_off + s.dim) / 4, (sp + 1) * FCP_WAVE); ++q)

@@ -13,15 +13,25 @@ bool stream_is_capturing(hipStream_t stream) {
 }
 
 // Plain dense plans: the span image of a descriptor slot (host copy, behind the slot's FcpColDyn records) = the plan's
-// template + what the request and the bound tables decide: every column's id stream and table address.
-static void fill_plain_image(const fcp_plan *p, const FcpColStatic *cols, FcpColDyn *h_dyn) {
+// template + what the request and the bound tables decide: every column's table address, its id stream and, with it, its
+// id fact (fcp_internal.h).  The facts follow the request's shapes alone: a table re-bind writes the values they had.
+// False, with the image unfinished: an id stream that a fact cannot name (not 4-byte aligned, or 4 GiB or more into the
+// blob) — the request takes the generic kernel.
+static bool fill_plain_image(const fcp_plan *p, const FcpColStatic *cols, FcpColDyn *h_dyn) {
   char *img = reinterpret_cast<char *>(h_dyn) + slot_image_off(p);
   std::memcpy(img, p->plain_tmpl.data(), p->plain_tmpl.size());
   for (const auto &e : p->plain_entries) {
     FcpPlainCol *c = reinterpret_cast<FcpPlainCol *>(img + e.first);
     c->table = cols[e.second].table;
     c->ids_off = h_dyn[e.second].ids_off;
+    const uint64_t off = (uint64_t)c->ids_off;
+    if ((off & 3) || (off >> 32)) return false;
+    const uint32_t rec = e.first / (uint32_t)p->plain_stride * (uint32_t)p->plain_stride;
+    const uint32_t j = (e.first - rec - (uint32_t)p->plain_cols_off) / (uint32_t)sizeof(FcpPlainCol);
+    const uint32_t kind = c->kind == FCP_IDS_I64 ? FCP_PLAIN_FACT_I64 : c->kind == FCP_IDS_I32 ? FCP_PLAIN_FACT_I32 : FCP_PLAIN_FACT_F32;
+    reinterpret_cast<uint32_t *>(img + rec + FCP_PLAIN_FACTS_OFF)[j] = (uint32_t)(off >> 2) | kind << 30;
   }
+  return true;
 }
 
 // Bind the table addresses (FeatureColumnProcess `inputs`).  TF variables keep their address between requests, so this
@@ -54,7 +64,7 @@ int bind_tables(fcp_plan *p, const void *const *input_ptrs, bool capturing) {
   if (p->plain_dense) { // the span images hold table addresses: rebuilt (the device has drained; the caller holds the plan's mutex)
     for (auto &s : p->slots) {
       if (!s.img_built) continue;
-      fill_plain_image(p, p->h_cols.data(), s.h_dyn);
+      (void)fill_plain_image(p, p->h_cols.data(), s.h_dyn); // (its id streams were nameable when the slot was installed)
       const size_t off = slot_image_off(p);
       HIP_TRY(hipMemcpy(reinterpret_cast<char *>(s.d_dyn) + off, reinterpret_cast<const char *>(s.h_dyn) + off, p->plain_tmpl.size(),
                         hipMemcpyHostToDevice));
@@ -182,8 +192,9 @@ int install_slot(fcp_plan *p, const fcp_process_args_t *a, DynSlot &s) {
   std::unique_lock<std::mutex> image_lock(p->mu, std::defer_lock);
   if (s.meta.plain) {
     image_lock.lock();
-    fill_plain_image(p, p->h_cols.data(), s.h_dyn);
-    s.img_built = true;
+    s.meta.plain = fill_plain_image(p, p->h_cols.data(), s.h_dyn);
+    s.img_built = s.meta.plain;
+    if (!s.meta.plain) image_lock.unlock();
   }
   // (the image is the tail of the slot: shapes that do not take the plain kernel upload the records only)
   const size_t dyn_bytes = s.meta.plain ? slot_dyn_bytes(p) : (slot_dyn_bytes(p) - (p->plain_dense ? p->plain_tmpl.size() : 0));
