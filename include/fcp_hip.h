@@ -466,6 +466,49 @@ int64_t fcp_table_row_bytes(int32_t kind, int32_t dim);
  *   FCP_ERR_HIP               a kernel launch failed. */
 int fcp_table_convert(void *dst, int32_t dst_kind, int64_t dst_row0, const void *src, int32_t src_kind, int64_t rows,
                       int32_t dim, int32_t device, void *stream);
+/* ---- rows by id: refreshing and reading back rows of a served table --------------------------------------------------------- */
+/* fcp_table_update_rows: write n float32 rows into a table of ANY format at the row indices row_ids names — the delta a
+ * trainer ships to a served model.  `table` is the BASE of a table [table_rows, dim] in format `kind` (any FCP_TAB_* value,
+ * float32 included: one entry for every format); `row_ids` is int64 [n] and `rows` float32 [n, dim], rows back to back, both on
+ * the device.  Row i of `rows` is converted by fcp_table_convert's value model for float32 -> kind — q8: the row
+ * quantized::embedding_bag_byte_prepack writes, every operation rounded once; bf16 / fp16: fl16, rounded once; float32: a copy —
+ * and written at table row row_ids[i] (byte offset row_ids[i] * fcp_table_row_bytes of kind and dim, formed in 64 bits).  For
+ * pairwise distinct ids the table then equals, byte for byte, what fcp_table_convert would have written from the float32
+ * master with the delta applied.  Only this entry can patch a q8 row: its codes, scale and bias are the quantiser's.
+ * Device to device on `device`, asynchronous on `stream` (a hipStream_t), no allocation, no synchronisation; a plan — or any
+ * other work — on the same stream sees the updated rows.
+ *
+ * An id outside [0, table_rows) — the whole 64-bit value is compared, as the plans compare ids — is SKIPPED: its row touches
+ * no memory.  `skipped` may be NULL; otherwise it points at an int64 counter on the device, which is increased by the number
+ * of skipped rows (the caller zeroes it and reads it back, both on `stream`).
+ *
+ * The caller's side of the contract, NOT checked: the ids of one call are pairwise distinct (with duplicates the destination
+ * row holds unspecified bytes — a q8 row may mix the codes of one source with the scale and bias of another — and nothing
+ * outside that row is touched); `rows` and `row_ids` do not overlap the table; a request that reads the table on ANOTHER
+ * stream at the same time may see either version of a row, or a q8 row of mixed parts.
+ *
+ * Alignment: `table` obeys the plan's rule for its kind (with V the largest of 4 | 2 | 1 that divides dim: a float32 base
+ * 4 * V-byte aligned, a bf16 / fp16 base 2 * V-byte aligned, a q8 base 4-byte aligned), `rows` that of a float32 table of this
+ * dim, `row_ids` and `skipped` 8 bytes.  table_rows lies in [1, 2^32 - 3), the row limit of a plan's table, and n < 2^32 - 3.
+ *
+ * Status, decided in this order (the first two need no device):
+ *   FCP_ERR_INVALID_ARGUMENT  n < 0 or beyond its limit, table_rows outside its range, dim <= 0, a kind that is no FCP_TAB_*
+ *                             value, a null table / row_ids / rows with n > 0, a misaligned pointer; fcp_last_error names
+ *                             the argument between backquotes;
+ *   FCP_OK                    n == 0: nothing is launched and no device is touched;
+ *   FCP_ERR_NO_DEVICE         no usable gfx950 device;
+ *   FCP_ERR_HIP               a kernel launch failed.
+ * No combination of valid arguments is FCP_ERR_UNSUPPORTED. */
+int fcp_table_update_rows(void *table, int32_t kind, int64_t table_rows, int32_t dim, const int64_t *row_ids, const float *rows,
+                          int64_t n, int64_t *skipped, int32_t device, void *stream);
+/* fcp_table_read_rows: the float32 values a plan reads at row_ids, for verifying an applied delta or exporting a row.  Row i of
+ * `rows` (float32 [n, dim] on the device) receives table row row_ids[i] as the plans see it: fma(float(code), scale, bias)
+ * rounded once for q8, the exact widening for bf16 / fp16, a copy for float32, and a row of +0.0 for an id outside
+ * [0, table_rows) — the plans' rule for ids outside the vocabulary.  Bit for bit the output of a one-column FCP_FORM_GATHER
+ * plan over that table.  `rows` must not overlap the table (not checked).  Arguments, alignment, limits, asynchrony and the
+ * status order are those of fcp_table_update_rows. */
+int fcp_table_read_rows(float *rows, const void *table, int32_t kind, int64_t table_rows, int32_t dim, const int64_t *row_ids,
+                        int64_t n, int32_t device, void *stream);
 /* ---- placement gate (replaces check_table_size, cuda_emitter.cc:1080-1094) -------- */
 /* The reference keeps a column on the CPU when its table exceeds max_table_size =
  * 256 MiB (fc_optimize_pass.cc:71, RECOM_CPU_GPU_CO_RUN).  On MI355X the question is

@@ -1,0 +1,318 @@
+// fcp_table_rows.hip — fcp_table_update_rows / fcp_table_read_rows: rows of a table in any of the formats the plans read
+// (FCP_TAB_F32 / _BF16 / _F16 / _Q8), written from float32 rows and read back as float32 rows BY ID, on the device.  The day
+// after the load: a trainer ships (row ids, float32 rows) deltas, and fcp_table_convert (fcp_convert.hip) writes contiguous runs
+// only.  The reference reads float32 tables only and has no counterpart.
+//
+//   update -> q8      fcp_update_q8_kernel<V, G>: the row quantiser of fcp_quantize_q8_kernel<V, G>, restated — the same 3 V x 7 G
+//                     matrix, the same group of G lanes per row, the row kept in registers (kQSlots slots per lane of a 64-lane
+//                     group, the tail beyond read a second time), min and max by __shfl_xor butterflies, the two correctly
+//                     rounded divisions, rint to even, nothing contracted — with the destination row taken from the row's id
+//                     instead of its index.  Every lane of a group loads the same id (one address).  A group is live when its
+//                     row exists and (uint64_t)id < table_rows; lanes of dead groups take part in the exchanges and touch no
+//                     memory.  Codes leave V bytes at a time, scale and bias as one pair (Q8Pair<V>) from the group's first lane:
+//                     id * (dim + 8) keeps the alignment dst_row0 * (dim + 8) has in fcp_convert.hip, a multiple of V.
+//   update -> 16 / float32   fcp_update_rows_kernel<V>: streaming, one V-element slot per lane, thread -> (row, slot) as
+//                     fcp_dequantize_q8_kernel; st_out_narrow<V> (fl16, rounded once) or a float32 slot store.
+//   read <- any kind  fcp_read_rows_kernel<V>: the same mapping; ld_q8<V> (one v_fma_f32 per element), widen16<V> (exact) or a
+//                     float32 slot load; a row of +0.0 for an id outside the table, the plans' rule.
+// The element type of the two streaming kernels is a kernel argument (wave-uniform branch), as tab_kind is in the fused
+// kernels.  Ids are whole 64-bit values, compared unsigned against table_rows: a negative id is outside.  Skipped rows are
+// counted with at most one atomicAdd per wave (a ballot of the lanes that hold a skipped row's first slot).
+// The host chunks every call into launches of at most 2^30 threads, so an in-launch index fits 32 bits; byte offsets are
+// formed in 64 bits.
+//
+// No scratch, no LDS; the default modes of the other units (denormals kept, IEEE).  Contraction is off from here to the end of
+// the file: every operation of the quantiser rounds once, by itself.  The divisions are the correctly rounded ones.
+#include "fcp_fused_bodies.h"
+#include "fcp_host.h"
+
+#pragma clang fp contract(off)
+
+static_assert(FCP_TAB_BF16 == FCP_OUT_BF16 && FCP_TAB_F16 == FCP_OUT_F16, "st_out_narrow takes the table kind as its output kind");
+
+namespace {
+
+constexpr int kQSlots = 4;                          // slots of a row a lane of a 64-lane group keeps in registers (fcp_convert.hip)
+constexpr int64_t kMaxLaunchThreads = 1ll << 30;    // per launch: in-launch indices fit 32 bits, grid x block < 2^32
+
+template <int V> __device__ __forceinline__ VF<V> ld_f32(const float *p) {
+  typedef typename VecType<V>::T T;
+  const T t = *as_global(reinterpret_cast<const T *>(p));
+  VF<V> r;
+  __builtin_memcpy(&r, &t, sizeof(T));
+  return r;
+}
+template <int V> __device__ __forceinline__ void st_f32(float *p, const VF<V> &v) {
+  typedef typename VecType<V>::T T;
+  T t;
+  __builtin_memcpy(&t, &v, sizeof(T));
+  *as_global(reinterpret_cast<T *>(p)) = t;
+}
+
+template <int V> __device__ __forceinline__ void minmax(const VF<V> &x, float &mn, float &mx) {
+#pragma unroll
+  for (int i = 0; i < V; ++i) {
+    mn = fminf(mn, x.v[i]);
+    mx = fmaxf(mx, x.v[i]);
+  }
+}
+
+// rint((x - mn) * inv), round-half-even (v_rndne_f32), each operation rounded once; element i in byte i
+template <int V> __device__ __forceinline__ void st_codes(char *p, const VF<V> &x, float mn, float inv) {
+  uint32_t c = 0;
+#pragma unroll
+  for (int i = 0; i < V; ++i) {
+    const float d = x.v[i] - mn;
+    const float q = __builtin_rintf(d * inv);
+    c |= ((uint32_t)(int32_t)q & 0xFFu) << (8 * i);
+  }
+  *as_global(reinterpret_cast<typename Q8Codes<V>::T *>(p)) = (typename Q8Codes<V>::T)c;
+}
+
+// One vector atomicAdd per wave at most: `mine` is set in the one lane that speaks for a skipped row.  Every lane of the wave
+// gets here (no lane has returned yet), so the wave's first lane is there to issue it.
+__device__ __forceinline__ void count_skipped(unsigned long long *skipped, bool mine) {
+  if (!skipped) return;
+  const unsigned long long m = __ballot(mine);
+  if (m != 0 && (threadIdx.x & 63) == 0) atomicAdd(skipped, (unsigned long long)__popcll(m));
+}
+
+// table: the table's base; ids / src: the first row of this launch; rows: of this launch (< 2^30).  Block = 256 / G rows; a
+// group never straddles a wave, and it is live or not as a whole.
+template <int V, int G>
+__global__ void __launch_bounds__(FCP_BLOCK_THREADS)
+    fcp_update_q8_kernel(char *table, const int64_t *ids, const float *src, int32_t rows, int32_t dim, uint64_t table_rows,
+                         unsigned long long *skipped) {
+  constexpr int S = G == 64 ? kQSlots : (G == 1 ? 3 : 1); // G == 1: dim 3 is three one-element slots of one lane
+  const int tid = threadIdx.x;
+  const int lane = tid & (G - 1);
+  const int64_t row = (int64_t)blockIdx.x * (FCP_BLOCK_THREADS / G) + tid / G;
+  const bool have = row < rows;
+  const uint64_t id = have ? (uint64_t)*as_global(ids + row) : ~0ull; // the whole group: one address
+  const bool live = have && id < table_rows;
+  count_skipped(skipped, have && !live && lane == 0);
+  const int nslots = dim / V;
+  const float *srow = src + row * dim;
+  char *drow = table + (live ? id : 0) * ((uint64_t)dim + 8);
+
+  VF<V> x[S];
+  float mn = __builtin_inff(), mx = -__builtin_inff();
+#pragma unroll
+  for (int k = 0; k < S; ++k) {
+    x[k] = vzero<V>();
+    const int slot = lane + k * G;
+    if (live && slot < nslots) {
+      x[k] = ld_f32<V>(srow + (int64_t)slot * V);
+      minmax<V>(x[k], mn, mx);
+    }
+  }
+  if constexpr (G == 64) {
+    if (live)
+      for (int slot = lane + S * G; slot < nslots; slot += G) {
+        const VF<V> t = ld_f32<V>(srow + (int64_t)slot * V);
+        minmax<V>(t, mn, mx);
+      }
+  }
+#pragma unroll
+  for (int m = G / 2; m >= 1; m >>= 1) {
+    mn = fminf(mn, __shfl_xor(mn, m, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, m, 64));
+  }
+  const float range = mx - mn;
+  const float scale = range / 255.0f;
+  const float inv = 255.0f / (range + 1e-8f);
+  if (!live) return;
+#pragma unroll
+  for (int k = 0; k < S; ++k) {
+    const int slot = lane + k * G;
+    if (slot < nslots) st_codes<V>(drow + (int64_t)slot * V, x[k], mn, inv);
+  }
+  if constexpr (G == 64) {
+    for (int slot = lane + S * G; slot < nslots; slot += G) // beyond the register cap: the row's tail is read again
+      st_codes<V>(drow + (int64_t)slot * V, ld_f32<V>(srow + (int64_t)slot * V), mn, inv);
+  }
+  if (lane == 0) {
+    const uint64_t pair = (uint64_t)__float_as_uint(scale) | ((uint64_t)__float_as_uint(mn) << 32);
+    *(FCP_GLOBAL typename Q8Pair<V>::T *)(drow + dim) = pair;
+  }
+}
+
+// n: slots of this launch (<= 2^30, one row of more: < 2^31); ids / src: the first row of this launch; spr: slots per row,
+// dim / V; kind: FCP_TAB_F32 | _BF16 | _F16, the same for every wave
+template <int V>
+__global__ void __launch_bounds__(FCP_BLOCK_THREADS)
+    fcp_update_rows_kernel(char *table, const int64_t *ids, const float *src, uint32_t n, uint32_t spr, int32_t dim, int32_t kind,
+                           uint64_t table_rows, unsigned long long *skipped) {
+  const uint32_t i = blockIdx.x * FCP_BLOCK_THREADS + threadIdx.x;
+  const bool have = i < n;
+  const uint32_t r = have ? i / spr : 0;
+  const uint32_t e = (i - r * spr) * V;
+  const uint64_t id = have ? (uint64_t)*as_global(ids + r) : ~0ull;
+  const bool live = have && id < table_rows;
+  count_skipped(skipped, have && !live && e == 0);
+  if (!live) return;
+  const VF<V> x = ld_f32<V>(src + (uint64_t)i * V);
+  if (kind == FCP_TAB_F32)
+    st_f32<V>(reinterpret_cast<float *>(table) + (id * (uint64_t)dim + e), x);
+  else
+    st_out_narrow<V>(table + 2 * (id * (uint64_t)dim + e), x, FCP_ST_PLAIN, kind);
+}
+
+// dst / ids: the first row of this launch; kind: any FCP_TAB_* value, the same for every wave
+template <int V>
+__global__ void __launch_bounds__(FCP_BLOCK_THREADS)
+    fcp_read_rows_kernel(float *dst, const char *table, const int64_t *ids, uint32_t n, uint32_t spr, int32_t dim, int32_t kind,
+                         uint64_t table_rows) {
+  const uint32_t i = blockIdx.x * FCP_BLOCK_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t r = i / spr;
+  const uint32_t e = (i - r * spr) * V;
+  const uint64_t id = (uint64_t)*as_global(ids + r);
+  VF<V> x = vzero<V>();
+  if (id < table_rows) {
+    if (kind == FCP_TAB_F32) {
+      x = ld_f32<V>(reinterpret_cast<const float *>(table) + (id * (uint64_t)dim + e));
+    } else if (kind == FCP_TAB_Q8) {
+      const char *row = table + id * ((uint64_t)dim + 8);
+      x = ld_q8<V>(row + e, row + dim);
+    } else {
+      typedef typename NarrowType<V>::T T;
+      const T t = *as_global(reinterpret_cast<const T *>(table + 2 * (id * (uint64_t)dim + e)));
+      x = widen16<V>(t, kind);
+    }
+  }
+  st_f32<V>(dst + (uint64_t)i * V, x);
+}
+
+inline dim3 blocks_for(int64_t threads) { return dim3((uint32_t)((threads + FCP_BLOCK_THREADS - 1) / FCP_BLOCK_THREADS)); }
+
+template <int V, int G>
+void update_q8_rows(char *table, const int64_t *ids, const float *src, int64_t n, int dim, uint64_t table_rows,
+                    unsigned long long *skipped, hipStream_t s) {
+  const int64_t per_launch = kMaxLaunchThreads / G;
+  for (int64_t r0 = 0; r0 < n; r0 += per_launch) {
+    const int64_t rows = std::min(n - r0, per_launch);
+    hipLaunchKernelGGL((fcp_update_q8_kernel<V, G>), blocks_for(rows * G), dim3(FCP_BLOCK_THREADS), 0, s, table, ids + r0,
+                       src + r0 * dim, (int32_t)rows, (int32_t)dim, table_rows, skipped);
+  }
+}
+
+// G: 1 for dims <= 4, else the power of two that holds the row's slots, at most 64 (fcp_convert.hip)
+template <int V>
+void update_q8(char *table, const int64_t *ids, const float *src, int64_t n, int dim, uint64_t table_rows, unsigned long long *skipped,
+               hipStream_t s) {
+  const int nslots = dim / V;
+  int g = 1;
+  if (dim > 4)
+    while (g < nslots && g < 64) g <<= 1;
+  switch (g) {
+  case 1: update_q8_rows<V, 1>(table, ids, src, n, dim, table_rows, skipped, s); break;
+  case 2: update_q8_rows<V, 2>(table, ids, src, n, dim, table_rows, skipped, s); break;
+  case 4: update_q8_rows<V, 4>(table, ids, src, n, dim, table_rows, skipped, s); break;
+  case 8: update_q8_rows<V, 8>(table, ids, src, n, dim, table_rows, skipped, s); break;
+  case 16: update_q8_rows<V, 16>(table, ids, src, n, dim, table_rows, skipped, s); break;
+  case 32: update_q8_rows<V, 32>(table, ids, src, n, dim, table_rows, skipped, s); break;
+  default: update_q8_rows<V, 64>(table, ids, src, n, dim, table_rows, skipped, s); break;
+  }
+}
+
+template <int V>
+void update(void *table, int kind, const int64_t *ids, const float *src, int64_t n, int dim, uint64_t table_rows,
+            unsigned long long *skipped, hipStream_t s) {
+  if (kind == FCP_TAB_Q8) return update_q8<V>(static_cast<char *>(table), ids, src, n, dim, table_rows, skipped, s);
+  const int64_t spr = dim / V;
+  const int64_t per_launch = std::max<int64_t>(1, kMaxLaunchThreads / spr); // (one row of 2^31 - 1 elements: 2^31 threads)
+  for (int64_t r0 = 0; r0 < n; r0 += per_launch) {
+    const int64_t slots = std::min(n - r0, per_launch) * spr;
+    hipLaunchKernelGGL(fcp_update_rows_kernel<V>, blocks_for(slots), dim3(FCP_BLOCK_THREADS), 0, s, static_cast<char *>(table),
+                       ids + r0, src + r0 * dim, (uint32_t)slots, (uint32_t)spr, (int32_t)dim, (int32_t)kind, table_rows, skipped);
+  }
+}
+
+template <int V>
+void read(float *dst, const void *table, int kind, const int64_t *ids, int64_t n, int dim, uint64_t table_rows, hipStream_t s) {
+  const int64_t spr = dim / V;
+  const int64_t per_launch = std::max<int64_t>(1, kMaxLaunchThreads / spr);
+  for (int64_t r0 = 0; r0 < n; r0 += per_launch) {
+    const int64_t slots = std::min(n - r0, per_launch) * spr;
+    hipLaunchKernelGGL(fcp_read_rows_kernel<V>, blocks_for(slots), dim3(FCP_BLOCK_THREADS), 0, s, dst + r0 * dim,
+                       static_cast<const char *>(table), ids + r0, (uint32_t)slots, (uint32_t)spr, (int32_t)dim, (int32_t)kind,
+                       table_rows);
+  }
+}
+
+bool known_kind(int32_t k) { return k == FCP_TAB_F32 || k == FCP_TAB_BF16 || k == FCP_TAB_F16 || k == FCP_TAB_Q8; }
+int vec_of(int32_t dim) { return dim % 4 == 0 ? 4 : dim % 2 == 0 ? 2 : 1; }
+// the base alignment of a table of `kind`: what a plan asks of the same table (base_alignment of fcp_convert.hip)
+int base_alignment(int32_t kind, int vec) { return kind == FCP_TAB_F32 ? 4 * vec : kind == FCP_TAB_Q8 ? 4 : 2 * vec; }
+const char *kind_name(int32_t k) { return k == FCP_TAB_F32 ? "float32" : k == FCP_TAB_BF16 ? "bf16" : k == FCP_TAB_F16 ? "fp16" : "q8"; }
+
+// The argument checks both entries share, in the stated order; `who` is the entry's name.  The argument is named between
+// backquotes: `rows` is also part of two other arguments' names.
+int check_args(const char *who, const void *table, int32_t kind, int64_t table_rows, int32_t dim, const void *row_ids, const void *rows,
+               int64_t n, const void *skipped) {
+  const std::string w = std::string(who) + ": ";
+  if (n < 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`n` is negative");
+  if (n >= (1ll << 32) - 3) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`n` must stay below 2^32 - 3");
+  if (table_rows < 1 || table_rows >= (1ll << 32) - 3)
+    return fail(FCP_ERR_INVALID_ARGUMENT, w + "`table_rows` must lie in [1, 2^32 - 3), a plan's row limit");
+  if (dim <= 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`dim` must be positive");
+  if (!known_kind(kind)) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`kind` is no FCP_TAB_* value");
+  if (n > 0 && !table) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`table` is null");
+  if (n > 0 && !row_ids) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`row_ids` is null");
+  if (n > 0 && !rows) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`rows` is null");
+  const int vec = vec_of(dim);
+  if ((uintptr_t)table % base_alignment(kind, vec))
+    return fail(FCP_ERR_INVALID_ARGUMENT, w + "`table` is not " + std::to_string(base_alignment(kind, vec)) + "-byte aligned (a " +
+                                              kind_name(kind) + " table of this dim)");
+  if ((uintptr_t)rows % (4 * vec))
+    return fail(FCP_ERR_INVALID_ARGUMENT, w + "`rows` is not " + std::to_string(4 * vec) + "-byte aligned (float32 rows of this dim)");
+  if ((uintptr_t)row_ids % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`row_ids` is not 8-byte aligned");
+  if ((uintptr_t)skipped % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`skipped` is not 8-byte aligned");
+  return FCP_OK;
+}
+
+} // namespace
+
+extern "C" int fcp_table_update_rows(void *table, int32_t kind, int64_t table_rows, int32_t dim, const int64_t *row_ids,
+                                     const float *rows, int64_t n, int64_t *skipped, int32_t device, void *stream) {
+  int rc = check_args("fcp_table_update_rows", table, kind, table_rows, dim, row_ids, rows, n, skipped);
+  if (rc) return rc;
+  if (n == 0) return FCP_OK;
+  DeviceGuard guard;
+  rc = guard.enter(device);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  unsigned long long *sk = reinterpret_cast<unsigned long long *>(skipped);
+  const int vec = vec_of(dim);
+  if (vec == 4)
+    update<4>(table, kind, row_ids, rows, n, dim, (uint64_t)table_rows, sk, s);
+  else if (vec == 2)
+    update<2>(table, kind, row_ids, rows, n, dim, (uint64_t)table_rows, sk, s);
+  else
+    update<1>(table, kind, row_ids, rows, n, dim, (uint64_t)table_rows, sk, s);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail("fcp_table_update_rows: kernel launch", e);
+  return FCP_OK;
+}
+
+extern "C" int fcp_table_read_rows(float *rows, const void *table, int32_t kind, int64_t table_rows, int32_t dim,
+                                   const int64_t *row_ids, int64_t n, int32_t device, void *stream) {
+  int rc = check_args("fcp_table_read_rows", table, kind, table_rows, dim, row_ids, rows, n, nullptr);
+  if (rc) return rc;
+  if (n == 0) return FCP_OK;
+  DeviceGuard guard;
+  rc = guard.enter(device);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int vec = vec_of(dim);
+  if (vec == 4)
+    read<4>(rows, table, kind, row_ids, n, dim, (uint64_t)table_rows, s);
+  else if (vec == 2)
+    read<2>(rows, table, kind, row_ids, n, dim, (uint64_t)table_rows, s);
+  else
+    read<1>(rows, table, kind, row_ids, n, dim, (uint64_t)table_rows, s);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail("fcp_table_read_rows: kernel launch", e);
+  return FCP_OK;
+}

@@ -166,7 +166,7 @@ EXPORTS = [
     "fcp_plan_probe_private_streams", "fcp_plan_private_streams_verdict", "fcp_plan_verify_private_streams",
     "fcp_plan_private_streams_stats", "fcp_plan_last_launch", "fcp_plan_last_csr", "fcp_aux_launch_counts",
     "fcp_plan_out_dtype", "fcp_plan_last_dense_front", "fcp_plan_table_dtype",
-    "fcp_table_row_bytes", "fcp_table_convert",
+    "fcp_table_row_bytes", "fcp_table_convert", "fcp_table_update_rows", "fcp_table_read_rows",
 ]
 
 _lib = None
@@ -320,6 +320,11 @@ def load() -> C.CDLL:
         L.fcp_table_row_bytes.argtypes = [C.c_int32, C.c_int32]
         L.fcp_table_convert.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
                                         C.c_void_p]
+    if hasattr(L, "fcp_table_update_rows"):
+        L.fcp_table_update_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                            C.c_void_p, C.c_int32, C.c_void_p]
+        L.fcp_table_read_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                          C.c_int32, C.c_void_p]
     if L.fcp_abi_version() != FCP_ABI_VERSION:
         raise ImportError("libfcp_hip.so ABI version mismatch; rebuild")
     _lib = L

@@ -1,5 +1,6 @@
 """Table conversion on the device (``fcp_table_convert``, recom_amd/csrc/fcp_convert.hip): float32 embedding tables to the
-formats the plans read — bf16, fp16 and 8-bit row-quantised ("q8") — and back, on torch device tensors.
+formats the plans read — bf16, fp16 and 8-bit row-quantised ("q8") — and back, on torch device tensors; and rows of such a
+table written and read back by id (``fcp_table_update_rows`` / ``fcp_table_read_rows``, recom_amd/csrc/fcp_table_rows.hip).
 
 Plans do not quantise; this does, once, at load time.  The value model is the header's (include/fcp_hip.h): float32 -> q8 is
 exactly the tensor ``quantized::embedding_bag_byte_prepack`` returns, q8 -> float32 is ``fma(code, scale, bias)`` rounded
@@ -112,3 +113,102 @@ def convert_from_host(table_cpu, dtype: str, device, chunk_rows: int = 1 << 16):
             staged[:n].copy_(bounce[:n], non_blocking=True)
             convert(staged[:n], dtype, out=out, dst_row0=r0, stream=stream.cuda_stream)
     return out
+
+
+# ---- rows by id (fcp_table_update_rows / fcp_table_read_rows) --------------------------------------------------------------
+def _ids_of(torch, table, row_ids):
+    if row_ids.dtype != torch.int64 or row_ids.dim() != 1 or not row_ids.is_contiguous():
+        raise ValueError("row_ids is a contiguous int64 [n] tensor")
+    if row_ids.device != table.device:
+        raise ValueError(f"table is on {table.device}, row_ids on {row_ids.device}")
+    return int(row_ids.shape[0])
+
+
+def _rows_of(torch, table, dim: int, n: int, rows, what: str) -> None:
+    if rows.dtype != torch.float32 or rows.dim() != 2 or not rows.is_contiguous():
+        raise ValueError(f"{what} is a contiguous float32 [n, dim] tensor")
+    if rows.device != table.device:
+        raise ValueError(f"table is on {table.device}, {what} on {rows.device}")
+    if rows.shape[0] != n:
+        raise ValueError(f"{what} has {rows.shape[0]} rows, row_ids names {n}")
+    if rows.shape[1] != dim:
+        raise ValueError(f"{what} has rows of dim {rows.shape[1]}; the table's are of dim {dim}")
+
+
+def update_rows(table, row_ids, rows, skipped=None, stream: Optional[int] = None):
+    """``fcp_table_update_rows``: write the float32 ``rows`` ``[n, dim]`` into ``table`` (a device tensor in one of the four
+    table formats) at the row indices ``row_ids`` (int64 ``[n]``, pairwise distinct — not checked), each converted as
+    ``convert`` converts float32 to the table's format.  Ids outside the table are skipped; ``skipped``, an int64 device
+    tensor of one element, is increased by their number (the caller zeroes it).  Asynchronous on ``stream`` (torch's current
+    stream of the device by default).  Returns ``table``."""
+    import torch
+    name, dim = _kind_and_dim(table, "table")
+    n = _ids_of(torch, table, row_ids)
+    _rows_of(torch, table, dim, n, rows, "rows")
+    if skipped is not None:
+        if skipped.dtype != torch.int64 or skipped.numel() != 1 or skipped.device != table.device:
+            raise ValueError("skipped is an int64 tensor of one element on the table's device")
+    if stream is None:
+        stream = torch.cuda.current_stream(table.device).cuda_stream
+    status = _lib.load().fcp_table_update_rows(C.c_void_p(table.data_ptr()), _lib.TABLE_KINDS[name], int(table.shape[0]), dim,
+                                               C.c_void_p(row_ids.data_ptr()), C.c_void_p(rows.data_ptr()), n,
+                                               C.c_void_p(skipped.data_ptr()) if skipped is not None else None,
+                                               table.device.index or 0, C.c_void_p(stream))
+    _lib.check(status, "fcp_table_update_rows")
+    return table
+
+
+def read_rows(table, row_ids, out=None, stream: Optional[int] = None):
+    """``fcp_table_read_rows``: the float32 values a plan reads at ``row_ids`` (int64 ``[n]``) of ``table`` — a row of +0.0
+    for an id outside the table.  ``out``: float32 ``[n, dim]`` on the table's device, allocated when not given.
+    Asynchronous on ``stream`` (torch's current stream of the device by default).  Returns ``out``."""
+    import torch
+    name, dim = _kind_and_dim(table, "table")
+    n = _ids_of(torch, table, row_ids)
+    if out is None:
+        out = torch.empty((n, dim), dtype=torch.float32, device=table.device)
+    _rows_of(torch, table, dim, n, out, "out")
+    if stream is None:
+        stream = torch.cuda.current_stream(table.device).cuda_stream
+    status = _lib.load().fcp_table_read_rows(C.c_void_p(out.data_ptr()), C.c_void_p(table.data_ptr()), _lib.TABLE_KINDS[name],
+                                             int(table.shape[0]), dim, C.c_void_p(row_ids.data_ptr()), n,
+                                             table.device.index or 0, C.c_void_p(stream))
+    _lib.check(status, "fcp_table_read_rows")
+    return out
+
+
+def update_from_host(table, ids_cpu, rows_cpu, chunk_rows: int = 1 << 16):
+    """A host delta — ``ids_cpu`` int64 ``[n]`` and ``rows_cpu`` float32 ``[n, dim]``, torch CPU tensors — into the device
+    ``table``, streamed through ONE pinned bounce buffer and one device buffer of ``chunk_rows`` rows (and as many ids), as
+    ``convert_from_host`` streams a table.  The copy of a chunk waits for the update of the one before; returns ``table``
+    after the last update is enqueued on torch's current stream."""
+    import torch
+    if ids_cpu.dtype != torch.int64 or ids_cpu.dim() != 1 or ids_cpu.is_cuda:
+        raise ValueError("update_from_host takes an int64 [n] tensor of ids on the host")
+    if rows_cpu.dtype != torch.float32 or rows_cpu.dim() != 2 or rows_cpu.is_cuda:
+        raise ValueError("update_from_host takes a float32 [n, dim] tensor of rows on the host")
+    if chunk_rows <= 0:
+        raise ValueError("chunk_rows must be positive")
+    _name, dim = _kind_and_dim(table, "table")
+    n = int(ids_cpu.shape[0])
+    if rows_cpu.shape[0] != n:
+        raise ValueError(f"rows has {rows_cpu.shape[0]} rows, ids names {n}")
+    if rows_cpu.shape[1] != dim:
+        raise ValueError(f"rows has rows of dim {rows_cpu.shape[1]}; the table's are of dim {dim}")
+    device = table.device
+    chunk = min(chunk_rows, max(n, 1))
+    bounce = torch.empty((chunk, dim), dtype=torch.float32, pin_memory=True)
+    bounce_ids = torch.empty((chunk,), dtype=torch.int64, pin_memory=True)
+    staged = torch.empty((chunk, dim), dtype=torch.float32, device=device)
+    staged_ids = torch.empty((chunk,), dtype=torch.int64, device=device)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device)
+        for r0 in range(0, n, chunk):
+            m = min(chunk, n - r0)
+            stream.synchronize()                      # the bounce buffers' last copies have left them
+            bounce[:m].copy_(rows_cpu[r0:r0 + m])
+            bounce_ids[:m].copy_(ids_cpu[r0:r0 + m])
+            staged[:m].copy_(bounce[:m], non_blocking=True)
+            staged_ids[:m].copy_(bounce_ids[:m], non_blocking=True)
+            update_rows(table, staged_ids[:m], staged[:m], stream=stream.cuda_stream)
+    return table
