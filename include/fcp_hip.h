@@ -213,7 +213,21 @@ enum {
    * are given; fcp_table_convert does, once, at load time.  Together with FCP_FLAG_TABLES_BF16 / _F16: FCP_ERR_INVALID_ARGUMENT.  Refused with FCP_ERR_UNSUPPORTED:
    * together with FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16, shard_world > 1, any column with per-id weights or
    * FCP_COMBINER_SQRTN. */
-  FCP_FLAG_TABLES_Q8 = 1u << 5
+  FCP_FLAG_TABLES_Q8 = 1u << 5,
+  /* Per-input table formats: the format is a property of each embedding table (device input), not of the plan.  Every
+   * column names its table's format in fcp_column_ext_t::table_kind1 (1 + FCP_TAB_*, 0 = float32); the field is read only
+   * with this bit (`ext` NULL: every table float32).  Columns that share a table_input must name the same kind (else
+   * FCP_ERR_INVALID_ARGUMENT, naming both columns); PASSTHROUGH / BATCH_COL_REDUCTION / EXTERNAL columns carry 0.  Together
+   * with FCP_FLAG_TABLES_BF16 / _F16 / _Q8: FCP_ERR_INVALID_ARGUMENT.  Each table follows its own format's rules, exactly as
+   * described above: layout, base alignment (4 * V | 2 * V | 2 * V | 4 bytes for float32 | bf16 | fp16 | q8), widening /
+   * dequantisation; the plan computes, bit for bit, what the float32 plan computes on the widened / dequantised tables.
+   * If ALL tables of the plan have one kind, the plan IS the plan-wide plan of that kind (the same kernels, the same
+   * fcp_plan_last_launch, fcp_plan_table_dtype and plan-file version).  A truly mixed plan reports FCP_TAB_MIXED and its
+   * kinds through fcp_plan_table_kinds; fcp_plan_table_bytes sums each table at its own row size, table shapes are checked
+   * against each table's own row width.  Refused with FCP_ERR_UNSUPPORTED ("per-input table formats ..."), as the
+   * plan-wide formats are: together with FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16, shard_world > 1, any column with per-id
+   * weights or FCP_COMBINER_SQRTN. */
+  FCP_FLAG_TABLES_PER_INPUT = 1u << 6
 };
 /* element type of the plan's outputs (fcp_plan_out_dtype) */
 enum { FCP_OUT_F32 = 0, FCP_OUT_BF16 = 1, FCP_OUT_F16 = 2 };
@@ -221,6 +235,9 @@ enum { FCP_OUT_F32 = 0, FCP_OUT_BF16 = 1, FCP_OUT_F16 = 2 };
 enum { FCP_TAB_F32 = 0, FCP_TAB_BF16 = 1, FCP_TAB_F16 = 2 };
 /* (FCP_FLAG_TABLES_Q8: uint8 codes with a float32 scale and bias behind every row) */
 enum { FCP_TAB_Q8 = 3 };
+/* (FCP_FLAG_TABLES_PER_INPUT: what fcp_plan_table_dtype answers for a plan whose tables have more than one format.  NOT a row
+ * format: fcp_table_convert, fcp_table_row_bytes and fcp_table_update_rows refuse it like any other unknown kind.) */
+enum { FCP_TAB_MIXED = 255 };
 /* A plan without device resources: layout / arena / table-byte queries and plan-file checks on a machine
  * without a GPU (offline graph tooling).  Anything that computes returns FCP_ERR_NO_DEVICE — there is no
  * CPU fallback.  (A macro: the value does not fit an int enumerator.) */
@@ -369,7 +386,11 @@ typedef struct fcp_column_ext {
   int32_t weights_input1;
   int64_t seg_map_mul[FCP_SEG_MAP_MAX];
   int64_t seg_map_div;
-  int64_t reserved1[2];
+  /* FCP_FLAG_TABLES_PER_INPUT only (never read without the bit): 1 + FCP_TAB_* of the table this column reads, 0 = float32;
+   * 0 for columns without a table */
+  int32_t table_kind1;
+  int32_t reserved0;
+  int64_t reserved1[1];
 } fcp_column_ext_t;
 /* `ext`: NULL, or one record per column of `desc`. */
 int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext, fcp_plan_t **plan);
@@ -394,7 +415,10 @@ int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext,
  *   version 7 files (plans with 16-bit tables, and only those) carry "table_dtype bf16" or
  *   "table_dtype f16" in the same place under the same rules (and no out_dtype line: the
  *   two features exclude each other); plans with 8-bit row-quantised tables are version 7
- *   files too and carry "table_dtype q8".
+ *   files too and carry "table_dtype q8"; version 8 files (plans whose tables have more than
+ *   one format, and only those) carry "table_dtypes D k0 ... k(D-1)" in that place under the
+ *   same rules: one of f32 | bf16 | f16 | q8 per device input, "-" for an input no lookup
+ *   column reads; plan-wide table bits in `flags` with such a file are FCP_ERR_INVALID_ARGUMENT.
  * `flags`: fcp_plan_desc_t::flags.  FCP_FLAG_OUT_BF16 / _F16 on a file without the
  * line select the dtype; bits that name the file's dtype are fine, the other dtype is
  * FCP_ERR_INVALID_ARGUMENT; FCP_FLAG_TABLES_BF16 / _F16 / _Q8 and a table_dtype line likewise.
@@ -415,13 +439,16 @@ int fcp_plan_output_columns(const fcp_plan_t *plan, int32_t *n, int32_t *indices
 /* FCP_OUT_*: the element type of the plan's outputs (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16). */
 int fcp_plan_out_dtype(const fcp_plan_t *plan, int32_t *out);
 /* FCP_TAB_*: the element type of the plan's embedding tables (FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16 /
- * FCP_FLAG_TABLES_Q8). */
+ * FCP_FLAG_TABLES_Q8); FCP_TAB_MIXED for a FCP_FLAG_TABLES_PER_INPUT plan whose tables have more than one format. */
 int fcp_plan_table_dtype(const fcp_plan_t *plan, int32_t *out);
+/* One FCP_TAB_* per device input (any plan), -1 for an input no lookup column reads: `kinds` receives up to `capacity`
+ * values, *n the number of device inputs (either may be NULL). */
+int fcp_plan_table_kinds(const fcp_plan_t *plan, int32_t *kinds, int32_t capacity, int32_t *n);
 /* Bytes of embedding tables this plan reads on THIS device (its shard of every
  * table, shared tables counted once) and the largest single table's bytes
  * (unsharded) — the inputs of the placement gate, fcp_placement_decide; 2 bytes per
  * element in a plan with 16-bit tables, dim + 8 bytes per row in a plan with 8-bit
- * row-quantised tables. */
+ * row-quantised tables, each table at its own row size in a plan with per-input formats. */
 int fcp_plan_table_bytes(const fcp_plan_t *plan, int64_t *shard_bytes,
                          int64_t *max_table_bytes_unsharded);
 
@@ -575,7 +602,9 @@ enum {
   /* the 16-bit-table instantiations of the three (FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16 plans) */
   FCP_LAUNCH_DENSE_TAB16 = 8, FCP_LAUNCH_RAGGED_TAB16 = 9, FCP_LAUNCH_HYBRID_TAB16 = 10,
   /* the 8-bit row-quantised-table instantiations of the three (FCP_FLAG_TABLES_Q8 plans) */
-  FCP_LAUNCH_DENSE_TABQ8 = 11, FCP_LAUNCH_RAGGED_TABQ8 = 12, FCP_LAUNCH_HYBRID_TABQ8 = 13
+  FCP_LAUNCH_DENSE_TABQ8 = 11, FCP_LAUNCH_RAGGED_TABQ8 = 12, FCP_LAUNCH_HYBRID_TABQ8 = 13,
+  /* the per-input-format instantiations of the three (FCP_FLAG_TABLES_PER_INPUT plans whose tables really differ) */
+  FCP_LAUNCH_DENSE_TABMIX = 14, FCP_LAUNCH_RAGGED_TABMIX = 15, FCP_LAUNCH_HYBRID_TABMIX = 16
 };
 enum { FCP_LAUNCH_STORE_NT = 0, FCP_LAUNCH_STORE_SC1_NT = 1, FCP_LAUNCH_STORE_PLAIN = 4 };
 enum { FCP_LAUNCH_SEG_NONE = 0, FCP_LAUNCH_SEG_PREPASS = 1, FCP_LAUNCH_SEG_SEARCH = 2 };

@@ -625,6 +625,36 @@ __device__ __forceinline__ uint32_t fetch_slot_offset(const LdsCol &c, const Fcp
   return slot_offset_from_raw<V, SHARDED>(c, xf, lo, hi, lds_bnd, rank, world, bad);
 }
 
+// ---- per-input table formats (fcp_tables_mixed.hip: FCP_FLAG_TABLES_PER_INPUT plans whose tables really differ) ------------
+// The R reads of one lane of the dense body by the kind of its column's table (FCP_TAB_*): the three loader families above,
+// each with all its R reads in flight.  `table`: the table's base; `e`: the lane's element offset in the row.  Called with a
+// scalar `kind` where the wave holds one kind (the branches are then scalar), with the lane's own otherwise (three
+// exec-masked sections, each skipped when no lane takes it).
+template <int V, int R>
+__device__ __forceinline__ void ld_rows_mixed(VF<V> (&v)[R], const uint32_t (&off)[R], int kind, const char *table, int e, int dim, bool wide) {
+#pragma unroll
+  for (int r = 0; r < R; ++r) v[r] = vzero<V>();
+  if (kind == FCP_TAB_F32) {
+    const float *tb = reinterpret_cast<const float *>(table) + e;
+    const uint32_t spr = (uint32_t)(dim / V);
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      if (is_row(off[r])) v[r] = wide ? ld_slot<V>(tb, off[r], spr) : ld_slot32<V>(tb, off[r]);
+  } else if (kind == FCP_TAB_Q8) {
+    const char *tb8 = table + e; // the lane's codes in row 0; the scale dim - e behind
+    const int tail = dim - e;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      if (is_row(off[r])) v[r] = wide ? ld_slot_q8<V>(tb8, tail, off[r], (uint32_t)dim + 8u) : ld_slot32_q8<V>(tb8, tail, off[r]);
+  } else {
+    const char *tb16 = table + 2 * (int64_t)e; // element offset x 2, in 64 bits
+    const uint32_t spr = (uint32_t)(dim / V);
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      if (is_row(off[r])) v[r] = wide ? ld_slot16<V>(tb16, off[r], spr, kind) : ld_slot32_16<V>(tb16, off[r], kind);
+  }
+}
+
 // Common block header: which group / span / row tile this block owns.
 struct BlockPos {
   int rows, nslots, q0, row_blk, ncols;
@@ -711,7 +741,11 @@ template <int R> struct DenseLds {
 // TABQ8: the instantiation for 8-bit row-quantised table plans (fcp_tables_q8.hip).  The table address and the load differ,
 // and a row index is scaled by the row stride in slots, (dim + 8) / V, where the float32 plan scales by dim / V; all behind
 // `if constexpr (TABQ8)`.
-template <int V, int R, bool SHARDED, bool NARROW = false, bool TAB16 = false, bool TABQ8 = false>
+// TABMIX: the instantiation for plans whose tables have more than one format (fcp_tables_mixed.hip).  The kind is a fact of each
+// COLUMN (FCP_F_TABKIND of its record's flags: a 64-slot span routinely holds columns of different formats), so the row stride
+// that scales a row index and the loader are chosen per lane — wave-uniformly where one ballot shows that the whole wave
+// holds one kind; all behind `if constexpr (TABMIX)`.
+template <int V, int R, bool SHARDED, bool NARROW = false, bool TAB16 = false, bool TABQ8 = false, bool TABMIX = false>
 __device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *smem, int out_kind = 0, int tab_kind = 0) {
   constexpr int RB = DenseLds<R>::RB, IDS = DenseLds<R>::IDS, BND = DenseLds<R>::BND;
   DenseLds<R> &S = *reinterpret_cast<DenseLds<R> *>(smem);
@@ -820,7 +854,9 @@ __device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *sm
         off = slot_offset_from_raw<V, SHARDED>(c, L.xforms + B.first_col + j, raw_lo[h], raw_hi[h],
                                                c.bnd_off >= 0 ? s_bnd + c.bnd_off : nullptr,
                                                rank, world, bad);
-        if constexpr (TABQ8) {
+        if constexpr (TABMIX) { // the stride of THIS column's format: (dim + 8) / V for a q8 table, dim / V for the others
+          if (!wide && is_row(off)) off *= (uint32_t)((c.dim + (FCP_F_TABKIND(pflags[h]) == FCP_TAB_Q8 ? 8 : 0)) / V);
+        } else if constexpr (TABQ8) {
           if (!wide && is_row(off)) off *= (uint32_t)((c.dim + 8) / V); // the row STRIDE in slots: offset x V = the row's byte offset
         } else {
           if (!wide && is_row(off)) off *= (uint32_t)(c.dim / V); // every table of the plan has < 2^32 - 3 slots: pre-scaled
@@ -849,8 +885,17 @@ __device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *sm
 #pragma unroll
   for (int r = 0; r < R; ++r) off[r] = s_off[j * IDS + r0 + r];
   VF<V> v[R];
+  if constexpr (TABMIX) {
+    // (a PASSTHROUGH column carries kind 0 and its "table" is its float32 payload: the float32 path)
+    const int kind = (int)FCP_F_TABKIND(s_col[j].flags), k0 = __builtin_amdgcn_readfirstlane(kind);
+    const char *table = reinterpret_cast<const char *>(s_col[j].table);
+    if (__ballot(kind != k0) == 0ull)
+      ld_rows_mixed<V, R>(v, off, k0, table, e, s_col[j].dim, wide); // one kind in the whole wave: scalar branches
+    else
+      ld_rows_mixed<V, R>(v, off, kind, table, e, s_col[j].dim, wide);
+  }
 #pragma unroll
-  for (int r = 0; r < R; ++r) {
+  for (int r = 0; r < (TABMIX ? 0 : R); ++r) { // (TABMIX: read above, by kind)
     v[r] = vzero<V>();
     if constexpr (TAB16) {
       if (FCP_F_FORM(s_col[j].flags) != FCP_FORM_PASSTHROUGH) {
@@ -1163,11 +1208,15 @@ struct RaggedLds {
 // together with WEIGHTED (such plans are refused when they are created).
 // TABQ8: as in the dense body — 8-bit row-quantised table plans (fcp_tables_q8.hip), everything behind `if constexpr (TABQ8)`;
 // never together with WEIGHTED either.
-template <int V, bool SHARDED, bool WEIGHTED = false, bool NARROW = false, bool TAB16 = false, bool TABQ8 = false>
+// TABMIX: as in the dense body — plans whose tables have more than one format (fcp_tables_mixed.hip): the lane's column names
+// its kind (FCP_F_TABKIND), the walk is the float32, the 16-bit or the q8 walk accordingly; everything behind
+// `if constexpr (TABMIX)`; never together with WEIGHTED either.
+template <int V, bool SHARDED, bool WEIGHTED = false, bool NARROW = false, bool TAB16 = false, bool TABQ8 = false, bool TABMIX = false>
 __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *smem, const int64_t *wts = nullptr, int out_kind = 0,
                                             int tab_kind = 0) {
   static_assert(!(TAB16 && WEIGHTED), "the weighted walk reads float32 tables");
   static_assert(!(TABQ8 && (WEIGHTED || TAB16)), "one table format per instantiation; the weighted walk reads float32 tables");
+  static_assert(!(TABMIX && (WEIGHTED || TAB16 || TABQ8)), "per-column kinds replace the plan-wide ones; the weighted walk reads float32 tables");
   constexpr int RB = RaggedLds::RB, CAPW = RaggedLds::CAPW;
   RaggedLds &S = *reinterpret_cast<RaggedLds *>(smem);
   LdsCol *s_col = S.col;
@@ -1325,6 +1374,18 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
       q8_tail = s_col[j].dim - e;
       spr = (uint32_t)s_col[j].dim + 8u;
     }
+    int kind = 0; // TABMIX: FCP_TAB_* of this lane's table; `tb`, `spr` and `q8_tail` as that format's walk takes them
+    if constexpr (TABMIX) {
+      kind = (int)FCP_F_TABKIND(s_col[j].flags);
+      const int e = q * V - s_col[j].out_off;
+      if (kind == FCP_TAB_Q8) {
+        tb = reinterpret_cast<const float *>(reinterpret_cast<const char *>(s_col[j].table) + e);
+        q8_tail = s_col[j].dim - e;
+        spr = (uint32_t)s_col[j].dim + 8u;
+      } else if (kind != FCP_TAB_F32) {
+        tb = reinterpret_cast<const float *>(reinterpret_cast<const char *>(s_col[j].table) + 2 * (int64_t)e);
+      }
+    }
     if (form == FCP_FORM_SEGMENT_REDUCE) {
       if ((s_col[j].xform & 3u) == FCP_XFORM_FILTER && (FCP_F_COMBINER(s_col[j].flags) == FCP_COMBINER_MEAN ||
                                                         (WEIGHTED && FCP_F_COMBINER(s_col[j].flags) == FCP_COMBINER_SQRTN))) {
@@ -1341,6 +1402,22 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
         } else { // (no wider than kWalkLong: next to the weight pointer and the denominator a 10-wide batch spills at V = 4)
           bag_walk_sum<V, (WALK < kWalkLong ? WALK : kWalkLong)>(tb, H.zeros, spr, s, n, acc);
         }
+      } else if constexpr (TABMIX) {
+        // the walk of the lane's kind; the votes inside a walk count the lanes of that kind only.  One ballot tells whether
+        // the wave's pooled lanes hold one kind: then the choice is a scalar branch and the 16-bit widening knows its type
+        auto walk = [&](int k) __attribute__((always_inline)) {
+          if (k == FCP_TAB_F32)
+            bag_walk_sum<V, WALK>(tb, H.zeros, spr, s, n, acc);
+          else if (k == FCP_TAB_Q8)
+            bag_walk_sum<V, WALK, false, true>(tb, H.zeros, spr, s, n, acc, 0, q8_tail);
+          else
+            bag_walk_sum<V, WALK, true>(tb, H.zeros, spr, s, n, acc, k);
+        };
+        const int k0 = __builtin_amdgcn_readfirstlane(kind);
+        if (__ballot(kind != k0) == 0ull)
+          walk(k0);
+        else
+          walk(kind);
       } else if constexpr (TABQ8) {
         bag_walk_sum<V, WALK, false, true>(tb, H.zeros, spr, s, n, acc, 0, q8_tail);
       } else if constexpr (TAB16) {
@@ -1356,7 +1433,16 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
       const uint32_t off = s[k];
       if (off != kFiltered) {
         acc = vzero<V>();
-        if constexpr (TABQ8) {
+        if constexpr (TABMIX) {
+          if (is_row(off)) {
+            if (kind == FCP_TAB_F32)
+              acc = ld_slot<V>(tb, off, spr);
+            else if (kind == FCP_TAB_Q8)
+              acc = ld_slot_q8<V>(reinterpret_cast<const char *>(tb), q8_tail, off, spr);
+            else
+              acc = ld_slot16<V>(reinterpret_cast<const char *>(tb), off, spr, kind);
+          }
+        } else if constexpr (TABQ8) {
           if (is_row(off)) acc = ld_slot_q8<V>(reinterpret_cast<const char *>(tb), q8_tail, off, spr);
         } else if constexpr (TAB16) {
           if (is_row(off)) acc = ld_slot16<V>(reinterpret_cast<const char *>(tb), off, spr, tab_kind);

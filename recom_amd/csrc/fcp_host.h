@@ -291,6 +291,17 @@ struct fcp_plan {
   // every row.  Geometry stays in elements; the row STRIDE in slots, (dim + 8) / vec, is what scales a row index and what
   // wide_rows is decided from
   int tab_row_tail = 0;
+  // Per-input table formats (FCP_FLAG_TABLES_PER_INPUT) whose tables really differ: tab_kind FCP_TAB_MIXED, tab_elem 0, and the
+  // kind of every column's table (FCP_TAB_*, by plan column; FCP_TAB_F32 for columns without one) — it rides in bits 16..17
+  // of the column record's flags.  Plans whose tables all have one kind are the plan-wide plan of that kind: col_kind empty.
+  std::vector<int8_t> col_kind;
+  bool tab_mixed() const { return !col_kind.empty(); }
+  int col_tab_kind(size_t k) const { return col_kind.empty() ? tab_kind : col_kind[k]; }
+  // bytes of one row of the table column k reads
+  int64_t col_row_bytes(size_t k, int dim) const {
+    const int kind = col_tab_kind(k);
+    return kind == FCP_TAB_F32 ? 4 * (int64_t)dim : kind == FCP_TAB_Q8 ? (int64_t)dim + 8 : 2 * (int64_t)dim;
+  }
   std::vector<FcpColStatic> h_cols;
   char *d_const = nullptr;
   int32_t *d_seg_cols = nullptr;

@@ -25,6 +25,9 @@
 #define FCP_F_COMBINER(f) (((f) >> 4) & 0xFu)
 #define FCP_F_IDSRC(f) (((f) >> 8) & 0xFu)
 #define FCP_F_SEGKIND(f) (((f) >> 12) & 0xFu)
+// bits 16..17: FCP_TAB_* of the column's table — set in plans with per-input table formats only (FCP_FLAG_TABLES_PER_INPUT,
+// tables that really differ; fcp_tables_mixed.hip), zero everywhere else: the kind travels with the record, no record grows
+#define FCP_F_TABKIND(f) (((f) >> 16) & 0x3u)
 #define FCP_F_PACK(form, comb, idsrc, segkind) \
   ((uint32_t)(form) | ((uint32_t)(comb) << 4) | ((uint32_t)(idsrc) << 8) | ((uint32_t)(segkind) << 12))
 
@@ -210,6 +213,11 @@ int fcp_launch_tab16_hybrid(const FcpLaunch &Ldense, int dense_blocks, const Fcp
 int fcp_launch_tabq8(const FcpLaunch &L, int vec, bool dense_kernel, int grid_blocks, ihipStream_t *s);
 int fcp_launch_tabq8_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch &Lragged, int ragged_blocks, int vec,
                             ihipStream_t *s);
+// (fcp_tables_mixed.hip) the same for plans whose tables have more than one format (FCP_FLAG_TABLES_PER_INPUT): the kind is a
+// fact of each column record (FCP_F_TABKIND)
+int fcp_launch_tabmix(const FcpLaunch &L, int vec, bool dense_kernel, int grid_blocks, ihipStream_t *s);
+int fcp_launch_tabmix_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch &Lragged, int ragged_blocks, int vec,
+                             ihipStream_t *s);
 // (fcp_dense_plain.hip) the small dense kernel of plain dense plans: V 4, R 4, the grid of fcp_launch_fused's dense kernel
 int fcp_launch_dense_plain(const FcpPlainLaunch &P, int grid_blocks, ihipStream_t *s);
 // what the next fused launch of this thread would carry (stop event, any-order flag): taken and cleared

@@ -232,6 +232,56 @@ int validate_tables_q8(const fcp_plan_desc_t *d, const fcp_column_ext_t *ext) {
   return FCP_OK;
 }
 
+// Per-input table formats (FCP_FLAG_TABLES_PER_INPUT): the kind of every column's table from fcp_column_ext_t::table_kind1.
+// `col_kind` receives one FCP_TAB_* per column (FCP_TAB_F32 for columns without a table), `uniform` the one kind all tables of
+// the plan share, or -1 when they really differ.
+int resolve_table_kinds(const fcp_plan_desc_t *d, const fcp_column_ext_t *ext, std::vector<int8_t> *col_kind, int *uniform) {
+  if (d->flags & (FCP_FLAG_TABLES_BF16 | FCP_FLAG_TABLES_F16 | FCP_FLAG_TABLES_Q8))
+    return fail(FCP_ERR_INVALID_ARGUMENT, "FCP_FLAG_TABLES_PER_INPUT and FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16 / FCP_FLAG_TABLES_Q8 exclude each other");
+  std::vector<int> in_kind(d->n_device_inputs, -1), in_col(d->n_device_inputs, -1);
+  col_kind->assign(d->n_columns, (int8_t)FCP_TAB_F32);
+  *uniform = -2; // no table seen yet
+  for (int k = 0; k < d->n_columns; ++k) {
+    const fcp_column_desc_t &c = d->columns[k];
+    const std::string where = "column " + std::to_string(k) + ": ";
+    const int kind1 = ext ? ext[k].table_kind1 : 0;
+    if (kind1 < 0 || kind1 > 1 + FCP_TAB_Q8) return fail(FCP_ERR_INVALID_ARGUMENT, where + "table_kind1 is no 1 + FCP_TAB_* value");
+    const bool lookup = c.form == FCP_FORM_GATHER || c.form == FCP_FORM_SEGMENT_REDUCE || c.form == FCP_FORM_GATHER_SCATTER;
+    if (!lookup) {
+      if (kind1 != 0) return fail(FCP_ERR_INVALID_ARGUMENT, where + "a column without a table carries table_kind1 0");
+      continue;
+    }
+    const int kind = kind1 ? kind1 - 1 : FCP_TAB_F32, t = c.table_input;
+    if (in_kind[t] >= 0 && in_kind[t] != kind)
+      return fail(FCP_ERR_INVALID_ARGUMENT, "columns " + std::to_string(in_col[t]) + " and " + std::to_string(k) + " share table input " +
+                                                std::to_string(t) + " but name different table kinds");
+    if (in_kind[t] < 0) {
+      in_kind[t] = kind;
+      in_col[t] = k;
+    }
+    (*col_kind)[k] = (int8_t)kind;
+    *uniform = *uniform == -2 || *uniform == kind ? kind : -1;
+  }
+  if (*uniform == -2) *uniform = FCP_TAB_F32; // a plan without tables
+  return FCP_OK;
+}
+
+// ... whose tables really differ: the refusals of the plan-wide formats, by name, for the kernels of fcp_tables_mixed.hip.
+int validate_tables_mixed(const fcp_plan_desc_t *d, const fcp_column_ext_t *ext) {
+  if (d->flags & (FCP_FLAG_OUT_BF16 | FCP_FLAG_OUT_F16))
+    return fail(FCP_ERR_UNSUPPORTED, "per-input table formats with narrow output (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16): the mixed-table kernels store float32");
+  if (d->shard_world > 1)
+    return fail(FCP_ERR_UNSUPPORTED, "per-input table formats on a row-sharded plan (shard_world > 1): the sharded kernels read float32 tables");
+  for (int k = 0; k < d->n_columns; ++k) {
+    const std::string where = "column " + std::to_string(k) + ": ";
+    if (ext && ext[k].weights_input1 > 0)
+      return fail(FCP_ERR_UNSUPPORTED, where + "per-input table formats with per-id weights: weighted plans take the float32 weighted kernel");
+    if (d->columns[k].combiner == FCP_COMBINER_SQRTN && d->columns[k].form == FCP_FORM_SEGMENT_REDUCE)
+      return fail(FCP_ERR_UNSUPPORTED, where + "per-input table formats with FCP_COMBINER_SQRTN: sqrtn plans take the float32 weighted kernel");
+  }
+  return FCP_OK;
+}
+
 // Run-time shapes -> per-column dynamic records, arena layout and launch
 // geometry.  Mirrors what the generated host code evaluates per call from
 // SymEngine expressions (cuda_emitter.cc:2151-2179, :2410-2455).
@@ -808,6 +858,7 @@ int init_device(fcp_plan *p) {
     s.dim = hc.d.dim;
     s.out_off = hc.out_off;
     s.flags = FCP_F_PACK(hc.d.form, hc.d.combiner, hc.d.id_source, hc.d.seg_kind);
+    if (p->tab_mixed()) s.flags |= (uint32_t)p->col_kind[p->order[pos]] << 16; // FCP_F_TABKIND: read by the mixed-table kernels only
     s.n_boundaries = (int32_t)hc.boundaries.size();
     s.seg_stride = hc.d.seg_stride < 1 ? 1 : hc.d.seg_stride;
     s.bnd_b0 = 0.0f;
@@ -874,8 +925,9 @@ int init_device(fcp_plan *p) {
   // (8-bit row-quantised tables: a skipped id reads zero codes AND, dim - e bytes behind them, a zero scale and bias: the
   // line is as long as the plan's longest row)
   size_t zero_bytes = 256;
-  if (p->tab_row_tail)
-    for (const auto &hc : p->cols) zero_bytes = std::max(zero_bytes, (size_t)((hc.d.dim + p->tab_row_tail + 255) / 256 * 256));
+  if (p->tab_row_tail || p->tab_mixed())
+    for (size_t k = 0; k < p->cols.size(); ++k)
+      if (p->col_tab_kind(k) == FCP_TAB_Q8) zero_bytes = std::max(zero_bytes, (size_t)((p->cols[k].d.dim + 8 + 255) / 256 * 256));
   HIP_TRY(hipMalloc(&p->d_zeros, zero_bytes));
   HIP_TRY(hipMemset(p->d_zeros, 0, zero_bytes));
   if (p->desc.flags & FCP_FLAG_COUNT_BAD_IDS) {
@@ -955,11 +1007,33 @@ int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext,
   int rc = validate_desc(desc);
   if (rc) return rc;
   if (ext && (rc = validate_ext(desc, ext))) return rc;
+  // Per-input table formats: tables that all share one kind make this the plan-wide plan of that kind — the descriptor is
+  // rewritten to that plan's flags here, and nothing behind this point knows the difference.  Only tables that really
+  // differ keep their per-column kinds (col_kind) and take the mixed-table kernels.
+  fcp_plan_desc_t canonical;
+  std::vector<int8_t> col_kind;
+  if (desc->flags & FCP_FLAG_TABLES_PER_INPUT) {
+    int uniform = -1;
+    if ((rc = resolve_table_kinds(desc, ext, &col_kind, &uniform))) return rc;
+    canonical = *desc;
+    canonical.flags &= ~(uint32_t)FCP_FLAG_TABLES_PER_INPUT;
+    if (uniform >= 0) {
+      col_kind.clear();
+      canonical.flags |= uniform == FCP_TAB_BF16 ? FCP_FLAG_TABLES_BF16 : uniform == FCP_TAB_F16 ? FCP_FLAG_TABLES_F16 : uniform == FCP_TAB_Q8 ? FCP_FLAG_TABLES_Q8 : 0u;
+    }
+    desc = &canonical;
+  }
   if ((rc = validate_narrow(desc, ext))) return rc;
+  if (!col_kind.empty() && (rc = validate_tables_mixed(desc, ext))) return rc;
   if ((rc = validate_tables_q8(desc, ext))) return rc;
   if ((rc = validate_tables16(desc, ext))) return rc;
   fcp_plan *p = new (std::nothrow) fcp_plan();
   if (!p) return fail(FCP_ERR_ALLOC, "out of host memory");
+  if (!col_kind.empty()) {
+    p->tab_kind = FCP_TAB_MIXED;
+    p->tab_elem = 0; // (no plan-wide element size: col_row_bytes)
+    p->col_kind.swap(col_kind);
+  }
   if (desc->flags & (FCP_FLAG_OUT_BF16 | FCP_FLAG_OUT_F16)) {
     p->out_kind = (desc->flags & FCP_FLAG_OUT_BF16) ? FCP_OUT_BF16 : FCP_OUT_F16;
     p->out_elem = 2;
@@ -1061,7 +1135,9 @@ int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext,
       return fail(FCP_ERR_UNSUPPORTED, "column " + std::to_string(k) + ": table shard exceeds 2^32 - 3 rows");
     }
     // (8-bit row-quantised tables: a row index is scaled by the row STRIDE in slots, (dim + 8) / vec — vec divides 8)
-    if (local_vocab * ((c.dim + p->tab_row_tail) / p->vec) >= 0xFFFFFFFDLL || wide_rows_forced) p->wide_rows = true;
+    // (per-input formats: the table's own kind decides)
+    const int row_tail = p->tab_mixed() ? (p->col_kind[k] == FCP_TAB_Q8 ? 8 : 0) : p->tab_row_tail;
+    if (local_vocab * ((c.dim + row_tail) / p->vec) >= 0xFFFFFFFDLL || wide_rows_forced) p->wide_rows = true;
   }
   // concat layout: offsets = prefix sums of dims in slot order
   // (concat_outputs_op_gpu.cu.cc:74-79)
@@ -1170,6 +1246,7 @@ struct ParsedPlanFile {
   bool has_stage = false;
   int out_kind = FCP_OUT_F32; // the "out_dtype" line (version 6)
   int tab_kind = FCP_TAB_F32; // the "table_dtype" line (version 7)
+  std::vector<int> in_kinds;  // the "table_dtypes" line (version 8): FCP_TAB_* per device input, -1 = "-"
 };
 
 int parse_plan_file(const char *path, ParsedPlanFile &P) {
@@ -1184,9 +1261,21 @@ int parse_plan_file(const char *path, ParsedPlanFile &P) {
   int version = 0, n_host = 0, n_cols = 0;
   fcp_plan_desc_t &d = P.d;
   std::memset(&d, 0, sizeof(d));
-  if (std::fscanf(f, "%31s %d", tag, &version) != 2 || std::strcmp(tag, "fcp_plan") || version < 1 || version > 7)
+  if (std::fscanf(f, "%31s %d", tag, &version) != 2 || std::strcmp(tag, "fcp_plan") || version < 1 || version > 8)
     return fail(FCP_ERR_INVALID_ARGUMENT, where + "bad header");
-  if (version >= 7) { // plans with 16-bit tables: "table_dtype bf16|f16", under the rules of version 6's line, which they never carry
+  if (version >= 8) { // plans whose tables have more than one format: "table_dtypes D k0 ... k(D-1)", under the same rules
+    int n_kinds = -1;
+    if (std::fscanf(f, "%31s %d", tag, &n_kinds) != 2 || std::strcmp(tag, "table_dtypes") || n_kinds < 0 || n_kinds > (1 << 24))
+      return fail(FCP_ERR_INVALID_ARGUMENT, where + "expected 'table_dtypes D k0 ... k(D-1)'");
+    P.in_kinds.resize(n_kinds);
+    for (int t = 0; t < n_kinds; ++t) {
+      if (std::fscanf(f, "%31s", t2) != 1) return fail(FCP_ERR_INVALID_ARGUMENT, where + "truncated table_dtypes line");
+      const int kind = !std::strcmp(t2, "f32") ? FCP_TAB_F32 : !std::strcmp(t2, "bf16") ? FCP_TAB_BF16 : !std::strcmp(t2, "f16") ? FCP_TAB_F16
+                       : !std::strcmp(t2, "q8") ? FCP_TAB_Q8 : !std::strcmp(t2, "-") ? -1 : -2;
+      if (kind == -2) return fail(FCP_ERR_INVALID_ARGUMENT, where + "unknown table dtype '" + t2 + "' in the table_dtypes line");
+      P.in_kinds[t] = kind;
+    }
+  } else if (version >= 7) { // plans with 16-bit tables: "table_dtype bf16|f16", under the rules of version 6's line, which they never carry
     if (std::fscanf(f, "%31s %31s", tag, t2) != 2 || std::strcmp(tag, "table_dtype") ||
         (std::strcmp(t2, "bf16") && std::strcmp(t2, "f16") && std::strcmp(t2, "q8")))
       return fail(FCP_ERR_INVALID_ARGUMENT, where + "expected 'table_dtype bf16', 'table_dtype f16' or 'table_dtype q8'");
@@ -1201,6 +1290,9 @@ int parse_plan_file(const char *path, ParsedPlanFile &P) {
   if (std::fscanf(f, "%31s %d %31s %d %31s %d", tag, &d.n_groups, t2, &d.n_symbols, t3, &d.n_device_inputs) != 6 ||
       std::strcmp(tag, "groups") || std::strcmp(t2, "symbols") || std::strcmp(t3, "device_inputs"))
     return fail(FCP_ERR_INVALID_ARGUMENT, where + "expected 'groups G symbols S device_inputs D'");
+  if (version >= 8 && (int)P.in_kinds.size() != d.n_device_inputs)
+    return fail(FCP_ERR_INVALID_ARGUMENT, where + "the table_dtypes line names " + std::to_string(P.in_kinds.size()) + " inputs, the plan has " +
+                                              std::to_string(d.n_device_inputs) + " device inputs");
   if (std::fscanf(f, "%31s %d", tag, &n_host) != 2 || std::strcmp(tag, "host_inputs") || n_host < 0 || n_host > (1 << 24))
     return fail(FCP_ERR_INVALID_ARGUMENT, where + "expected 'host_inputs N'");
   P.ranks.resize(n_host);
@@ -1303,6 +1395,27 @@ int parse_plan_file(const char *path, ParsedPlanFile &P) {
       return fail(FCP_ERR_INVALID_ARGUMENT, where + "unexpected section '" + tag + "'");
     }
   }
+  if (version >= 8) { // the kinds travel to fcp_plan_create_ex as every column's table_kind1
+    if (P.ext.empty()) P.ext.assign(n_cols, fcp_column_ext_t{});
+    std::vector<char> read(P.in_kinds.size(), 0);
+    int first = -1;
+    bool differ = false;
+    for (int k = 0; k < n_cols; ++k) {
+      const fcp_column_desc_t &c = P.cols[k];
+      if (c.form != FCP_FORM_GATHER && c.form != FCP_FORM_SEGMENT_REDUCE && c.form != FCP_FORM_GATHER_SCATTER) continue;
+      if (c.table_input < 0 || c.table_input >= (int)P.in_kinds.size() || P.in_kinds[c.table_input] < 0)
+        return fail(FCP_ERR_INVALID_ARGUMENT, where + "column " + std::to_string(k) + " reads a table the table_dtypes line gives no dtype");
+      read[c.table_input] = 1;
+      const int kind = P.in_kinds[c.table_input];
+      P.ext[k].table_kind1 = 1 + kind;
+      differ = differ || (first >= 0 && kind != first);
+      if (first < 0) first = kind;
+    }
+    for (size_t t = 0; t < read.size(); ++t)
+      if (!read[t] && P.in_kinds[t] >= 0)
+        return fail(FCP_ERR_INVALID_ARGUMENT, where + "the table_dtypes line gives device input " + std::to_string(t) + ", which no lookup column reads, a dtype");
+    if (!differ) return fail(FCP_ERR_INVALID_ARGUMENT, where + "version 8 is for plans whose tables have more than one dtype; this one is a version <= 7 plan");
+  }
   d.abi_version = FCP_ABI_VERSION;
   d.n_columns = n_cols;
   d.columns = P.cols.data();
@@ -1338,6 +1451,11 @@ int fcp_plan_create_from_file(const char *path, int32_t device, uint32_t flags, 
     if (flags & (FCP_FLAG_TABLES_BF16 | FCP_FLAG_TABLES_F16 | FCP_FLAG_TABLES_Q8) & ~file_bit)
       return fail(FCP_ERR_INVALID_ARGUMENT, std::string("column plan ") + path + ": flags ask for another table dtype than the file's table_dtype line");
     P.d.flags |= file_bit;
+  }
+  if (!P.in_kinds.empty()) { // a version-8 file names every table's dtype: plan-wide table bits contradict it
+    if (flags & (FCP_FLAG_TABLES_BF16 | FCP_FLAG_TABLES_F16 | FCP_FLAG_TABLES_Q8))
+      return fail(FCP_ERR_INVALID_ARGUMENT, std::string("column plan ") + path + ": plan-wide table dtype flags with a file that carries a table_dtypes line");
+    P.d.flags |= FCP_FLAG_TABLES_PER_INPUT;
   }
   return fcp_plan_create_ex(&P.d, P.ext.empty() ? nullptr : P.ext.data(), out);
 }
@@ -1393,17 +1511,32 @@ int fcp_plan_table_dtype(const fcp_plan_t *p, int32_t *out) {
   return FCP_OK;
 }
 
+int fcp_plan_table_kinds(const fcp_plan_t *p, int32_t *kinds, int32_t capacity, int32_t *n) {
+  if (!p) return fail(FCP_ERR_INVALID_ARGUMENT, "null plan");
+  std::vector<int32_t> in_kind(p->desc.n_device_inputs, -1);
+  for (size_t k = 0; k < p->cols.size(); ++k) {
+    const int f = p->cols[k].d.form;
+    if (f == FCP_FORM_GATHER || f == FCP_FORM_SEGMENT_REDUCE || f == FCP_FORM_GATHER_SCATTER) in_kind[p->cols[k].d.table_input] = p->col_tab_kind(k);
+  }
+  for (int32_t t = 0; t < p->desc.n_device_inputs && t < capacity; ++t)
+    if (kinds) kinds[t] = in_kind[t];
+  if (n) *n = p->desc.n_device_inputs;
+  return FCP_OK;
+}
+
 int fcp_plan_table_bytes(const fcp_plan_t *p, int64_t *shard_bytes, int64_t *max_table_bytes_unsharded) {
   if (!p) return fail(FCP_ERR_INVALID_ARGUMENT, "null plan");
   // a table input may feed several columns (shared embeddings): count each once
   std::vector<int64_t> local(p->desc.n_device_inputs, 0), whole(p->desc.n_device_inputs, 0);
-  for (const HostColumn &hc : p->cols) {
+  for (size_t k = 0; k < p->cols.size(); ++k) {
+    const HostColumn &hc = p->cols[k];
     const int f = hc.d.form;
     if (f != FCP_FORM_GATHER && f != FCP_FORM_SEGMENT_REDUCE && f != FCP_FORM_GATHER_SCATTER) continue;
     const int64_t local_vocab =
         (hc.d.vocab - p->desc.shard_rank + p->desc.shard_world - 1) / p->desc.shard_world;
-    local[hc.d.table_input] = std::max(local[hc.d.table_input], local_vocab * (hc.d.dim * p->tab_elem + p->tab_row_tail));
-    whole[hc.d.table_input] = std::max(whole[hc.d.table_input], hc.d.vocab * (hc.d.dim * p->tab_elem + p->tab_row_tail));
+    const int64_t row_bytes = p->col_row_bytes(k, hc.d.dim); // (per-input formats: each table at its own row size)
+    local[hc.d.table_input] = std::max(local[hc.d.table_input], local_vocab * row_bytes);
+    whole[hc.d.table_input] = std::max(whole[hc.d.table_input], hc.d.vocab * row_bytes);
   }
   int64_t sum = 0, mx = 0;
   for (int t = 0; t < p->desc.n_device_inputs; ++t) {

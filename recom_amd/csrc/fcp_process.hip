@@ -285,15 +285,16 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
   if (p->desc.n_device_inputs > 0 && !a->input_ptrs) return fail(FCP_ERR_INVALID_ARGUMENT, "null input_ptrs");
   if (p->desc.n_symbols > 0 && !a->symbols) return fail(FCP_ERR_INVALID_ARGUMENT, "plan needs symbols");
   if (a->input_shapes) { // optional cross-check of the table shapes
-    for (const HostColumn &hc : p->cols) {
+    for (size_t k = 0; k < p->cols.size(); ++k) {
+      const HostColumn &hc = p->cols[k];
       const int f = hc.d.form;
       if (f == FCP_FORM_PASSTHROUGH || f == FCP_FORM_BATCH_COL_REDUCTION || f == FCP_FORM_EXTERNAL) continue;
       const int32_t *s = a->input_shapes + 2 * hc.d.table_input;
       const int64_t local_vocab = p->desc.shard_world > 1
                                       ? (hc.d.vocab - p->desc.shard_rank + p->desc.shard_world - 1) / p->desc.shard_world
                                       : hc.d.vocab;
-      // (8-bit row-quantised tables: a row is dim codes and 8 bytes of scale and bias)
-      if (s[0] != local_vocab || s[1] != hc.d.dim + p->tab_row_tail)
+      // (8-bit row-quantised tables: a row is dim codes and 8 bytes of scale and bias; per-input formats: the table's own kind)
+      if (s[0] != local_vocab || s[1] != hc.d.dim + (p->col_tab_kind(k) == FCP_TAB_Q8 ? 8 : 0))
         return fail(FCP_ERR_SHAPE_MISMATCH, "table shape does not match the plan");
     }
   }
@@ -361,6 +362,7 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
                     : (p->out_elem == 2 && fused) ? fused + (FCP_LAUNCH_DENSE_NARROW - FCP_LAUNCH_DENSE) // narrow plans: fcp_narrow.hip
                     : (p->tab_elem == 2 && fused) ? fused + (FCP_LAUNCH_DENSE_TAB16 - FCP_LAUNCH_DENSE)  // 16-bit tables: fcp_tables16.hip
                     : (p->tab_elem == 1 && fused) ? fused + (FCP_LAUNCH_DENSE_TABQ8 - FCP_LAUNCH_DENSE)  // 8-bit tables: fcp_tables_q8.hip
+                    : (p->tab_mixed() && fused)   ? fused + (FCP_LAUNCH_DENSE_TABMIX - FCP_LAUNCH_DENSE) // per-input formats: fcp_tables_mixed.hip
                                                   : fused,
                     std::memory_order_relaxed);
     p->last_dense_front.store(m.geo[0].grid_blocks <= 0 || p->weighted_kernel ? FCP_DENSE_FRONT_NONE
@@ -462,6 +464,19 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
       e = fcp_launch_tabq8(L, p->vec, true, m.geo[0].grid_blocks, stream);
     }
     if (e) return hip_fail("8-bit-table kernel launch", (hipError_t)e);
+  } else if (p->tab_mixed()) { // tables of more than one format: likewise
+    int e = 0;
+    if (m.geo[1].grid_blocks > 0 && m.geo[0].grid_blocks > 0) {
+      FcpLaunch Ld;
+      fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &Ld);
+      e = fcp_launch_tabmix_hybrid(Ld, m.geo[0].grid_blocks, L, m.geo[1].grid_blocks, p->vec, stream);
+    } else if (m.geo[1].grid_blocks > 0) {
+      e = fcp_launch_tabmix(L, p->vec, false, m.geo[1].grid_blocks, stream);
+    } else if (m.geo[0].grid_blocks > 0) {
+      fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &L);
+      e = fcp_launch_tabmix(L, p->vec, true, m.geo[0].grid_blocks, stream);
+    }
+    if (e) return hip_fail("mixed-table kernel launch", (hipError_t)e);
   } else if (m.geo[1].grid_blocks > 0 && m.geo[0].grid_blocks > 0) {
     FcpLaunch Ld;
     fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &Ld);

@@ -35,12 +35,16 @@ TAB_Q8 = 3                 # FCP_TAB_Q8
 # every table dtype the library knows (the two dicts above are the 16-bit feature's, these add "q8")
 ALL_TABLE_DTYPES = {**TABLE_DTYPES, TAB_Q8: "q8"}
 ALL_TABLE_DTYPE_FLAGS = {**TABLE_DTYPE_FLAGS, "q8": FLAG_TABLES_Q8}
+FLAG_TABLES_PER_INPUT = 1 << 6   # the table format is a property of each device input (ColumnExt.table_kind1), not of the plan
+TAB_MIXED = 255                  # FCP_TAB_MIXED: fcp_plan_table_dtype of a plan whose tables have more than one format; no row format
+PLAN_TABLE_DTYPES = {**ALL_TABLE_DTYPES, TAB_MIXED: "mixed"}   # what fcp_plan_table_dtype may answer
 TABLE_KINDS = {name: kind for kind, name in ALL_TABLE_DTYPES.items()}   # name -> FCP_TAB_* (fcp_table_convert)
 # fcp_launch_info_t (fcp_plan_last_launch): names of the kernel, store-policy and segment-offset codes
 LAUNCH_KERNELS = {0: "none", 1: "dense", 2: "ragged", 3: "hybrid", 4: "ragged_weighted",
                   5: "dense_narrow", 6: "ragged_narrow", 7: "hybrid_narrow",
                   8: "dense_tab16", 9: "ragged_tab16", 10: "hybrid_tab16",
-                  11: "dense_tabq8", 12: "ragged_tabq8", 13: "hybrid_tabq8"}
+                  11: "dense_tabq8", 12: "ragged_tabq8", 13: "hybrid_tabq8",
+                  14: "dense_tabmix", 15: "ragged_tabmix", 16: "hybrid_tabmix"}
 DENSE_FRONTS = {0: "none", 1: "generic", 2: "plain"}   # fcp_plan_last_dense_front
 LAUNCH_STORES = {0: "nt", 1: "sc1_nt", 4: "plain"}
 LAUNCH_SEGMENT_OFFSETS = {0: "none", 1: "prepass", 2: "search"}
@@ -72,10 +76,12 @@ class ColumnDesc(C.Structure):
 
 
 class ColumnExt(C.Structure):
-    """fcp_column_ext_t: per-column extensions (segment-id maps, per-id weights)"""
+    """fcp_column_ext_t: per-column extensions (segment-id maps, per-id weights, the table's format under
+    FLAG_TABLES_PER_INPUT: ``table_kind1`` = 1 + FCP_TAB_*, 0 = float32)"""
     _fields_ = [
         ("seg_map_n", C.c_int32), ("seg_map_sym", C.c_int32), ("seg_map_sym_slot", C.c_int32), ("weights_input1", C.c_int32),
-        ("seg_map_mul", C.c_int64 * 4), ("seg_map_div", C.c_int64), ("reserved1", C.c_int64 * 2),
+        ("seg_map_mul", C.c_int64 * 4), ("seg_map_div", C.c_int64),
+        ("table_kind1", C.c_int32), ("reserved0", C.c_int32), ("reserved1", C.c_int64 * 1),
     ]
 
 
@@ -167,6 +173,7 @@ EXPORTS = [
     "fcp_plan_private_streams_stats", "fcp_plan_last_launch", "fcp_plan_last_csr", "fcp_aux_launch_counts",
     "fcp_plan_out_dtype", "fcp_plan_last_dense_front", "fcp_plan_table_dtype",
     "fcp_table_row_bytes", "fcp_table_convert", "fcp_table_update_rows", "fcp_table_read_rows",
+    "fcp_plan_table_kinds",
 ]
 
 _lib = None
@@ -236,6 +243,7 @@ def load() -> C.CDLL:
     L.fcp_plan_table_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.fcp_plan_out_dtype.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.fcp_plan_table_dtype.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    L.fcp_plan_table_kinds.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]
     L.fcp_plan_release_captures.argtypes = [C.c_void_p]
     L.fcp_placement_decide.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
                                        C.POINTER(Placement)]

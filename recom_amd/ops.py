@@ -183,10 +183,13 @@ class Plan:
             spec.n_device_inputs, spec.n_groups, spec.n_symbols, spec.layout, device,
             spec.shard_rank, spec.shard_world, flags)
         handle = C.c_void_p()
-        if any(len(c.seg_mul) or c.weights_input != -1 for c in spec.columns):   # per-column extensions: segment-id maps, weights
+        # per-column extensions: segment-id maps, weights, per-input table formats
+        if any(len(c.seg_mul) or c.weights_input != -1 for c in spec.columns) or spec.table_dtypes is not None:
             ext = (_lib.ColumnExt * spec.n_columns)()
             for k, c in enumerate(spec.columns):
                 ext[k].weights_input1 = int(c.weights_input) + 1          # 0 = unweighted
+                if spec.table_dtypes is not None and c.form in (FORM_GATHER, FORM_SEGMENT_REDUCE, FORM_GATHER_SCATTER):
+                    ext[k].table_kind1 = 1 + _lib.TABLE_KINDS[spec.table_dtypes[c.table_input]]   # 0 = float32 / no table
                 if len(c.seg_mul):
                     ext[k].seg_map_n, ext[k].seg_map_sym, ext[k].seg_map_sym_slot = len(c.seg_mul), c.seg_sym, c.seg_sym_slot
                     for j, v in enumerate(list(c.seg_mul)[:4]):
@@ -219,7 +222,7 @@ class Plan:
         self.spec = load_plan(path)          # Python-side bookkeeping only
         if self.out_dtype() != self.spec.out_dtype:
             self.spec = dataclasses.replace(self.spec, out_dtype=self.out_dtype())
-        if self.table_dtype() != self.spec.table_dtype:
+        if self.table_dtype() not in (self.spec.table_dtype, "mixed"):   # (mixed: the file's table_dtypes line, which load_plan read)
             self.spec = dataclasses.replace(self.spec, table_dtype=self.table_dtype())
         return self
 
@@ -230,10 +233,20 @@ class Plan:
         return _lib.OUT_DTYPES[v.value]
 
     def table_dtype(self) -> str:
-        """``fcp_plan_table_dtype``: "f32", "bf16", "f16" or "q8" — the element type of every embedding table the plan reads."""
+        """``fcp_plan_table_dtype``: "f32", "bf16", "f16" or "q8" — the element type of every embedding table the plan reads;
+        "mixed" for a plan whose tables have more than one format (``table_dtypes`` names them)."""
         v = C.c_int32()
         _lib.check(self._L.fcp_plan_table_dtype(self.handle, C.byref(v)), "fcp_plan_table_dtype")
-        return _lib.ALL_TABLE_DTYPES[v.value]
+        return _lib.PLAN_TABLE_DTYPES[v.value]
+
+    def table_dtypes(self) -> tuple:
+        """``fcp_plan_table_kinds``: one of "f32" / "bf16" / "f16" / "q8" per device input, "-" for an input no lookup column
+        reads — of any plan (a plan-wide format names every read input alike)."""
+        n = C.c_int32()
+        _lib.check(self._L.fcp_plan_table_kinds(self.handle, None, 0, C.byref(n)), "fcp_plan_table_kinds")
+        kinds = (C.c_int32 * max(1, n.value))()
+        _lib.check(self._L.fcp_plan_table_kinds(self.handle, kinds, n.value, None), "fcp_plan_table_kinds")
+        return tuple("-" if kinds[t] < 0 else _lib.ALL_TABLE_DTYPES[kinds[t]] for t in range(n.value))
 
     def table_bytes(self):
         """``fcp_plan_table_bytes``: (bytes of tables this plan reads on its device, largest table unsharded)."""
@@ -416,11 +429,13 @@ class FeatureColumnProcess:
         self.out_dtype = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[self.plan.out_dtype()]
         # likewise the element type the bound tables must have (a wrong one would be read as garbage, or out of bounds)
         # (q8: torch.uint8 [vocab, dim + 8] — what quantized::embedding_bag_byte_prepack returns)
-        self.table_dtype = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "q8": torch.uint8}[self.plan.table_dtype()]
-        self._q8_shapes = {}
-        if self.plan.table_dtype() == "q8":
-            self._q8_shapes = {c.table_input: (int(c.vocab), int(c.dim) + 8) for c in self.plan.spec.columns
-                               if c.form in (FORM_GATHER, FORM_SEGMENT_REDUCE, FORM_GATHER_SCATTER)}
+        # (per-input table formats: every input is held to ITS kind, as the LIBRARY names it — self.table_dtype is then None)
+        torch_dtypes = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "q8": torch.uint8}
+        self.table_dtype = torch_dtypes.get(self.plan.table_dtype())
+        kinds = self.plan.table_dtypes()
+        self._input_dtypes = {t: torch_dtypes[k] for t, k in enumerate(kinds) if k != "-"}
+        self._q8_shapes = {c.table_input: (int(c.vocab), int(c.dim) + 8) for c in self.plan.spec.columns
+                           if c.form in (FORM_GATHER, FORM_SEGMENT_REDUCE, FORM_GATHER_SCATTER) and kinds[c.table_input] == "q8"}
         self._table_inputs = sorted({c.table_input for c in self.plan.spec.columns
                                      if c.form in (FORM_GATHER, FORM_SEGMENT_REDUCE, FORM_GATHER_SCATTER)})
 
@@ -468,9 +483,12 @@ class FeatureColumnProcess:
             tptrs, tshapes = cached[1], cached[2]  # same table list object as last time (hundreds of tables)
         else:
             for i in self._table_inputs:
-                if i < len(inputs) and inputs[i].dtype != self.table_dtype:
+                if i < len(inputs) and self.table_dtype is not None and inputs[i].dtype != self.table_dtype:
                     raise ValueError(f"FeatureColumnProcess: table {i} is {inputs[i].dtype}, the plan reads {self.table_dtype} tables "
                                      "(PlanSpec.table_dtype)")
+                if i < len(inputs) and self.table_dtype is None and inputs[i].dtype != self._input_dtypes[i]:
+                    raise ValueError(f"FeatureColumnProcess: table {i} is {inputs[i].dtype}, the plan reads input {i} as a "
+                                     f"{self._input_dtypes[i]} table (PlanSpec.table_dtypes)")
                 if i < len(inputs) and i in self._q8_shapes and (tuple(inputs[i].shape) != self._q8_shapes[i] or not inputs[i].is_contiguous()):
                     raise ValueError(f"FeatureColumnProcess: table {i} has shape {tuple(inputs[i].shape)}, the plan reads a contiguous "
                                      f"torch.uint8 table of shape {self._q8_shapes[i]}: [vocab, dim + 8] (codes, float32 scale, float32 bias)")

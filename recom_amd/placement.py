@@ -47,7 +47,7 @@ def table_bytes(spec: PlanSpec) -> np.ndarray:
     out = np.zeros(spec.n_device_inputs, np.int64)
     for c in spec.columns:
         if c.form in (FORM_GATHER, FORM_SEGMENT_REDUCE, FORM_GATHER_SCATTER):
-            out[c.table_input] = max(int(out[c.table_input]), int(c.vocab) * spec.table_row_bytes(c.dim))
+            out[c.table_input] = max(int(out[c.table_input]), int(c.vocab) * spec.input_row_bytes(c.table_input, c.dim))
     return out
 
 

@@ -37,6 +37,9 @@ FLAG_OUT_BF16, FLAG_OUT_F16 = 1 << 1, 1 << 2   # narrow output (PlanSpec.out_dty
 FLAG_TABLES_BF16, FLAG_TABLES_F16 = 1 << 3, 1 << 4   # 16-bit tables (PlanSpec.table_dtype sets the bit)
 FLAG_TABLES_Q8 = 1 << 5   # 8-bit row-quantised tables (PlanSpec.table_dtype "q8" sets the bit)
 Q8_ROW_TAIL = 8           # bytes behind the codes of a q8 row: float32 scale, float32 bias
+FLAG_TABLES_PER_INPUT = 1 << 6   # the table format is a property of each device input (PlanSpec.table_dtypes sets the bit)
+_TABLE_DTYPE_NAMES = ("f32", "bf16", "f16", "q8")
+_LOOKUP_FORMS = (FORM_GATHER, FORM_SEGMENT_REDUCE, FORM_GATHER_SCATTER)
 
 
 class NarrowOutputUnsupported(ValueError):
@@ -49,6 +52,10 @@ class Tables16Unsupported(ValueError):
 
 class TablesQ8Unsupported(ValueError):
     """A plan kind the 8-bit-table kernels do not serve (the library answers FCP_ERR_UNSUPPORTED)."""
+
+
+class TablesMixedUnsupported(ValueError):
+    """A plan kind the mixed-table kernels (per-input table formats) do not serve (the library answers FCP_ERR_UNSUPPORTED)."""
 
 _ID_ELEM_SIZE = {IDS_I32: 4, IDS_I64: 8, IDS_F32_BUCKETIZE: 4}
 _ID_NP_DTYPE = {IDS_I32: np.int32, IDS_I64: np.int64, IDS_F32_BUCKETIZE: np.float32}
@@ -184,6 +191,10 @@ class PlanSpec:
     # or — FCP_FLAG_TABLES_Q8 — "q8": uint8 [vocab, dim + 8] rows of codes, float32 scale, float32 bias; an element is
     # fma(code, scale, bias) rounded once, the plan computes what the float32 plan computes on the dequantised tables
     table_dtype: str = "f32"
+    # per-input table formats — FCP_FLAG_TABLES_PER_INPUT: None, or one of "f32" / "bf16" / "f16" / "q8" per DEVICE INPUT ("-"
+    # for an input no lookup column reads); each table then follows its own format's rules.  ``with_table_dtypes`` sets it and
+    # turns a tuple whose tables all share one kind into ``table_dtype`` (the library does the same with the flag)
+    table_dtypes: Optional[tuple] = None
 
     # ---- static layout facts ------------------------------------------------
     def validate(self) -> None:
@@ -213,7 +224,8 @@ class PlanSpec:
     def plan_flags(self) -> int:
         """``fcp_plan_desc_t::flags``: ``flags`` plus the bit ``out_dtype`` stands for."""
         return (self.flags | {"f32": 0, "bf16": FLAG_OUT_BF16, "f16": FLAG_OUT_F16}.get(self.out_dtype, 0)
-                | {"f32": 0, "bf16": FLAG_TABLES_BF16, "f16": FLAG_TABLES_F16, "q8": FLAG_TABLES_Q8}.get(self.table_dtype, 0))
+                | {"f32": 0, "bf16": FLAG_TABLES_BF16, "f16": FLAG_TABLES_F16, "q8": FLAG_TABLES_Q8}.get(self.table_dtype, 0)
+                | (FLAG_TABLES_PER_INPUT if self.table_dtypes is not None else 0))
 
     @property
     def out_elem_size(self) -> int:
@@ -253,12 +265,76 @@ class PlanSpec:
         """Bytes of one table row of ``dim`` elements: ``dim`` x the element size, plus scale and bias in a q8 table."""
         return dim * self.table_elem_size + (Q8_ROW_TAIL if self.plan_flags() & FLAG_TABLES_Q8 else 0)
 
+    # ---- per-input table formats --------------------------------------------
+    def read_inputs(self) -> List[int]:
+        """The device inputs some lookup column reads, ascending."""
+        return sorted({c.table_input for c in self.columns if c.form in _LOOKUP_FORMS})
+
+    def input_table_dtype(self, table_input: int) -> str:
+        """The format of device input ``table_input``: its entry of ``table_dtypes``, else the plan-wide ``table_dtype``."""
+        return self.table_dtype if self.table_dtypes is None else self.table_dtypes[table_input]
+
+    def input_row_bytes(self, table_input: int, dim: int) -> int:
+        """Bytes of one row of ``dim`` elements of device input ``table_input``, in that table's own format."""
+        kind = self.input_table_dtype(table_input)
+        return dim + Q8_ROW_TAIL if kind == "q8" else dim * (4 if kind == "f32" else 2)
+
+    def mixed_tables(self) -> bool:
+        """Whether the plan's tables really have more than one format (what the library calls FCP_TAB_MIXED)."""
+        return self.table_dtypes is not None and len({self.table_dtypes[t] for t in self.read_inputs()}) > 1
+
+    def with_table_dtypes(self, table_dtypes) -> "PlanSpec":
+        """One format name per device input (a sequence; entries of inputs no lookup column reads are ignored), or None.  Tables
+        that all share one format make it the plan-wide ``table_dtype``: the uniform plan IS the plan-wide plan."""
+        if table_dtypes is None:
+            return dataclasses.replace(self, table_dtypes=None)
+        names = [str(n) for n in table_dtypes]
+        if len(names) != self.n_device_inputs:
+            raise ValueError(f"table_dtypes names {len(names)} inputs, the plan has {self.n_device_inputs} device inputs")
+        read = set(self.read_inputs())
+        names = tuple(n if t in read else "-" for t, n in enumerate(names))
+        for t in read:
+            if names[t] not in _TABLE_DTYPE_NAMES:
+                raise ValueError(f"table_dtypes[{t}] must be 'f32', 'bf16', 'f16' or 'q8', not {names[t]!r}")
+        kinds = {names[t] for t in read}
+        if len(kinds) <= 1:
+            return dataclasses.replace(self, table_dtype=kinds.pop() if kinds else "f32", table_dtypes=None)
+        return dataclasses.replace(self, table_dtype="f32", table_dtypes=names)
+
+    def _validate_table_dtypes(self) -> None:
+        """The library's rules for FCP_FLAG_TABLES_PER_INPUT, with its words."""
+        names = tuple(self.table_dtypes)
+        if self.table_dtype != "f32" or self.flags & (FLAG_TABLES_BF16 | FLAG_TABLES_F16 | FLAG_TABLES_Q8):
+            raise ValueError("FCP_FLAG_TABLES_PER_INPUT and FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16 / FCP_FLAG_TABLES_Q8 exclude each other")
+        if len(names) != self.n_device_inputs:
+            raise ValueError(f"table_dtypes names {len(names)} inputs, the plan has {self.n_device_inputs} device inputs")
+        read = self.read_inputs()
+        for t, n in enumerate(names):
+            if n not in (_TABLE_DTYPE_NAMES if t in read else _TABLE_DTYPE_NAMES + ("-",)):
+                raise ValueError(f"table_dtypes[{t}] must be 'f32', 'bf16', 'f16' or 'q8', not {n!r}")
+        if not self.mixed_tables():   # one kind: the plan-wide plan's rules
+            kind = names[read[0]] if read else "f32"
+            dataclasses.replace(self, table_dtype=kind, table_dtypes=None).validate_table_dtype()
+            return
+        if self.plan_flags() & (FLAG_OUT_BF16 | FLAG_OUT_F16):
+            raise TablesMixedUnsupported("per-input table formats with narrow output (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16): the mixed-table kernels store float32")
+        if self.shard_world > 1:
+            raise TablesMixedUnsupported("per-input table formats on a row-sharded plan (shard_world > 1): the sharded kernels read float32 tables")
+        for k, c in enumerate(self.columns):
+            if c.weights_input >= 0:
+                raise TablesMixedUnsupported(f"column {k}: per-input table formats with per-id weights: weighted plans take the float32 weighted kernel")
+            if c.combiner == COMBINER_SQRTN and c.form == FORM_SEGMENT_REDUCE:
+                raise TablesMixedUnsupported(f"column {k}: per-input table formats with FCP_COMBINER_SQRTN: sqrtn plans take the float32 weighted kernel")
+
     def validate_table_dtype(self) -> None:
         """The library's rules for 16-bit tables (``fcp_plan_create``): one dtype, and none of the three plan kinds the
         16-bit-table kernels do not serve.  ``Tables16Unsupported`` mirrors FCP_ERR_UNSUPPORTED, ValueError
         FCP_ERR_INVALID_ARGUMENT."""
         if self.table_dtype not in ("f32", "bf16", "f16", "q8"):
             raise ValueError(f"table_dtype must be 'f32', 'bf16', 'f16' or 'q8', not {self.table_dtype!r}")
+        if self.table_dtypes is not None:   # per-input table formats: their own rules
+            self._validate_table_dtypes()
+            return
         f = self.plan_flags()
         if f & FLAG_TABLES_Q8:   # 8-bit row-quantised tables: the same rules, by their own name
             if f & (FLAG_TABLES_BF16 | FLAG_TABLES_F16):
@@ -332,6 +408,8 @@ class PlanSpec:
             del d["out_dtype"]
         if self.table_dtype == "f32":      # likewise
             del d["table_dtype"]
+        if self.table_dtypes is None:      # likewise
+            del d["table_dtypes"]
         for c, src in zip(d["columns"], self.columns):
             c["boundaries"] = None if src.boundaries is None else np.asarray(src.boundaries, np.float32)
             c["xform_lo"] = [int(v) for v in src.xform_lo]
@@ -491,7 +569,7 @@ class PlanSpec:
                 rows_b += numel(c.ids_input) * 4
             else:
                 nnz = numel(c.ids_input)
-                rows_b += nnz * self.table_row_bytes(c.dim)
+                rows_b += nnz * self.input_row_bytes(c.table_input, c.dim)
                 ids_b += nnz * _ID_ELEM_SIZE[c.id_source]
                 if c.seg_kind == SEG_CSR_I32:
                     seg_b += (rows + 1) * 4

@@ -20,7 +20,12 @@ def save_plan(spec: PlanSpec, path: str, stage: "StageInfo | None" = None) -> No
         maps = [(k, c) for k, c in enumerate(spec.columns) if len(c.seg_mul)]
         weights = [(k, c) for k, c in enumerate(spec.columns) if c.weights_input >= 0]
         v5 = bool(weights) or any(c.combiner == COMBINER_SQRTN for c in spec.columns)
-        if spec.table_dtype != "f32":   # version 7, plans with 16-bit or 8-bit tables only (never narrow output as well): likewise
+        if spec.table_dtypes is not None and not spec.mixed_tables():   # one kind under per-input formats: the plan-wide plan's file
+            read = spec.read_inputs()
+            spec = spec.with_table_dtypes(None).with_table_dtype(spec.table_dtypes[read[0]] if read else "f32")
+        if spec.table_dtypes is not None:   # version 8, plans whose tables have more than one format only: one name per device input
+            f.write(f"fcp_plan 8\ntable_dtypes {spec.n_device_inputs} {' '.join(spec.table_dtypes)}\n")
+        elif spec.table_dtype != "f32":   # version 7, plans with 16-bit or 8-bit tables only (never narrow output as well): likewise
             f.write(f"fcp_plan 7\ntable_dtype {spec.table_dtype}\n")
         elif spec.out_dtype != "f32":   # version 6, narrow-output plans only: the dtype is the file's second line
             f.write(f"fcp_plan 6\nout_dtype {spec.out_dtype}\n")
@@ -70,10 +75,24 @@ def load_plan(path: str) -> PlanSpec:
     if nxt() != "fcp_plan":
         raise ValueError("bad plan header")
     version = int(nxt())
-    if version not in (1, 2, 3, 4, 5, 6, 7):
+    if version not in (1, 2, 3, 4, 5, 6, 7, 8):
         raise ValueError("bad plan header")
     out_dtype = table_dtype = "f32"
-    if version >= 7:              # "table_dtype bf16|f16|q8": the same place and rules, in version 7 files and no others
+    table_dtypes = None
+    if version >= 8:              # "table_dtypes D k0 ... k(D-1)": the same place and rules, in version 8 files and no others
+        if nxt() != "table_dtypes":
+            raise ValueError(f"expected 'table_dtypes D k0 ... k(D-1)' in {path}")
+        try:
+            n_kinds = int(nxt())
+        except ValueError:
+            raise ValueError(f"expected 'table_dtypes D k0 ... k(D-1)' in {path}") from None
+        if n_kinds < 0:
+            raise ValueError(f"expected 'table_dtypes D k0 ... k(D-1)' in {path}")
+        table_dtypes = tuple(nxt() for _ in range(n_kinds))
+        for n in table_dtypes:
+            if n not in ("f32", "bf16", "f16", "q8", "-"):
+                raise ValueError(f"unknown table dtype {n!r} in the table_dtypes line of {path}")
+    elif version >= 7:              # "table_dtype bf16|f16|q8": the same place and rules, in version 7 files and no others
         if nxt() != "table_dtype":
             raise ValueError(f"expected 'table_dtype bf16', 'table_dtype f16' or 'table_dtype q8' in {path}")
         table_dtype = nxt()
@@ -135,12 +154,24 @@ def load_plan(path: str) -> PlanSpec:
             v = [int(x) for x in rest[2 + 9 * j: 11 + 9 * j]]
             cols[v[0]] = dataclasses.replace(cols[v[0]], seg_mul=tuple(v[4:4 + v[1]]), seg_div=v[8], seg_sym=v[2],
                                              seg_sym_slot=v[3])
-    if tok.count("table_dtype") != (1 if version >= 7 else 0):
+    if tok.count("table_dtypes") != (1 if version >= 8 else 0):
+        raise ValueError(f"misplaced or repeated table_dtypes line in {path}")
+    if tok.count("table_dtype") != (1 if version == 7 else 0):
         raise ValueError(f"misplaced or repeated table_dtype line in {path}")
     if tok.count("out_dtype") != (1 if version == 6 else 0):   # anywhere but the second line, twice, or in an older file
         raise ValueError(f"misplaced or repeated out_dtype line in {path}")
     spec = PlanSpec(cols, ranks, esz, n_dev, n_groups=n_groups, n_symbols=n_symbols, layout=layout, out_dtype=out_dtype,
                     table_dtype=table_dtype)
+    if table_dtypes is not None:
+        if len(table_dtypes) != n_dev:
+            raise ValueError(f"the table_dtypes line names {len(table_dtypes)} inputs, the plan has {n_dev} device inputs: {path}")
+        read = set(spec.read_inputs())
+        for t, n in enumerate(table_dtypes):
+            if (n == "-") != (t not in read):
+                raise ValueError(f"the table_dtypes line of {path} must name exactly the device inputs lookup columns read (input {t})")
+        spec = dataclasses.replace(spec, table_dtypes=table_dtypes)
+        if not spec.mixed_tables():
+            raise ValueError(f"version 8 is for plans whose tables have more than one dtype: {path}")
     spec.validate()
     return spec
 

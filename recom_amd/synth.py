@@ -275,7 +275,18 @@ class SynthModel:
 
     def numpy_tables(self) -> List[np.ndarray]:
         """float32 tables; uint16 bit patterns for a plan with 16-bit tables (``spec.table_dtype``); uint8 [vocab, dim + 8]
-        rows for a plan with q8 tables (their own closed form, ``q8_rows``)."""
+        rows for a plan with q8 tables (their own closed form, ``q8_rows``).  A plan with per-input table formats
+        (``spec.table_dtypes``): each table in its own kind."""
+        if self.spec.table_dtypes is not None:
+            out = []
+            for i, t in enumerate(self.tables):
+                dt = self.spec.input_table_dtype(i)
+                if dt == "q8":
+                    out.append(q8_table_numpy(t.seed, t.vocab, t.dim))
+                else:
+                    x = hash_table_numpy(t.seed, t.vocab, t.dim)
+                    out.append(x if dt in ("f32", "-") else table_patterns(x, dt))
+            return out
         dt = self.spec.table_dtype
         if dt == "q8":
             return [q8_table_numpy(t.seed, t.vocab, t.dim) for t in self.tables]
@@ -286,6 +297,17 @@ class SynthModel:
         """The tables on a torch device, in the plan's table dtype (torch's cast rounds to nearest-even, as
         ``table_patterns`` does); converted one table at a time, so a 16-bit model never holds its float32 form whole."""
         import torch
+        if self.spec.table_dtypes is not None:   # per-input table formats: each table in its own kind (never sharded either)
+            tds = {"f32": None, "-": None, "bf16": torch.bfloat16, "f16": torch.float16}
+            out = []
+            for i, t in enumerate(self.tables):
+                dt = self.spec.input_table_dtype(i)
+                if dt == "q8":
+                    out.append(q8_table_torch(t.seed, t.vocab, t.dim, device))
+                else:
+                    x = hash_table_torch(t.seed, t.vocab, t.dim, device, shard_rank, shard_world)
+                    out.append(x if tds[dt] is None else x.to(tds[dt]))
+            return out
         if self.spec.table_dtype == "q8":   # (never sharded: such plans are refused)
             return [q8_table_torch(t.seed, t.vocab, t.dim, device) for t in self.tables]
         td = {"f32": None, "bf16": torch.bfloat16, "f16": torch.float16}[self.spec.table_dtype]
@@ -296,6 +318,9 @@ class SynthModel:
         return out
 
     def table_bytes(self) -> int:
+        if self.spec.table_dtypes is not None:   # each table at its own row size (an input no column reads: float32)
+            return sum(t.vocab * (4 * t.dim if self.spec.input_table_dtype(i) == "-" else self.spec.input_row_bytes(i, t.dim))
+                       for i, t in enumerate(self.tables))
         return sum(t.vocab * self.spec.table_row_bytes(t.dim) for t in self.tables)
 
 
@@ -474,12 +499,15 @@ def _add_ragged(b: _Builder, vocab: int, dim: int, slot: int, combiner: int, seg
 
 def _finish(name: str, b: _Builder, batch: int, n_groups: int = 1, n_symbols: int = 0, description: str = "",
             symbol_values: Optional[Callable[[int], np.ndarray]] = None, out_dtype: str = "f32",
-            table_dtype: str = "f32") -> SynthModel:
+            table_dtype: str = "f32", table_dtypes: Optional[dict] = None) -> SynthModel:
+    """``table_dtypes``: a dim -> format mapping (dims it does not name stay float32): per-input table formats."""
     spec = b.spec(n_groups, n_symbols)
     if out_dtype != "f32":   # narrow output: the concat groups as bf16 / fp16
         spec = spec.with_out_dtype(out_dtype)
     if table_dtype != "f32":   # 16-bit / q8 tables: numpy_tables / torch_tables then produce 16-bit patterns / q8 rows
         spec = spec.with_table_dtype(table_dtype)
+    if table_dtypes is not None:   # per-input formats by table width; tables that all get one format make it the plan-wide one
+        spec = spec.with_table_dtypes([table_dtypes.get(t.dim, "f32") for t in b.tables])
     spec.validate()
     gens = list(b.gens)
 
@@ -526,12 +554,14 @@ def model_s1(columns: int = 100, dim: int = 16, vocab: int = 10_000, batch: int 
 
 
 def model_s2(columns: int = 1000, vocab: int = 1_000_000, batch: int = 512, dist: str = "uniform",
-             dims: Sequence[int] = (8, 16, 32, 64), vocab_of: Optional[dict] = None, out_dtype: str = "f32", table_dtype: str = "f32") -> SynthModel:
+             dims: Sequence[int] = (8, 16, 32, 64), vocab_of: Optional[dict] = None, out_dtype: str = "f32", table_dtype: str = "f32",
+             table_dtypes: Optional[dict] = None) -> SynthModel:
     """S2 (headline): 1000 columns, dims cycling 8/16/32/64, vocab 1M (120 GB of
     tables), batch 512, one id per row (form 1); every 10th column is sourced by
     a float feature bucketized with 100 boundaries (the reference's dominant
     column type), the others by int64 ids.  `vocab_of`: {column: vocab} for the
-    few columns whose table is of another size (placement tests)."""
+    few columns whose table is of another size (placement tests).  `table_dtypes`:
+    {dim: format} — per-input table formats by table width (e.g. 64 -> "q8")."""
     b = _Builder()
     for c in range(columns):
         d = dims[c % len(dims)]
@@ -540,7 +570,7 @@ def model_s2(columns: int = 1000, vocab: int = 1_000_000, batch: int = 512, dist
             _add_dense(b, v, d, slot=c, id_source=IDS_F32_BUCKETIZE, boundaries=MICROBENCH_BOUNDARIES)
         else:
             _add_dense(b, v, d, slot=c, dist=dist)
-    return _finish("S2", b, batch, out_dtype=out_dtype, table_dtype=table_dtype,
+    return _finish("S2", b, batch, out_dtype=out_dtype, table_dtype=table_dtype, table_dtypes=table_dtypes,
                    description=f"{columns} cols, dims {'/'.join(map(str, dims))}, vocab {vocab}, B {batch}, "
                                f"1 id/row, 10% bucketize-f32, ids {dist}")
 
