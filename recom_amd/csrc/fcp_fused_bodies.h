@@ -1,8 +1,10 @@
 // fcp_fused_bodies.h — the device code the fused kernels are made of: loads / stores, the id path, the dense body and the
-// ragged body (with its per-id-weight variant).  Shared by the two translation units that instantiate kernels from it:
-// fcp_kernels.hip (the fused matrix: dense, ragged, hybrid) and fcp_weighted.hip (the weighted ragged kernels, which do not
-// fit the 64-VGPR budget of the tuned instantiations and are launched only for plans that need them).  Everything lives in
-// an unnamed namespace: each translation unit gets its own copy.
+// ragged body, each a template over the variant it is instantiated for (FcpVariant, fcp_internal.h).  Shared by the
+// translation units that instantiate kernels from it, one per variant: fcp_kernels.hip (the float32 matrix: dense, ragged,
+// hybrid), fcp_weighted.hip (the weighted ragged kernels, which do not fit the 64-VGPR budget of the tuned instantiations and
+// are launched only for plans that need them), fcp_narrow.hip, fcp_tables16.hip, fcp_tables_q8.hip and fcp_tables_mixed.hip;
+// what their kernels and launchers share on top of the bodies is fcp_fused_launch.h.  Everything lives in an unnamed
+// namespace: each translation unit gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -745,8 +747,12 @@ template <int R> struct DenseLds {
 // COLUMN (FCP_F_TABKIND of its record's flags: a 64-slot span routinely holds columns of different formats), so the row stride
 // that scales a row index and the loader are chosen per lane — wave-uniformly where one ballot shows that the whole wave
 // holds one kind; all behind `if constexpr (TABMIX)`.
-template <int V, int R, bool SHARDED, bool NARROW = false, bool TAB16 = false, bool TABQ8 = false, bool TABMIX = false>
-__device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *smem, int out_kind = 0, int tab_kind = 0) {
+// `kind`: what NARROW and TAB16 call out_kind / tab_kind; the other variants do not read it.
+template <int V, int R, bool SHARDED, FcpVariant X = FCP_VAR_F32>
+__device__ __forceinline__ void dense_body(const FcpLaunch &L, int bid, char *smem, int kind = 0) {
+  constexpr bool NARROW = X == FCP_VAR_NARROW, TAB16 = X == FCP_VAR_TAB16, TABQ8 = X == FCP_VAR_TABQ8, TABMIX = X == FCP_VAR_TABMIX;
+  static_assert(X != FCP_VAR_WEIGHTED, "the weighted kernel is a ragged one");
+  const int out_kind = kind, tab_kind = kind;
   constexpr int RB = DenseLds<R>::RB, IDS = DenseLds<R>::IDS, BND = DenseLds<R>::BND;
   DenseLds<R> &S = *reinterpret_cast<DenseLds<R> *>(smem);
   LdsCol *s_col = S.col;
@@ -1071,9 +1077,11 @@ __device__ __forceinline__ Q8Raw ld_slot_or_zero_q8(const char *tb, const float 
 // TAB16 (16-bit tables): `tb` carries the lane's base as a byte address, the reads are the 16-bit loader's.
 // TABQ8 (8-bit row-quantised tables): `tb` carries the lane's base as a byte address, `q8_tail` the distance from the lane's
 // codes to the row's scale; `spr` is the row's size in BYTES, dim + 8.
-template <int V, int N, bool TAB16 = false, bool TABQ8 = false>
+// X: FCP_VAR_TAB16, FCP_VAR_TABQ8, or any other variant for the float32 walk.
+template <int V, int N, FcpVariant X = FCP_VAR_F32>
 __device__ __forceinline__ void bag_walk_batch(const float *tb, const float *zeros, uint32_t spr, const uint32_t *s, int base, int n, VF<V> &acc,
                                                int tab_kind = 0, int q8_tail = 0) {
+  constexpr bool TAB16 = X == FCP_VAR_TAB16, TABQ8 = X == FCP_VAR_TABQ8;
   uint32_t off[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) off[k] = base + k < n ? s[base + k] : kNoRow;
@@ -1103,7 +1111,7 @@ __device__ __forceinline__ void bag_walk_batch(const float *tb, const float *zer
     for (int t = 0; t < V; ++t) acc.v[t] = acc.v[t] + w[k].v[t]; // id order
 }
 
-template <int V, int WALK, bool TAB16 = false, bool TABQ8 = false>
+template <int V, int WALK, FcpVariant X = FCP_VAR_F32>
 __device__ __forceinline__ void bag_walk_sum(const float *tb, const float *zeros, uint32_t spr, const uint32_t *s, int n, VF<V> &acc,
                                              int tab_kind = 0, int q8_tail = 0) {
   // The first batch is as wide as the wave's longest bag needs, up to kWalkFirst reads per lane: every bag of
@@ -1112,20 +1120,20 @@ __device__ __forceinline__ void bag_walk_sum(const float *tb, const float *zeros
   // 9- and 10-id bags; RAGGED 30.2 -> 28.9 us, profiles/r03_ragged_walk_width_ab.txt).  Wave-uniform choices.
   int base = WALK;
   if (WALK >= 8 && !__any(n > 4)) {
-    bag_walk_batch<V, 4, TAB16, TABQ8>(tb, zeros, spr, s, 0, n, acc, tab_kind, q8_tail);
+    bag_walk_batch<V, 4, X>(tb, zeros, spr, s, 0, n, acc, tab_kind, q8_tail);
     return;
   } else if (WALK >= 8 && kWalkFirst > WALK && __any(n > WALK)) {
-    bag_walk_batch<V, kWalkFirst, TAB16, TABQ8>(tb, zeros, spr, s, 0, n, acc, tab_kind, q8_tail);
+    bag_walk_batch<V, kWalkFirst, X>(tb, zeros, spr, s, 0, n, acc, tab_kind, q8_tail);
     base = kWalkFirst;
   } else {
-    bag_walk_batch<V, WALK, TAB16, TABQ8>(tb, zeros, spr, s, 0, n, acc, tab_kind, q8_tail);
+    bag_walk_batch<V, WALK, X>(tb, zeros, spr, s, 0, n, acc, tab_kind, q8_tail);
   }
   for (; __any(n > base);) { // wave-uniform trip count
     if (WALK > 4 && !__any(n > base + 4)) { // a short tail (bags of 9..12 ids): half a batch
-      bag_walk_batch<V, 4, TAB16, TABQ8>(tb, zeros, spr, s, base, n, acc, tab_kind, q8_tail);
+      bag_walk_batch<V, 4, X>(tb, zeros, spr, s, base, n, acc, tab_kind, q8_tail);
       base += 4;
     } else {
-      bag_walk_batch<V, WALK, TAB16, TABQ8>(tb, zeros, spr, s, base, n, acc, tab_kind, q8_tail);
+      bag_walk_batch<V, WALK, X>(tb, zeros, spr, s, base, n, acc, tab_kind, q8_tail);
       base += WALK;
     }
   }
@@ -1211,12 +1219,12 @@ struct RaggedLds {
 // TABMIX: as in the dense body — plans whose tables have more than one format (fcp_tables_mixed.hip): the lane's column names
 // its kind (FCP_F_TABKIND), the walk is the float32, the 16-bit or the q8 walk accordingly; everything behind
 // `if constexpr (TABMIX)`; never together with WEIGHTED either.
-template <int V, bool SHARDED, bool WEIGHTED = false, bool NARROW = false, bool TAB16 = false, bool TABQ8 = false, bool TABMIX = false>
-__device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *smem, const int64_t *wts = nullptr, int out_kind = 0,
-                                            int tab_kind = 0) {
-  static_assert(!(TAB16 && WEIGHTED), "the weighted walk reads float32 tables");
-  static_assert(!(TABQ8 && (WEIGHTED || TAB16)), "one table format per instantiation; the weighted walk reads float32 tables");
-  static_assert(!(TABMIX && (WEIGHTED || TAB16 || TABQ8)), "per-column kinds replace the plan-wide ones; the weighted walk reads float32 tables");
+// `kind`: as in the dense body.
+template <int V, bool SHARDED, FcpVariant X = FCP_VAR_F32>
+__device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *smem, const int64_t *wts = nullptr, int kind = 0) {
+  constexpr bool WEIGHTED = X == FCP_VAR_WEIGHTED, NARROW = X == FCP_VAR_NARROW, TAB16 = X == FCP_VAR_TAB16, TABQ8 = X == FCP_VAR_TABQ8,
+                 TABMIX = X == FCP_VAR_TABMIX;
+  const int out_kind = kind, tab_kind = kind;
   constexpr int RB = RaggedLds::RB, CAPW = RaggedLds::CAPW;
   RaggedLds &S = *reinterpret_cast<RaggedLds *>(smem);
   LdsCol *s_col = S.col;
@@ -1409,9 +1417,9 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
           if (k == FCP_TAB_F32)
             bag_walk_sum<V, WALK>(tb, H.zeros, spr, s, n, acc);
           else if (k == FCP_TAB_Q8)
-            bag_walk_sum<V, WALK, false, true>(tb, H.zeros, spr, s, n, acc, 0, q8_tail);
+            bag_walk_sum<V, WALK, FCP_VAR_TABQ8>(tb, H.zeros, spr, s, n, acc, 0, q8_tail);
           else
-            bag_walk_sum<V, WALK, true>(tb, H.zeros, spr, s, n, acc, k);
+            bag_walk_sum<V, WALK, FCP_VAR_TAB16>(tb, H.zeros, spr, s, n, acc, k);
         };
         const int k0 = __builtin_amdgcn_readfirstlane(kind);
         if (__ballot(kind != k0) == 0ull)
@@ -1419,9 +1427,9 @@ __device__ __forceinline__ void ragged_body(const FcpLaunch &L, int bid, char *s
         else
           walk(kind);
       } else if constexpr (TABQ8) {
-        bag_walk_sum<V, WALK, false, true>(tb, H.zeros, spr, s, n, acc, 0, q8_tail);
+        bag_walk_sum<V, WALK, FCP_VAR_TABQ8>(tb, H.zeros, spr, s, n, acc, 0, q8_tail);
       } else if constexpr (TAB16) {
-        bag_walk_sum<V, WALK, true>(tb, H.zeros, spr, s, n, acc, tab_kind);
+        bag_walk_sum<V, WALK, FCP_VAR_TAB16>(tb, H.zeros, spr, s, n, acc, tab_kind);
       } else {
         bag_walk_sum<V, WALK>(tb, H.zeros, spr, s, n, acc);
       }

@@ -269,6 +269,9 @@ struct fcp_plan {
   // without weighted columns have no such array).  weighted_kernel: has_weights, or some column's combiner is SQRTN — all
   // spans of the plan run the weighted ragged kernel.
   bool has_weights = false, weighted_kernel = false;
+  // Which unit's fused kernels serve the plan (fcp_internal.h): decided once, when the plan is created, from weighted_kernel,
+  // out_elem, tab_elem and col_kind below; the request path dispatches on it and on nothing else.
+  FcpVariant variant = FCP_VAR_F32;
   // Plain dense plan (fcp_dense_plain.hip): float32 concat output, one group, unsharded, V 4, no wide rows, no id transform,
   // every column a gather by int32 / int64 ids or by float32 values bucketized with reproducible boundaries.  Decided at
   // plan creation (FCP_DIAG=dense_generic keeps such a plan on the generic kernel).  Every descriptor slot then carries,

@@ -185,42 +185,50 @@ struct FcpSegLaunch {
   int32_t skip_inverse;      // 1: leave the any-order scatter columns alone (fcp_shard_finalize only wants row lengths)
 };
 
-// ---- launchers implemented in fcp_kernels.hip --------------------------------
+// ---- the variants of the fused kernels ------------------------------------------------------------------------------------
+// One per translation unit that instantiates the fused bodies (fcp_fused_bodies.h).  The same value is the template
+// parameter of the bodies, a field of the plan (fcp_plan::variant, decided when the plan is created) and the index of the
+// request path's dispatch (fcp_process.hip).  A plan is exactly one of them.
+enum FcpVariant {
+  FCP_VAR_F32 = 0,  // float32 tables and output (fcp_kernels.hip); sharded plans too
+  FCP_VAR_WEIGHTED, // per-id weights or the sqrtn combiner: one ragged kernel for all spans (fcp_weighted.hip); sharded plans too
+  FCP_VAR_NARROW,   // bf16 / fp16 output (fcp_narrow.hip); kind: FCP_OUT_BF16 | FCP_OUT_F16
+  FCP_VAR_TAB16,    // bf16 / fp16 tables (fcp_tables16.hip); kind: FCP_TAB_BF16 | FCP_TAB_F16
+  FCP_VAR_TABQ8,    // 8-bit row-quantised tables (fcp_tables_q8.hip)
+  FCP_VAR_TABMIX,   // tables of more than one format, the kind a fact of each column record (fcp_tables_mixed.hip)
+  FCP_VARIANTS
+};
+
+// ---- launchers: the fused ones in their variant's unit, the others in fcp_kernels.hip unless named otherwise ---------------
 struct ihipStream_t;
-// the next fused / hybrid launch of THIS thread carries `event` (hipEvent_t) as its stop event; pending = not taken yet
+// the next fused launch of THIS thread carries `event` (hipEvent_t) as its stop event; pending = not taken yet
 void fcp_set_stop_event(void *event);
 bool fcp_stop_event_pending();
-// the next fused / hybrid launch of THIS thread is an any-order launch (no barrier bit); cleared by the launch
+// the next fused launch of THIS thread is an any-order launch (no barrier bit); cleared by the launch
 void fcp_set_any_order(bool on);
-int fcp_launch_fused(const FcpLaunch &L, int vec, bool dense_kernel, int grid_blocks, ihipStream_t *s);
-int fcp_launch_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch &Lragged, int ragged_blocks, int vec,
-                      ihipStream_t *s);
-// (fcp_weighted.hip) the ragged body with per-id weights and the sqrtn combiner, for plans that have either; wts: per
-// column (concat order) the byte offset of its float32 weights in the blob, or -1 — the tail of the request's descriptor
-// slot in plans with weighted columns, null in plans that only use sqrtn
-int fcp_launch_weighted(const FcpLaunch &L, const int64_t *wts, int vec, int grid_blocks, ihipStream_t *s);
-// (fcp_narrow.hip) the dense / ragged / hybrid bodies for bf16 / fp16 output plans (unsharded); out_kind: FCP_OUT_BF16 |
-// FCP_OUT_F16; geometry, LDS and grids as fcp_launch_fused / fcp_launch_hybrid
-int fcp_launch_narrow(const FcpLaunch &L, int vec, bool dense_kernel, int out_kind, int grid_blocks, ihipStream_t *s);
-int fcp_launch_narrow_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch &Lragged, int ragged_blocks, int vec,
-                             int out_kind, ihipStream_t *s);
-// (fcp_tables16.hip) the dense / ragged / hybrid bodies for plans with bf16 / fp16 tables (unsharded, float32 output);
-// tab_kind: FCP_TAB_BF16 | FCP_TAB_F16; geometry, LDS and grids as fcp_launch_fused / fcp_launch_hybrid
-int fcp_launch_tab16(const FcpLaunch &L, int vec, bool dense_kernel, int tab_kind, int grid_blocks, ihipStream_t *s);
-int fcp_launch_tab16_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch &Lragged, int ragged_blocks, int vec,
-                            int tab_kind, ihipStream_t *s);
-// (fcp_tables_q8.hip) the same for plans with 8-bit row-quantised tables (FCP_FLAG_TABLES_Q8)
-int fcp_launch_tabq8(const FcpLaunch &L, int vec, bool dense_kernel, int grid_blocks, ihipStream_t *s);
-int fcp_launch_tabq8_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch &Lragged, int ragged_blocks, int vec,
-                            ihipStream_t *s);
-// (fcp_tables_mixed.hip) the same for plans whose tables have more than one format (FCP_FLAG_TABLES_PER_INPUT): the kind is a
-// fact of each column record (FCP_F_TABKIND)
-int fcp_launch_tabmix(const FcpLaunch &L, int vec, bool dense_kernel, int grid_blocks, ihipStream_t *s);
-int fcp_launch_tabmix_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch &Lragged, int ragged_blocks, int vec,
-                             ihipStream_t *s);
-// (fcp_dense_plain.hip) the small dense kernel of plain dense plans: V 4, R 4, the grid of fcp_launch_fused's dense kernel
+// The fused work of one request: spans whose columns are all copies run the dense body, the others the ragged body.
+// vec: 4 | 2 | 1; rows per wave of the dense body (1 | 2 | 4, rows per block = 4 x that) from dense->rows_per_wave, the
+// ragged body always 1.  A side without blocks is not read.
+struct FcpFusedWork {
+  const FcpLaunch *dense;
+  int dense_blocks;
+  const FcpLaunch *ragged;
+  int ragged_blocks;
+  int vec;
+  int kind;           // FCP_VAR_NARROW: FCP_OUT_*; FCP_VAR_TAB16: FCP_TAB_*; not read by the other variants
+  const int64_t *wts; // FCP_VAR_WEIGHTED: per column (concat order) the byte offset of its float32 weights in the blob, or -1 —
+                      // the tail of the request's descriptor slot in plans with weighted columns, null in plans that only use sqrtn
+};
+// One entry point per variant unit, in FcpVariant order: the hybrid kernel when both sides have blocks (one launch, the
+// ragged blocks first), else the ragged or the dense kernel; 0 without a launch when neither has.  Returns a hipError_t.
+// Only the first two serve sharded plans (shard_world > 1); the others refuse them, and a kind that is not theirs, with
+// hipErrorInvalidValue.  fcp_launch_weighted launches the ragged side only: plans of that variant have no dense spans.
+typedef int FcpFusedLauncher(const FcpFusedWork &W, ihipStream_t *s);
+FcpFusedLauncher fcp_launch_f32, fcp_launch_weighted, fcp_launch_narrow, fcp_launch_tab16, fcp_launch_tabq8, fcp_launch_tabmix;
+// (fcp_dense_plain.hip) the small dense kernel of plain dense plans: V 4, R 4, the grid of fcp_launch_f32's dense kernel
 int fcp_launch_dense_plain(const FcpPlainLaunch &P, int grid_blocks, ihipStream_t *s);
-// what the next fused launch of this thread would carry (stop event, any-order flag): taken and cleared
+// what the next fused launch of this thread carries (stop event, any-order flag): taken and cleared (fcp_klaunch,
+// fcp_fused_launch.h; the plain dense kernel's launcher)
 void fcp_take_launch_extras(void **stop_event, int *flags);
 int fcp_launch_upload(const void *host_mapped_src, void *dst, size_t bytes, ihipStream_t *s);
 // bytes (a multiple of 4) from host-mapped pinned memory to device memory by a kernel; both 4-byte aligned and equally

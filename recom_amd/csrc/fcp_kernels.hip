@@ -37,13 +37,12 @@
 #include <stdlib.h>
 
 #include <atomic>
-#include <type_traits>
 
 #include "../../include/fcp_hip.h"
 #include <hip/hip_ext.h>
 #include "fcp_internal.h"
 
-#include "fcp_fused_bodies.h"
+#include "fcp_fused_launch.h"
 
 namespace {
 
@@ -53,24 +52,10 @@ __global__ void __launch_bounds__(FCP_BLOCK_THREADS) __attribute__((amdgpu_waves
   ragged_body<V, SHARDED>(L, blockIdx.x, smem);
 }
 
-// ---------------------------------------------------------------------------
-// Hybrid launch: plans that mix one-hot and pooled columns (the reference's models
-// E / F: ~98 % bucketize / hash one-hot columns plus a few multi-hot ones).  Spans
-// whose columns are all GATHER / PASSTHROUGH run the dense body, the other spans
-// the ragged body — in ONE launch (block-uniform branch, one LDS buffer carved by
-// either body), because these models are launch-latency bound: as separate
-// dependent launches they cost 27.6 us per request, see DESIGN.md.
-// ---------------------------------------------------------------------------
-struct FcpHybridLaunch {
-  FcpLaunch ragged; // blocks [0, ragged_blocks)
-  FcpLaunch dense;  // blocks [ragged_blocks, grid)
-  int32_t ragged_blocks;
-};
-
+// (the hybrid launch: fcp_fused_launch.h)
 template <int V, int R, bool SHARDED>
 __global__ void __launch_bounds__(FCP_BLOCK_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) fcp_hybrid_kernel(const FcpHybridLaunch H) {
-  constexpr size_t kSmem = sizeof(RaggedLds) > sizeof(DenseLds<R>) ? sizeof(RaggedLds) : sizeof(DenseLds<R>);
-  __shared__ __attribute__((aligned(16))) char smem[kSmem];
+  __shared__ __attribute__((aligned(16))) char smem[kHybridLds<R>];
   const int bid = blockIdx.x;
   if (bid < H.ragged_blocks) {
     ragged_body<V, SHARDED>(H.ragged, bid, smem); // the longer-running blocks are dispatched first
@@ -391,75 +376,25 @@ bool fcp_stop_event_pending() { return tl_stop_event != nullptr; }
 // between 10 and 20 us, against 22.7 us with the barrier bit).
 static thread_local int tl_launch_flags = 0;
 void fcp_set_any_order(bool on) { tl_launch_flags = on ? (int)hipExtAnyOrderLaunch : 0; }
-// for the launchers of other translation units (fcp_weighted.hip): takes and clears what FCP_KLAUNCH would take
+// what fcp_klaunch (fcp_fused_launch.h) and the plain dense kernel's launcher take, and clear
 void fcp_take_launch_extras(void **stop_event, int *flags) {
   *stop_event = tl_stop_event;
   *flags = tl_launch_flags;
   tl_stop_event = nullptr;
   tl_launch_flags = 0;
 }
-#define FCP_KLAUNCH(KERNEL, GRID, BLOCK, LDS, STREAM, ...)                                      \
-  do {                                                                                          \
-    hipEvent_t stop_ = tl_stop_event;                                                           \
-    const int flags_ = tl_launch_flags;                                                         \
-    tl_stop_event = nullptr;                                                                    \
-    tl_launch_flags = 0;                                                                        \
-    if (stop_ || flags_)                                                                        \
-      hipExtLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, nullptr, stop_, flags_, __VA_ARGS__); \
-    else                                                                                        \
-      hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, __VA_ARGS__);                        \
-  } while (0)
 
-// A run-time value as a template argument: f(std::integral_constant<int, N>()) for the first N of the list equal to v,
-// for the last one when none is.
-template <int N, int... Rest, typename F> void with_int(int v, F &&f) {
-  if constexpr (sizeof...(Rest) == 0)
-    f(std::integral_constant<int, N>());
-  else if (v == N)
-    f(std::integral_constant<int, N>());
-  else
-    with_int<Rest...>(v, f);
-}
-template <typename F> void with_bool(bool v, F &&f) {
-  if (v)
-    f(std::true_type());
-  else
-    f(std::false_type());
-}
-
-// vec: 4 | 2 | 1; rows_per_wave: dense 1 | 2 | 4 (rows per block = 4 x that); ragged always 1.
-int fcp_launch_fused(const FcpLaunch &L, int vec, bool dense_kernel, int grid_blocks, ihipStream_t *s) {
-  if (grid_blocks <= 0) return 0;
-  const dim3 grid(grid_blocks), block(FCP_BLOCK_THREADS);
-  const bool sharded = L.shard_world > 1;
-  if (dense_kernel) {
-    with_int<4, 2, 1>(vec, [&](auto V) {
-      with_int<4, 2, 1>(L.rows_per_wave, [&](auto R) {
-        with_bool(sharded, [&](auto SHARDED) { FCP_KLAUNCH((fcp_dense_kernel<V, R, SHARDED>), grid, block, 0, s, L); });
-      });
-    });
-  } else {
-    with_int<4, 2, 1>(vec, [&](auto V) {
-      with_bool(sharded, [&](auto SHARDED) { FCP_KLAUNCH((fcp_ragged_kernel<V, SHARDED>), grid, block, 0, s, L); });
-    });
-  }
-  return (int)hipGetLastError();
-}
-
-int fcp_launch_hybrid(const FcpLaunch &Ldense, int dense_blocks, const FcpLaunch &Lragged, int ragged_blocks, int vec,
-                      ihipStream_t *s) {
-  FcpHybridLaunch H;
-  H.ragged = Lragged;
-  H.dense = Ldense;
-  H.ragged_blocks = ragged_blocks;
-  const dim3 grid(dense_blocks + ragged_blocks), block(FCP_BLOCK_THREADS);
-  const bool sharded = Ldense.shard_world > 1;
-  with_int<4, 2, 1>(vec, [&](auto V) {
-    with_int<4, 2, 1>(Ldense.rows_per_wave, [&](auto R) {
-      with_bool(sharded, [&](auto SHARDED) { FCP_KLAUNCH((fcp_hybrid_kernel<V, R, SHARDED>), grid, block, 0, s, H); });
-    });
+// the float32 matrix: every kernel in a sharded and an unsharded instantiation
+int fcp_launch_f32(const FcpFusedWork &W, ihipStream_t *s) {
+  if (W.dense_blocks <= 0 && W.ragged_blocks <= 0) return 0;
+  int e = 0;
+  with_bool(fcp_work_sharded(W), [&](auto SHARDED) {
+    constexpr bool SH = decltype(SHARDED)::value;
+    e = fcp_launch_work(
+        W, s, [](auto V, auto R) { return fcp_dense_kernel<V, R, SH>; }, [](auto V) { return fcp_ragged_kernel<V, SH>; },
+        [](auto V, auto R) { return fcp_hybrid_kernel<V, R, SH>; });
   });
-  return (int)hipGetLastError();
+  return e;
 }
 
 // Launch counters of the kernels outside the fused matrix (fcp_aux_launch_counts): process-wide, relaxed — the stager's

@@ -1091,6 +1091,13 @@ int fcp_plan_create_ex(const fcp_plan_desc_t *desc, const fcp_column_ext_t *ext,
       p->seg_cols.push_back(k);
   }
   p->vec = gcd4;
+  // (plan validation has refused what would be two of these at once)
+  p->variant = p->weighted_kernel  ? FCP_VAR_WEIGHTED
+               : p->out_elem == 2  ? FCP_VAR_NARROW
+               : p->tab_elem == 2  ? FCP_VAR_TAB16
+               : p->tab_elem == 1  ? FCP_VAR_TABQ8
+               : p->tab_mixed()    ? FCP_VAR_TABMIX
+                                   : FCP_VAR_F32;
   // any-order ScatterNd columns last: their part of the CSR scratch (the inverse maps, built with atomic max from zero)
   // is then ONE range at the tail, the only one a request has to clear
   std::stable_partition(p->seg_cols.begin(), p->seg_cols.end(), [&](int32_t k) { return p->cols[k].d.form != FCP_FORM_GATHER_SCATTER; });

@@ -270,6 +270,23 @@ void fill_launch(const fcp_plan *p, const DynSlot &s, int kind, const void *blob
 
 } // namespace fcph
 
+// Per FcpVariant: its unit's entry point, what a failed launch is called, and FCP_LAUNCH_* of its dense kernel less
+// FCP_LAUNCH_DENSE (the three values of a variant follow each other as dense, ragged, hybrid; the weighted variant has one)
+struct VariantEntry {
+  FcpFusedLauncher *launch;
+  const char *what;
+  int32_t launch_base;
+};
+static const VariantEntry kVariants[FCP_VARIANTS] = {
+    {fcp_launch_f32, nullptr /* kF32What */, 0},
+    {fcp_launch_weighted, "weighted ragged kernel launch", FCP_LAUNCH_RAGGED_WEIGHTED - FCP_LAUNCH_RAGGED},
+    {fcp_launch_narrow, "narrow-output kernel launch", FCP_LAUNCH_DENSE_NARROW - FCP_LAUNCH_DENSE},
+    {fcp_launch_tab16, "16-bit-table kernel launch", FCP_LAUNCH_DENSE_TAB16 - FCP_LAUNCH_DENSE},
+    {fcp_launch_tabq8, "8-bit-table kernel launch", FCP_LAUNCH_DENSE_TABQ8 - FCP_LAUNCH_DENSE},
+    {fcp_launch_tabmix, "mixed-table kernel launch", FCP_LAUNCH_DENSE_TABMIX - FCP_LAUNCH_DENSE},
+};
+static const char *const kF32What[4] = {"", "dense kernel launch", "ragged kernel launch", "hybrid kernel launch"}; // by FCP_LAUNCH_*
+
 extern "C" {
 
 // ---- ProcessFeatureColumns ------------------------------------------------------
@@ -357,14 +374,9 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
   fill_launch(p, *slot, 1, a->concated_inputs, arena, store_policy, &L);
   { // fcp_plan_last_launch (diagnostics): the dispatch below, as it will be made
     fcp_plan::LastLaunch &ll = p->last_launch;
-    const int32_t fused = (int32_t)(m.geo[0].grid_blocks > 0) | (int32_t)(m.geo[1].grid_blocks > 0) << 1;
-    ll.kernel.store(p->weighted_kernel ? (m.geo[1].grid_blocks > 0 ? FCP_LAUNCH_RAGGED_WEIGHTED : FCP_LAUNCH_NONE)
-                    : (p->out_elem == 2 && fused) ? fused + (FCP_LAUNCH_DENSE_NARROW - FCP_LAUNCH_DENSE) // narrow plans: fcp_narrow.hip
-                    : (p->tab_elem == 2 && fused) ? fused + (FCP_LAUNCH_DENSE_TAB16 - FCP_LAUNCH_DENSE)  // 16-bit tables: fcp_tables16.hip
-                    : (p->tab_elem == 1 && fused) ? fused + (FCP_LAUNCH_DENSE_TABQ8 - FCP_LAUNCH_DENSE)  // 8-bit tables: fcp_tables_q8.hip
-                    : (p->tab_mixed() && fused)   ? fused + (FCP_LAUNCH_DENSE_TABMIX - FCP_LAUNCH_DENSE) // per-input formats: fcp_tables_mixed.hip
-                                                  : fused,
-                    std::memory_order_relaxed);
+    const int32_t fused = (int32_t)(m.geo[0].grid_blocks > 0) | (int32_t)(m.geo[1].grid_blocks > 0) << 1; // FCP_LAUNCH_DENSE | _RAGGED | _HYBRID
+    const int32_t mine = p->variant == FCP_VAR_WEIGHTED ? fused & FCP_LAUNCH_RAGGED : fused; // (weighted: the ragged kernel only)
+    ll.kernel.store(mine ? mine + kVariants[p->variant].launch_base : FCP_LAUNCH_NONE, std::memory_order_relaxed);
     p->last_dense_front.store(m.geo[0].grid_blocks <= 0 || p->weighted_kernel ? FCP_DENSE_FRONT_NONE
                               : m.plain                                       ? FCP_DENSE_FRONT_PLAIN
                                                                               : FCP_DENSE_FRONT_GENERIC,
@@ -420,72 +432,11 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
     ~ClearAnyOrder() { fcp_set_any_order(false); }
   } clear_any_order;
   if (p->request_order == FCP_ORDER_INPUTS_READY && !queued_before && !capturing) fcp_set_any_order(true);
-  // hybrid dispatch: spans with pooled columns -> ragged body, all other spans -> dense body; a plan with per-id weights
-  // or the sqrtn combiner: every span -> the weighted ragged kernel (plan creation listed them all as ragged)
-  if (p->weighted_kernel) {
-    const int e = fcp_launch_weighted(L, slot_weights(p, slot->d_dyn), p->vec, m.geo[1].grid_blocks, stream);
-    if (e) return hip_fail("weighted ragged kernel launch", (hipError_t)e);
-  } else if (p->out_elem == 2) { // bf16 / fp16 output: the same three dispatches in their narrow instantiations
-    int e = 0;
-    if (m.geo[1].grid_blocks > 0 && m.geo[0].grid_blocks > 0) {
-      FcpLaunch Ld;
-      fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &Ld);
-      e = fcp_launch_narrow_hybrid(Ld, m.geo[0].grid_blocks, L, m.geo[1].grid_blocks, p->vec, p->out_kind, stream);
-    } else if (m.geo[1].grid_blocks > 0) {
-      e = fcp_launch_narrow(L, p->vec, false, p->out_kind, m.geo[1].grid_blocks, stream);
-    } else if (m.geo[0].grid_blocks > 0) {
-      fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &L);
-      e = fcp_launch_narrow(L, p->vec, true, p->out_kind, m.geo[0].grid_blocks, stream);
-    }
-    if (e) return hip_fail("narrow-output kernel launch", (hipError_t)e);
-  } else if (p->tab_elem == 2) { // bf16 / fp16 tables: the same three dispatches in their 16-bit-table instantiations
-    int e = 0;
-    if (m.geo[1].grid_blocks > 0 && m.geo[0].grid_blocks > 0) {
-      FcpLaunch Ld;
-      fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &Ld);
-      e = fcp_launch_tab16_hybrid(Ld, m.geo[0].grid_blocks, L, m.geo[1].grid_blocks, p->vec, p->tab_kind, stream);
-    } else if (m.geo[1].grid_blocks > 0) {
-      e = fcp_launch_tab16(L, p->vec, false, p->tab_kind, m.geo[1].grid_blocks, stream);
-    } else if (m.geo[0].grid_blocks > 0) {
-      fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &L);
-      e = fcp_launch_tab16(L, p->vec, true, p->tab_kind, m.geo[0].grid_blocks, stream);
-    }
-    if (e) return hip_fail("16-bit-table kernel launch", (hipError_t)e);
-  } else if (p->tab_elem == 1) { // 8-bit row-quantised tables: likewise
-    int e = 0;
-    if (m.geo[1].grid_blocks > 0 && m.geo[0].grid_blocks > 0) {
-      FcpLaunch Ld;
-      fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &Ld);
-      e = fcp_launch_tabq8_hybrid(Ld, m.geo[0].grid_blocks, L, m.geo[1].grid_blocks, p->vec, stream);
-    } else if (m.geo[1].grid_blocks > 0) {
-      e = fcp_launch_tabq8(L, p->vec, false, m.geo[1].grid_blocks, stream);
-    } else if (m.geo[0].grid_blocks > 0) {
-      fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &L);
-      e = fcp_launch_tabq8(L, p->vec, true, m.geo[0].grid_blocks, stream);
-    }
-    if (e) return hip_fail("8-bit-table kernel launch", (hipError_t)e);
-  } else if (p->tab_mixed()) { // tables of more than one format: likewise
-    int e = 0;
-    if (m.geo[1].grid_blocks > 0 && m.geo[0].grid_blocks > 0) {
-      FcpLaunch Ld;
-      fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &Ld);
-      e = fcp_launch_tabmix_hybrid(Ld, m.geo[0].grid_blocks, L, m.geo[1].grid_blocks, p->vec, stream);
-    } else if (m.geo[1].grid_blocks > 0) {
-      e = fcp_launch_tabmix(L, p->vec, false, m.geo[1].grid_blocks, stream);
-    } else if (m.geo[0].grid_blocks > 0) {
-      fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &L);
-      e = fcp_launch_tabmix(L, p->vec, true, m.geo[0].grid_blocks, stream);
-    }
-    if (e) return hip_fail("mixed-table kernel launch", (hipError_t)e);
-  } else if (m.geo[1].grid_blocks > 0 && m.geo[0].grid_blocks > 0) {
-    FcpLaunch Ld;
-    fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &Ld);
-    const int e = fcp_launch_hybrid(Ld, m.geo[0].grid_blocks, L, m.geo[1].grid_blocks, p->vec, stream);
-    if (e) return hip_fail("hybrid kernel launch", (hipError_t)e);
-  } else if (m.geo[1].grid_blocks > 0) {
-    const int e = fcp_launch_fused(L, p->vec, false, m.geo[1].grid_blocks, stream);
-    if (e) return hip_fail("ragged kernel launch", (hipError_t)e);
-  } else if (m.geo[0].grid_blocks > 0 && m.plain) { // plain dense plan: the small dense kernel, same grid (fcp_dense_plain.hip)
+  // hybrid dispatch: spans with pooled columns -> ragged body, all other spans -> dense body, in the instantiations of the
+  // plan's variant; a plan with per-id weights or the sqrtn combiner: every span -> the weighted ragged kernel (plan creation
+  // listed them all as ragged)
+  const int dense_blocks = p->variant == FCP_VAR_WEIGHTED ? 0 : m.geo[0].grid_blocks, ragged_blocks = m.geo[1].grid_blocks;
+  if (dense_blocks > 0 && m.plain) { // plain dense plan (float32, dense spans only): the small dense kernel, same grid (fcp_dense_plain.hip)
     const FcpGroupLaunch &G = m.geo[0].groups[0];
     FcpPlainLaunch P;
     P.img = reinterpret_cast<const char *>(slot->d_dyn) + slot_image_off(p);
@@ -499,12 +450,18 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
     P.img_stride = p->plain_stride;
     P.out_stride = p->group_width[0];
     P.store_policy = store_policy;
-    const int e = fcp_launch_dense_plain(P, m.geo[0].grid_blocks, stream);
+    const int e = fcp_launch_dense_plain(P, dense_blocks, stream);
     if (e) return hip_fail("plain dense kernel launch", (hipError_t)e);
-  } else if (m.geo[0].grid_blocks > 0) {
-    fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, &L);
-    const int e = fcp_launch_fused(L, p->vec, true, m.geo[0].grid_blocks, stream);
-    if (e) return hip_fail("dense kernel launch", (hipError_t)e);
+  } else {
+    // L describes the ragged side; the dense side takes a record of its own only next to it
+    FcpLaunch Ld;
+    FcpLaunch *dense = ragged_blocks > 0 ? &Ld : &L;
+    if (dense_blocks > 0) fill_launch(p, *slot, 0, a->concated_inputs, arena, store_policy, dense);
+    const VariantEntry &V = kVariants[p->variant];
+    const FcpFusedWork W = {dense, dense_blocks, &L, ragged_blocks, p->vec, p->variant == FCP_VAR_NARROW ? p->out_kind : p->tab_kind,
+                            slot_weights(p, slot->d_dyn)};
+    const int e = V.launch(W, stream);
+    if (e) return hip_fail(p->variant == FCP_VAR_F32 ? kF32What[(dense_blocks > 0) | (ragged_blocks > 0) << 1] : V.what, (hipError_t)e);
   }
   if (install) { // first kernel on freshly installed descriptors: lets a later install reuse the slot precisely
     const bool taken = attach_done && !fcp_stop_event_pending(); // the launcher took it: the kernel carries the event
