@@ -208,23 +208,13 @@ template <int V> void convert(void *dst, int dst_kind, const void *src, int src_
     stream16<V>(dst, src, rows * (dim / V), src_kind == FCP_TAB_F32, src_kind == FCP_TAB_F32 ? dst_kind : src_kind, s);
 }
 
-bool known_kind(int32_t k) { return k == FCP_TAB_F32 || k == FCP_TAB_BF16 || k == FCP_TAB_F16 || k == FCP_TAB_Q8; }
 int vec_of(int32_t dim) { return dim % 4 == 0 ? 4 : dim % 2 == 0 ? 2 : 1; }
-// the base alignment of a table of `kind`: what a plan asks of the same table
-int base_alignment(int32_t kind, int vec) { return kind == FCP_TAB_F32 ? 4 * vec : kind == FCP_TAB_Q8 ? 4 : 2 * vec; }
 const char *kind_name(int32_t k) { return k == FCP_TAB_F32 ? "float32" : k == FCP_TAB_BF16 ? "bf16" : k == FCP_TAB_F16 ? "fp16" : "q8"; }
 
 } // namespace
 
 extern "C" int64_t fcp_table_row_bytes(int32_t kind, int32_t dim) {
-  if (dim <= 0) return -1;
-  switch (kind) {
-  case FCP_TAB_F32: return 4 * (int64_t)dim;
-  case FCP_TAB_BF16:
-  case FCP_TAB_F16: return 2 * (int64_t)dim;
-  case FCP_TAB_Q8: return (int64_t)dim + 8;
-  default: return -1;
-  }
+  return dim > 0 && fcpf::known_tab_kind(kind) ? fcpf::row_bytes(kind, dim) : -1;
 }
 
 extern "C" int fcp_table_convert(void *dst, int32_t dst_kind, int64_t dst_row0, const void *src, int32_t src_kind, int64_t rows,
@@ -232,18 +222,18 @@ extern "C" int fcp_table_convert(void *dst, int32_t dst_kind, int64_t dst_row0, 
   if (rows < 0) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: rows is negative");
   if (dst_row0 < 0) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: dst_row0 is negative");
   if (dim <= 0) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: dim must be positive");
-  if (!known_kind(dst_kind)) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: dst_kind is no FCP_TAB_* value");
-  if (!known_kind(src_kind)) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: src_kind is no FCP_TAB_* value");
+  if (!fcpf::known_tab_kind(dst_kind)) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: dst_kind is no FCP_TAB_* value");
+  if (!fcpf::known_tab_kind(src_kind)) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: src_kind is no FCP_TAB_* value");
   if (rows > 0 && !dst) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: dst is null");
   if (rows > 0 && !src) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: src is null");
   if (rows + dst_row0 >= (1ll << 32) - 3 || rows >= (1ll << 32) - 3)
     return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: dst_row0 + rows must stay below 2^32 - 3, a plan's row limit");
   const int vec = vec_of(dim);
-  if ((uintptr_t)dst % base_alignment(dst_kind, vec))
-    return fail(FCP_ERR_INVALID_ARGUMENT, std::string("fcp_table_convert: dst is not ") + std::to_string(base_alignment(dst_kind, vec)) +
+  if ((uintptr_t)dst % fcpf::base_alignment(dst_kind, vec))
+    return fail(FCP_ERR_INVALID_ARGUMENT, std::string("fcp_table_convert: dst is not ") + std::to_string(fcpf::base_alignment(dst_kind, vec)) +
                                               "-byte aligned (a " + kind_name(dst_kind) + " table of this dim)");
-  if ((uintptr_t)src % base_alignment(src_kind, vec))
-    return fail(FCP_ERR_INVALID_ARGUMENT, std::string("fcp_table_convert: src is not ") + std::to_string(base_alignment(src_kind, vec)) +
+  if ((uintptr_t)src % fcpf::base_alignment(src_kind, vec))
+    return fail(FCP_ERR_INVALID_ARGUMENT, std::string("fcp_table_convert: src is not ") + std::to_string(fcpf::base_alignment(src_kind, vec)) +
                                               "-byte aligned (a " + kind_name(src_kind) + " table of this dim)");
   if (dst_kind == src_kind)
     return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: dst_kind equals src_kind; exactly one of the two is FCP_TAB_F32");

@@ -36,7 +36,7 @@
 
 #include "../../include/fcp_hip.h"
 
-int fcp_internal_fail(int code, const std::string &msg); // fcp_plan.hip: sets fcp_last_error
+int fcp_internal_fail(int code, const std::string &msg); // fcp_plan_desc.cc: sets fcp_last_error
 
 namespace {
 

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/fcp_hip.h"
+#include "fcp_formats.h"
 
 namespace {
 
@@ -381,7 +382,7 @@ int fcp_harness_last_output(fcp_harness *h, int t, int32_t n_groups, int32_t *gr
   OnDevice on(h->device);
   int32_t out_kind = FCP_OUT_F32;
   if (fcp_plan_out_dtype(h->plan, &out_kind)) return FCP_ERR_INVALID_ARGUMENT;
-  const size_t elem = out_kind == FCP_OUT_F32 ? sizeof(float) : 2;
+  const size_t elem = fcpf::kOut[out_kind].elem;
   for (int32_t g = 0; g < n_groups; ++g) {
     const size_t bytes = (size_t)l.group_shapes[2 * g] * (size_t)l.group_shapes[2 * g + 1] * elem;
     if (bytes) H_TRY(hipMemcpy(host_out[g], l.group_ptrs[g], bytes, hipMemcpyDeviceToHost));

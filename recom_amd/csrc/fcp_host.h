@@ -1,11 +1,14 @@
 // fcp_host.h — what the host-side translation units of libfcp_hip.so share: the plan object, the per-request descriptor
 // cache, the private-stream (lane) state and the helpers that cross files.  Internal: nothing here is part of the ABI
 // (include/fcp_hip.h).  Round 6 carved the single 3 700-line fcp_api.hip into
-//   fcp_plan.hip     plan creation / validation / plan files / geometry / const buffers / placement / accessors
+//   fcp_plan.hip     building the plan object, geometry (compute_dyn), const buffers and device resources, accessors
 //   fcp_process.hip  the request path: descriptor slots, launch records, fcp_internal_process, fcp_process_feature_columns
 //   fcp_lanes.hip    plan-owned private streams (EXPERIMENTAL): lanes, verification, supervisor, result registry
 //   fcp_concat.hip   Addons>ConcatOutputs entry points and fcp_shard_finalize
 //   fcp_stager.hip   Addons>ConcatInputs packers, the request stager, the pack pool
+// and the descriptor level, which needs no GPU header, became a unit of ordinary C++:
+//   fcp_plan_desc.cc validation, the formats' refusals, plan files, the placement gate, fcp_last_error (fcp_plan_desc.h)
+//   fcp_formats.h    the one table of the storage formats' facts (names, flag bits, element and row sizes)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -29,12 +32,12 @@
 #include "../../include/fcp_hip.h"
 #include "fcp_internal.h"
 #include "fcp_env.h"
+#include "fcp_formats.h"
+#include "fcp_plan_desc.h"
 
 namespace fcph {
 
-extern thread_local std::string g_last_error;
-int hip_fail(const char *what, hipError_t e);
-int fail(int code, const std::string &msg);
+int hip_fail(const char *what, hipError_t e); // (fail: fcp_plan_desc.h)
 
 #define HIP_TRY(expr)                                   \
   do {                                                  \
@@ -269,8 +272,8 @@ struct fcp_plan {
   // without weighted columns have no such array).  weighted_kernel: has_weights, or some column's combiner is SQRTN — all
   // spans of the plan run the weighted ragged kernel.
   bool has_weights = false, weighted_kernel = false;
-  // Which unit's fused kernels serve the plan (fcp_internal.h): decided once, when the plan is created, from weighted_kernel,
-  // out_elem, tab_elem and col_kind below; the request path dispatches on it and on nothing else.
+  // Which unit's fused kernels serve the plan (fcp_internal.h): decided once, when the plan is created, by check_desc
+  // (fcp_plan_desc.h); the request path dispatches on it and on nothing else.
   FcpVariant variant = FCP_VAR_F32;
   // Plain dense plan (fcp_dense_plain.hip): float32 concat output, one group, unsharded, V 4, no wide rows, no id transform,
   // every column a gather by int32 / int64 ids or by float32 values bucketized with reproducible boundaries.  Decided at
@@ -302,8 +305,7 @@ struct fcp_plan {
   int col_tab_kind(size_t k) const { return col_kind.empty() ? tab_kind : col_kind[k]; }
   // bytes of one row of the table column k reads
   int64_t col_row_bytes(size_t k, int dim) const {
-    const int kind = col_tab_kind(k);
-    return kind == FCP_TAB_F32 ? 4 * (int64_t)dim : kind == FCP_TAB_Q8 ? (int64_t)dim + 8 : 2 * (int64_t)dim;
+    return fcpf::row_bytes(col_tab_kind(k), dim);
   }
   std::vector<FcpColStatic> h_cols;
   char *d_const = nullptr;

@@ -311,7 +311,7 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
                                       ? (hc.d.vocab - p->desc.shard_rank + p->desc.shard_world - 1) / p->desc.shard_world
                                       : hc.d.vocab;
       // (8-bit row-quantised tables: a row is dim codes and 8 bytes of scale and bias; per-input formats: the table's own kind)
-      if (s[0] != local_vocab || s[1] != hc.d.dim + (p->col_tab_kind(k) == FCP_TAB_Q8 ? 8 : 0))
+      if (s[0] != local_vocab || s[1] != hc.d.dim + fcpf::kTab[p->col_tab_kind(k)].row_tail)
         return fail(FCP_ERR_SHAPE_MISMATCH, "table shape does not match the plan");
     }
   }

@@ -29,7 +29,7 @@
 #include "../../include/fcp_hip.h"
 #include "fcp_env.h"
 
-// failure reporting shared with fcp_plan.hip
+// failure reporting shared with fcp_plan_desc.cc
 int fcp_internal_fail(int code, const std::string &msg);
 extern "C" int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process_result_t *r); // fcp_process.hip
 

@@ -241,10 +241,7 @@ void read(float *dst, const void *table, int kind, const int64_t *ids, int64_t n
   }
 }
 
-bool known_kind(int32_t k) { return k == FCP_TAB_F32 || k == FCP_TAB_BF16 || k == FCP_TAB_F16 || k == FCP_TAB_Q8; }
 int vec_of(int32_t dim) { return dim % 4 == 0 ? 4 : dim % 2 == 0 ? 2 : 1; }
-// the base alignment of a table of `kind`: what a plan asks of the same table (base_alignment of fcp_convert.hip)
-int base_alignment(int32_t kind, int vec) { return kind == FCP_TAB_F32 ? 4 * vec : kind == FCP_TAB_Q8 ? 4 : 2 * vec; }
 const char *kind_name(int32_t k) { return k == FCP_TAB_F32 ? "float32" : k == FCP_TAB_BF16 ? "bf16" : k == FCP_TAB_F16 ? "fp16" : "q8"; }
 
 // The argument checks both entries share, in the stated order; `who` is the entry's name.  The argument is named between
@@ -257,13 +254,13 @@ int check_args(const char *who, const void *table, int32_t kind, int64_t table_r
   if (table_rows < 1 || table_rows >= (1ll << 32) - 3)
     return fail(FCP_ERR_INVALID_ARGUMENT, w + "`table_rows` must lie in [1, 2^32 - 3), a plan's row limit");
   if (dim <= 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`dim` must be positive");
-  if (!known_kind(kind)) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`kind` is no FCP_TAB_* value");
+  if (!fcpf::known_tab_kind(kind)) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`kind` is no FCP_TAB_* value");
   if (n > 0 && !table) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`table` is null");
   if (n > 0 && !row_ids) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`row_ids` is null");
   if (n > 0 && !rows) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`rows` is null");
   const int vec = vec_of(dim);
-  if ((uintptr_t)table % base_alignment(kind, vec))
-    return fail(FCP_ERR_INVALID_ARGUMENT, w + "`table` is not " + std::to_string(base_alignment(kind, vec)) + "-byte aligned (a " +
+  if ((uintptr_t)table % fcpf::base_alignment(kind, vec))
+    return fail(FCP_ERR_INVALID_ARGUMENT, w + "`table` is not " + std::to_string(fcpf::base_alignment(kind, vec)) + "-byte aligned (a " +
                                               kind_name(kind) + " table of this dim)");
   if ((uintptr_t)rows % (4 * vec))
     return fail(FCP_ERR_INVALID_ARGUMENT, w + "`rows` is not " + std::to_string(4 * vec) + "-byte aligned (float32 rows of this dim)");

@@ -9,6 +9,9 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+from .plan import (FLAG_OUT_BF16, FLAG_OUT_F16, FLAG_TABLES_BF16, FLAG_TABLES_F16, FLAG_TABLES_PER_INPUT, FLAG_TABLES_Q8,  # noqa: F401
+                   OUT_FORMATS, TABLE_FORMATS)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FCP_LIB_DIR: loads the library from another build directory (`make -C recom_amd/csrc OUT=<dir>`, e.g. of another commit)
 LIB_PATH = os.path.join(os.environ.get("FCP_LIB_DIR", _HERE), "libfcp_hip.so")
@@ -22,21 +25,15 @@ FCP_ERR_HIP = 4
 FCP_ERR_UNSUPPORTED = 5
 FCP_ERR_NO_DEVICE = 6
 FLAG_HOST_ONLY = 1 << 31  # plan without device resources (layout queries only)
-FLAG_OUT_BF16 = 1 << 1    # narrow output: the concat groups as bf16 / fp16 (at most one of the two)
-FLAG_OUT_F16 = 1 << 2
-OUT_DTYPES = {0: "f32", 1: "bf16", 2: "f16"}   # FCP_OUT_* (fcp_plan_out_dtype)
-OUT_DTYPE_FLAGS = {"f32": 0, "bf16": FLAG_OUT_BF16, "f16": FLAG_OUT_F16}
-FLAG_TABLES_BF16 = 1 << 3  # 16-bit tables: every embedding table of the plan as bf16 / fp16 (at most one of the two)
-FLAG_TABLES_F16 = 1 << 4
-TABLE_DTYPES = {0: "f32", 1: "bf16", 2: "f16"}   # FCP_TAB_* (fcp_plan_table_dtype)
-TABLE_DTYPE_FLAGS = {"f32": 0, "bf16": FLAG_TABLES_BF16, "f16": FLAG_TABLES_F16}
-FLAG_TABLES_Q8 = 1 << 5    # 8-bit row-quantised tables: uint8 [vocab, dim + 8], a float32 scale and bias behind every row
+# the storage formats (plan.OUT_FORMATS / plan.TABLE_FORMATS) as the library numbers them: FCP_OUT_* / FCP_TAB_* -> name, name -> flag bit
+OUT_DTYPES = dict(enumerate(OUT_FORMATS))                                 # fcp_plan_out_dtype
+OUT_DTYPE_FLAGS = {name: f.flag for name, f in OUT_FORMATS.items()}
+ALL_TABLE_DTYPES = dict(enumerate(TABLE_FORMATS))                         # fcp_plan_table_kinds
+ALL_TABLE_DTYPE_FLAGS = {name: f.flag for name, f in TABLE_FORMATS.items()}
 TAB_Q8 = 3                 # FCP_TAB_Q8
-# every table dtype the library knows (the two dicts above are the 16-bit feature's, these add "q8")
-ALL_TABLE_DTYPES = {**TABLE_DTYPES, TAB_Q8: "q8"}
-ALL_TABLE_DTYPE_FLAGS = {**TABLE_DTYPE_FLAGS, "q8": FLAG_TABLES_Q8}
-FLAG_TABLES_PER_INPUT = 1 << 6   # the table format is a property of each device input (ColumnExt.table_kind1), not of the plan
-TAB_MIXED = 255                  # FCP_TAB_MIXED: fcp_plan_table_dtype of a plan whose tables have more than one format; no row format
+TABLE_DTYPES = {k: n for k, n in ALL_TABLE_DTYPES.items() if k != TAB_Q8}   # the 16-bit feature's two dicts: without "q8"
+TABLE_DTYPE_FLAGS = {n: ALL_TABLE_DTYPE_FLAGS[n] for n in TABLE_DTYPES.values()}
+TAB_MIXED = 255            # FCP_TAB_MIXED: fcp_plan_table_dtype of a plan whose tables have more than one format; no row format
 PLAN_TABLE_DTYPES = {**ALL_TABLE_DTYPES, TAB_MIXED: "mixed"}   # what fcp_plan_table_dtype may answer
 TABLE_KINDS = {name: kind for kind, name in ALL_TABLE_DTYPES.items()}   # name -> FCP_TAB_* (fcp_table_convert)
 # fcp_launch_info_t (fcp_plan_last_launch): names of the kernel, store-policy and segment-offset codes

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import dataclasses
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -38,7 +38,24 @@ FLAG_TABLES_BF16, FLAG_TABLES_F16 = 1 << 3, 1 << 4   # 16-bit tables (PlanSpec.t
 FLAG_TABLES_Q8 = 1 << 5   # 8-bit row-quantised tables (PlanSpec.table_dtype "q8" sets the bit)
 Q8_ROW_TAIL = 8           # bytes behind the codes of a q8 row: float32 scale, float32 bias
 FLAG_TABLES_PER_INPUT = 1 << 6   # the table format is a property of each device input (PlanSpec.table_dtypes sets the bit)
-_TABLE_DTYPE_NAMES = ("f32", "bf16", "f16", "q8")
+
+
+class Format(NamedTuple):
+    """One storage format (== recom_amd/csrc/fcp_formats.h): its plan-wide flag bit, bytes per element, bytes behind a row."""
+    flag: int
+    elem: int
+    row_tail: int = 0
+
+    def row_bytes(self, dim: int) -> int:
+        return dim * self.elem + self.row_tail
+
+
+# by plan-file name, in FCP_TAB_* / FCP_OUT_* order
+TABLE_FORMATS = {"f32": Format(0, 4), "bf16": Format(FLAG_TABLES_BF16, 2), "f16": Format(FLAG_TABLES_F16, 2), "q8": Format(FLAG_TABLES_Q8, 1, Q8_ROW_TAIL)}
+OUT_FORMATS = {"f32": Format(0, 4), "bf16": Format(FLAG_OUT_BF16, 2), "f16": Format(FLAG_OUT_F16, 2)}
+_TABLE_DTYPE_NAMES = tuple(TABLE_FORMATS)
+_OUT_BITS = FLAG_OUT_BF16 | FLAG_OUT_F16
+_TAB16_BITS = FLAG_TABLES_BF16 | FLAG_TABLES_F16
 _LOOKUP_FORMS = (FORM_GATHER, FORM_SEGMENT_REDUCE, FORM_GATHER_SCATTER)
 
 
@@ -56,6 +73,27 @@ class TablesQ8Unsupported(ValueError):
 
 class TablesMixedUnsupported(ValueError):
     """A plan kind the mixed-table kernels (per-input table formats) do not serve (the library answers FCP_ERR_UNSUPPORTED)."""
+
+
+# What the kernels of a storage format do not serve, in the library's words and order (fcp_plan_desc.cc holds the same list).
+# A family: its exception, its subject phrase {S}, its kernels' name {K}.  A rule: the families it applies to, whether it looks
+# at a column ("column k: ", the lowest such k), its condition over (plan, plan flags, column), whether it refuses
+# (the family's exception, FCP_ERR_UNSUPPORTED) or is a ValueError (FCP_ERR_INVALID_ARGUMENT), and the message.
+_FAMILIES = {"narrow": (NarrowOutputUnsupported, "narrow output", "narrow"), "mixed": (TablesMixedUnsupported, "per-input table formats", "mixed-table"),
+             "q8": (TablesQ8Unsupported, "8-bit tables", "8-bit-table"), "tab16": (Tables16Unsupported, "16-bit tables", "16-bit-table")}
+_NARROW, _TABLES, _ALL = ("narrow",), ("mixed", "q8", "tab16"), tuple(_FAMILIES)
+_RULES = (
+    (_NARROW, False, lambda p, f, c: f & _OUT_BITS == _OUT_BITS, False, "FCP_FLAG_OUT_BF16 and FCP_FLAG_OUT_F16 exclude each other"),
+    (("q8",), False, lambda p, f, c: f & _TAB16_BITS, False, "FCP_FLAG_TABLES_Q8 and FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16 exclude each other"),
+    (("tab16",), False, lambda p, f, c: f & _TAB16_BITS == _TAB16_BITS, False, "FCP_FLAG_TABLES_BF16 and FCP_FLAG_TABLES_F16 exclude each other"),
+    (_TABLES, False, lambda p, f, c: f & _OUT_BITS, True, "{S} with narrow output (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16): the {K} kernels store float32"),
+    (_NARROW, False, lambda p, f, c: p.shard_world > 1, True, "{S} on a row-sharded plan (shard_world > 1): partial sums cross the exchange in float32"),
+    (_TABLES, False, lambda p, f, c: p.shard_world > 1, True, "{S} on a row-sharded plan (shard_world > 1): the sharded kernels read float32 tables"),
+    (_NARROW, False, lambda p, f, c: p.layout == LAYOUT_PER_COLUMN, True, "{S} needs FCP_LAYOUT_CONCAT: FCP_LAYOUT_PER_COLUMN is the reference's float32 arena"),
+    (_NARROW, True, lambda p, f, c: c.form == FORM_EXTERNAL, True, "{S} with an FCP_FORM_EXTERNAL slot: fcp_concat_outputs_host scatters float32 payloads"),
+    (_ALL, True, lambda p, f, c: c.weights_input >= 0, True, "{S} with per-id weights: weighted plans take the float32 weighted kernel"),
+    (_ALL, True, lambda p, f, c: c.combiner == COMBINER_SQRTN and c.form == FORM_SEGMENT_REDUCE, True, "{S} with FCP_COMBINER_SQRTN: sqrtn plans take the float32 weighted kernel"),
+)
 
 _ID_ELEM_SIZE = {IDS_I32: 4, IDS_I64: 8, IDS_F32_BUCKETIZE: 4}
 _ID_NP_DTYPE = {IDS_I32: np.int32, IDS_I64: np.int64, IDS_F32_BUCKETIZE: np.float32}
@@ -223,47 +261,46 @@ class PlanSpec:
 
     def plan_flags(self) -> int:
         """``fcp_plan_desc_t::flags``: ``flags`` plus the bit ``out_dtype`` stands for."""
-        return (self.flags | {"f32": 0, "bf16": FLAG_OUT_BF16, "f16": FLAG_OUT_F16}.get(self.out_dtype, 0)
-                | {"f32": 0, "bf16": FLAG_TABLES_BF16, "f16": FLAG_TABLES_F16, "q8": FLAG_TABLES_Q8}.get(self.table_dtype, 0)
+        none = Format(0, 0)   # (a name that is no format: validate() says so)
+        return (self.flags | OUT_FORMATS.get(self.out_dtype, none).flag | TABLE_FORMATS.get(self.table_dtype, none).flag
                 | (FLAG_TABLES_PER_INPUT if self.table_dtypes is not None else 0))
 
     @property
     def out_elem_size(self) -> int:
-        return 4 if self.out_dtype == "f32" else 2
+        return OUT_FORMATS[self.out_dtype].elem
+
+    def _refuse(self, family: str) -> None:
+        """Apply ``_RULES`` for one format family: the plan's rules, then column by column (the lowest refused column reports)."""
+        exc, subject, kernels = _FAMILIES[family]
+        f = self.plan_flags()
+        for k, c in [(None, None)] + list(enumerate(self.columns)):
+            for families, per_column, hit, unsupported, text in _RULES:
+                if family in families and per_column == (c is not None) and hit(self, f, c):
+                    where = "" if c is None else f"column {k}: "
+                    raise (exc if unsupported else ValueError)(where + text.format(S=subject, K=kernels))
 
     def validate_out_dtype(self) -> None:
         """The library's rules for narrow output (``fcp_plan_create``): one dtype, and none of the four plan kinds the narrow
         kernels do not serve.  ``NarrowOutputUnsupported`` mirrors FCP_ERR_UNSUPPORTED, ValueError FCP_ERR_INVALID_ARGUMENT."""
-        if self.out_dtype not in ("f32", "bf16", "f16"):
+        if self.out_dtype not in OUT_FORMATS:
             raise ValueError(f"out_dtype must be 'f32', 'bf16' or 'f16', not {self.out_dtype!r}")
-        f = self.plan_flags()
-        if not f & (FLAG_OUT_BF16 | FLAG_OUT_F16):
-            return
-        if f & FLAG_OUT_BF16 and f & FLAG_OUT_F16:
-            raise ValueError("FCP_FLAG_OUT_BF16 and FCP_FLAG_OUT_F16 exclude each other")
-        if self.shard_world > 1:
-            raise NarrowOutputUnsupported("narrow output on a row-sharded plan (shard_world > 1): partial sums cross the exchange in float32")
-        if self.layout == LAYOUT_PER_COLUMN:
-            raise NarrowOutputUnsupported("narrow output needs FCP_LAYOUT_CONCAT: FCP_LAYOUT_PER_COLUMN is the reference's float32 arena")
-        for k, c in enumerate(self.columns):
-            if c.form == FORM_EXTERNAL:
-                raise NarrowOutputUnsupported(f"column {k}: narrow output with an FCP_FORM_EXTERNAL slot: fcp_concat_outputs_host "
-                                              "scatters float32 payloads")
-            if c.weights_input >= 0:
-                raise NarrowOutputUnsupported(f"column {k}: narrow output with per-id weights: weighted plans take the float32 weighted kernel")
-            if c.combiner == COMBINER_SQRTN and c.form == FORM_SEGMENT_REDUCE:
-                raise NarrowOutputUnsupported(f"column {k}: narrow output with FCP_COMBINER_SQRTN: sqrtn plans take the float32 weighted kernel")
+        if self.plan_flags() & _OUT_BITS:
+            self._refuse("narrow")
 
     def with_out_dtype(self, out_dtype: str) -> "PlanSpec":
         return dataclasses.replace(self, out_dtype=out_dtype)
 
+    def _table_format(self) -> Format:
+        """The one format of every table of the plan (plan-wide formats)."""
+        return TABLE_FORMATS["q8" if self.plan_flags() & FLAG_TABLES_Q8 else self.table_dtype]
+
     @property
     def table_elem_size(self) -> int:
-        return 1 if self.plan_flags() & FLAG_TABLES_Q8 else 4 if self.table_dtype == "f32" else 2
+        return self._table_format().elem
 
     def table_row_bytes(self, dim: int) -> int:
         """Bytes of one table row of ``dim`` elements: ``dim`` x the element size, plus scale and bias in a q8 table."""
-        return dim * self.table_elem_size + (Q8_ROW_TAIL if self.plan_flags() & FLAG_TABLES_Q8 else 0)
+        return self._table_format().row_bytes(dim)
 
     # ---- per-input table formats --------------------------------------------
     def read_inputs(self) -> List[int]:
@@ -276,8 +313,7 @@ class PlanSpec:
 
     def input_row_bytes(self, table_input: int, dim: int) -> int:
         """Bytes of one row of ``dim`` elements of device input ``table_input``, in that table's own format."""
-        kind = self.input_table_dtype(table_input)
-        return dim + Q8_ROW_TAIL if kind == "q8" else dim * (4 if kind == "f32" else 2)
+        return TABLE_FORMATS[self.input_table_dtype(table_input)].row_bytes(dim)
 
     def mixed_tables(self) -> bool:
         """Whether the plan's tables really have more than one format (what the library calls FCP_TAB_MIXED)."""
@@ -316,52 +352,22 @@ class PlanSpec:
             kind = names[read[0]] if read else "f32"
             dataclasses.replace(self, table_dtype=kind, table_dtypes=None).validate_table_dtype()
             return
-        if self.plan_flags() & (FLAG_OUT_BF16 | FLAG_OUT_F16):
-            raise TablesMixedUnsupported("per-input table formats with narrow output (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16): the mixed-table kernels store float32")
-        if self.shard_world > 1:
-            raise TablesMixedUnsupported("per-input table formats on a row-sharded plan (shard_world > 1): the sharded kernels read float32 tables")
-        for k, c in enumerate(self.columns):
-            if c.weights_input >= 0:
-                raise TablesMixedUnsupported(f"column {k}: per-input table formats with per-id weights: weighted plans take the float32 weighted kernel")
-            if c.combiner == COMBINER_SQRTN and c.form == FORM_SEGMENT_REDUCE:
-                raise TablesMixedUnsupported(f"column {k}: per-input table formats with FCP_COMBINER_SQRTN: sqrtn plans take the float32 weighted kernel")
+        self._refuse("mixed")
 
     def validate_table_dtype(self) -> None:
         """The library's rules for 16-bit tables (``fcp_plan_create``): one dtype, and none of the three plan kinds the
         16-bit-table kernels do not serve.  ``Tables16Unsupported`` mirrors FCP_ERR_UNSUPPORTED, ValueError
         FCP_ERR_INVALID_ARGUMENT."""
-        if self.table_dtype not in ("f32", "bf16", "f16", "q8"):
+        if self.table_dtype not in TABLE_FORMATS:
             raise ValueError(f"table_dtype must be 'f32', 'bf16', 'f16' or 'q8', not {self.table_dtype!r}")
         if self.table_dtypes is not None:   # per-input table formats: their own rules
             self._validate_table_dtypes()
             return
         f = self.plan_flags()
         if f & FLAG_TABLES_Q8:   # 8-bit row-quantised tables: the same rules, by their own name
-            if f & (FLAG_TABLES_BF16 | FLAG_TABLES_F16):
-                raise ValueError("FCP_FLAG_TABLES_Q8 and FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16 exclude each other")
-            if f & (FLAG_OUT_BF16 | FLAG_OUT_F16):
-                raise TablesQ8Unsupported("8-bit tables with narrow output (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16): the 8-bit-table kernels store float32")
-            if self.shard_world > 1:
-                raise TablesQ8Unsupported("8-bit tables on a row-sharded plan (shard_world > 1): the sharded kernels read float32 tables")
-            for k, c in enumerate(self.columns):
-                if c.weights_input >= 0:
-                    raise TablesQ8Unsupported(f"column {k}: 8-bit tables with per-id weights: weighted plans take the float32 weighted kernel")
-                if c.combiner == COMBINER_SQRTN and c.form == FORM_SEGMENT_REDUCE:
-                    raise TablesQ8Unsupported(f"column {k}: 8-bit tables with FCP_COMBINER_SQRTN: sqrtn plans take the float32 weighted kernel")
-            return
-        if not f & (FLAG_TABLES_BF16 | FLAG_TABLES_F16):
-            return
-        if f & FLAG_TABLES_BF16 and f & FLAG_TABLES_F16:
-            raise ValueError("FCP_FLAG_TABLES_BF16 and FCP_FLAG_TABLES_F16 exclude each other")
-        if f & (FLAG_OUT_BF16 | FLAG_OUT_F16):
-            raise Tables16Unsupported("16-bit tables with narrow output (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16): the 16-bit-table kernels store float32")
-        if self.shard_world > 1:
-            raise Tables16Unsupported("16-bit tables on a row-sharded plan (shard_world > 1): the sharded kernels read float32 tables")
-        for k, c in enumerate(self.columns):
-            if c.weights_input >= 0:
-                raise Tables16Unsupported(f"column {k}: 16-bit tables with per-id weights: weighted plans take the float32 weighted kernel")
-            if c.combiner == COMBINER_SQRTN and c.form == FORM_SEGMENT_REDUCE:
-                raise Tables16Unsupported(f"column {k}: 16-bit tables with FCP_COMBINER_SQRTN: sqrtn plans take the float32 weighted kernel")
+            self._refuse("q8")
+        elif f & _TAB16_BITS:
+            self._refuse("tab16")
 
     def with_table_dtype(self, table_dtype: str) -> "PlanSpec":
         return dataclasses.replace(self, table_dtype=table_dtype)

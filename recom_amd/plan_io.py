@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .plan import COMBINER_SQRTN, ColumnSpec, PlanSpec, StageInfo
+from .plan import COMBINER_SQRTN, OUT_FORMATS, TABLE_FORMATS, ColumnSpec, PlanSpec, StageInfo
 
 
 def save_plan(spec: PlanSpec, path: str, stage: "StageInfo | None" = None) -> None:
@@ -90,19 +90,19 @@ def load_plan(path: str) -> PlanSpec:
             raise ValueError(f"expected 'table_dtypes D k0 ... k(D-1)' in {path}")
         table_dtypes = tuple(nxt() for _ in range(n_kinds))
         for n in table_dtypes:
-            if n not in ("f32", "bf16", "f16", "q8", "-"):
+            if n != "-" and n not in TABLE_FORMATS:
                 raise ValueError(f"unknown table dtype {n!r} in the table_dtypes line of {path}")
     elif version >= 7:              # "table_dtype bf16|f16|q8": the same place and rules, in version 7 files and no others
         if nxt() != "table_dtype":
             raise ValueError(f"expected 'table_dtype bf16', 'table_dtype f16' or 'table_dtype q8' in {path}")
         table_dtype = nxt()
-        if table_dtype not in ("bf16", "f16", "q8"):
+        if table_dtype == "f32" or table_dtype not in TABLE_FORMATS:
             raise ValueError(f"unknown table_dtype {table_dtype!r} in {path}")
     elif version >= 6:            # "out_dtype bf16|f16": here and nowhere else, in version 6 files and no others
         if nxt() != "out_dtype":
             raise ValueError(f"expected 'out_dtype bf16' or 'out_dtype f16' in {path}")
         out_dtype = nxt()
-        if out_dtype not in ("bf16", "f16"):
+        if out_dtype == "f32" or out_dtype not in OUT_FORMATS:
             raise ValueError(f"unknown out_dtype {out_dtype!r} in {path}")
     if nxt() != "layout":
         raise ValueError(f"expected 'layout' in {path}")

@@ -13,7 +13,7 @@ import ctypes as C
 from typing import Optional, Sequence
 
 from . import lib as _lib
-from .plan import FORM_GATHER, FORM_GATHER_SCATTER, FORM_SEGMENT_REDUCE, PlanSpec
+from .plan import FORM_GATHER, FORM_GATHER_SCATTER, FORM_SEGMENT_REDUCE, TABLE_FORMATS, PlanSpec
 
 _FORMS_WITH_TABLES = (FORM_GATHER, FORM_SEGMENT_REDUCE, FORM_GATHER_SCATTER)
 
@@ -43,7 +43,7 @@ def _kind_and_dim(t, what: str):
     if not t.is_cuda:
         raise ValueError(f"{what}: fcp_table_convert works device to device; the tensor is on {t.device}")
     name = names[t.dtype]
-    dim = t.shape[1] - 8 if name == "q8" else t.shape[1]
+    dim = t.shape[1] - TABLE_FORMATS[name].row_tail
     if dim <= 0:
         raise ValueError(f"{what}: a {name} table of shape {tuple(t.shape)} has no elements in a row")
     return name, int(dim)
@@ -62,7 +62,7 @@ def convert(src, dtype: str, out=None, dst_row0: int = 0, stream: Optional[int] 
     if out is None:
         if dst_row0:
             raise ValueError("dst_row0 needs out=: the whole destination table")
-        out = torch.empty((rows, dim + 8 if dtype == "q8" else dim), dtype=_torch_dtypes()[dtype], device=src.device)
+        out = torch.empty((rows, dim + TABLE_FORMATS[dtype].row_tail), dtype=_torch_dtypes()[dtype], device=src.device)
     out_name, out_dim = _kind_and_dim(out, "out")
     if out_name != dtype or out_dim != dim:
         raise ValueError(f"out is a {out_name} table of dim {out_dim}; the call writes a {dtype} table of dim {dim}")
@@ -100,7 +100,7 @@ def convert_from_host(table_cpu, dtype: str, device, chunk_rows: int = 1 << 16):
         raise ValueError("chunk_rows must be positive")
     device = torch.device(device)
     rows, dim = (int(v) for v in table_cpu.shape)
-    out = torch.empty((rows, dim + 8 if dtype == "q8" else dim), dtype=_torch_dtypes()[dtype], device=device)
+    out = torch.empty((rows, dim + TABLE_FORMATS[dtype].row_tail), dtype=_torch_dtypes()[dtype], device=device)
     chunk = min(chunk_rows, max(rows, 1))
     bounce = torch.empty((chunk, dim), dtype=torch.float32, pin_memory=True)
     staged = torch.empty((chunk, dim), dtype=torch.float32, device=device)
