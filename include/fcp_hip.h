@@ -536,6 +536,69 @@ int fcp_table_update_rows(void *table, int32_t kind, int64_t table_rows, int32_t
  * status order are those of fcp_table_update_rows. */
 int fcp_table_read_rows(float *rows, const void *table, int32_t kind, int64_t table_rows, int32_t dim, const int64_t *row_ids,
                         int64_t n, int32_t device, void *stream);
+/* ---- table audit: what each compact format would do to a float32 table, before anything is written --------------------------- */
+/* fcp_table_audit: judge `rows` float32 rows of width `dim` — a table before fcp_table_convert, or the rows of a delta before
+ * fcp_table_update_rows — against FCP_TAB_BF16, FCP_TAB_F16 and FCP_TAB_Q8 at once, reading every source element once (the
+ * part of a row beyond 256 * V elements twice, as the quantiser reads it).  fcp_table_convert and fcp_table_update_rows write
+ * what they write for a row a format cannot hold (+-inf in a 16-bit table, unspecified q8 codes); this entry is how a caller
+ * finds out first.  `src`, `out` and `workspace` are on the device; `workspace` holds fcp_table_audit_workspace_bytes bytes (a
+ * constant, independent of rows and dim) and its content before and after the call means nothing.  Device to device on
+ * `device`, asynchronous on `stream` (a hipStream_t), no allocation, no synchronisation: `out` is read after the stream has
+ * reached the call's end.
+ *
+ * Value model.  rt(x) is what the library itself does to an element on the way to the format and back, all in float32, every
+ * operation rounded once:
+ *   bf16 / fp16   the exact widening of fl16(x), fcp_table_convert's float32 -> 16-bit followed by its 16-bit -> float32;
+ *   q8            fma(float(code), scale, mn) with mn, scale and code exactly as fcp_table_convert's float32 -> q8 forms them
+ *                 for the row.
+ * e = x - rt(x), in float32.  A row is NON-FINITE if any element is NaN or +-inf: it counts in rows_nonfinite, is bad for every
+ * kind, and is not counted in any rows_bad.  A finite row is BAD for a 16-bit kind if any element rounds to +-inf (fp16:
+ * |x| >= 65520), for q8 if max - min overflows float32.  A bad row is left out of that kind's error fields, a non-finite row
+ * out of all sums, so no field is ever NaN.  The sums are float64 sums of exact float64 products of float32 values; their
+ * order is fixed by (rows, dim), there is no atomic operation, and two calls on the same input leave the same bytes in `out`.
+ * kind[FCP_TAB_F32] is zeros with first_bad_row -1.  rows == 0 is valid: zeros, and every first_* field -1.
+ *
+ * Alignment: `src` that of a float32 table of this dim (4 * V bytes, V the largest of 4 | 2 | 1 that divides dim); `out` and
+ * `workspace` 8 bytes.  rows stays below 2^32 - 3, the row limit of a plan's table.
+ *
+ * Status, decided in this order (the first needs no device):
+ *   FCP_ERR_INVALID_ARGUMENT  rows < 0, dim <= 0, a null out or workspace, a null src with rows > 0, rows beyond the row limit,
+ *                             a misaligned pointer; fcp_last_error names the argument;
+ *   FCP_ERR_NO_DEVICE         no usable gfx950 device (rows == 0 included: `out` is written on the device);
+ *   FCP_ERR_HIP               a kernel launch failed. */
+typedef struct fcp_table_audit_kind {
+  int64_t rows_bad;      /* rows this format cannot hold (non-finite rows not counted) */
+  int64_t first_bad_row; /* smallest such row index, -1 if none */
+  double sum_sq_err;     /* sum over good rows of (double)e * e */
+  float max_abs_err;     /* max over good rows of |e| */
+  int32_t reserved;      /* 0 */
+} fcp_table_audit_kind_t;
+typedef struct fcp_table_audit {
+  int64_t rows, rows_nonfinite, first_nonfinite_row; /* a NaN or +-inf in the source; -1 if no such row */
+  double sum_sq;                                     /* sum of (double)x * x over the finite rows */
+  fcp_table_audit_kind_t kind[4];                    /* indexed by FCP_TAB_* */
+} fcp_table_audit_t;
+int64_t fcp_table_audit_workspace_bytes(void);
+int fcp_table_audit(const float *src, int64_t rows, int32_t dim, fcp_table_audit_t *out, void *workspace, int32_t device,
+                    void *stream);
+/* fcp_table_formats_choose: turn a byte budget into one format per table, from the tables' audits (copied to the host).  Host
+ * only, no device.  Minimises  sum_t weight[t] * audits[t].kind[kinds_out[t]].sum_sq_err  subject to
+ * sum_t rows[t] * fcp_table_row_bytes of kinds_out[t] and dims[t]  <=  budget_bytes.  table_weight NULL: 1 / sum_sq of the table
+ * (0 where sum_sq is 0 or its reciprocal overflows), i.e. every table's relative squared error counts alike.  allowed_kinds: bit k admits FCP_TAB_k;
+ * float32 is always admissible, a kind with rows_bad > 0 never is for that table, and a table with rows_nonfinite > 0 stays
+ * float32.  The algorithm is fixed, so the answer is reproducible: per table the lower convex hull of (bytes, weighted error)
+ * over its admissible kinds (equal bytes: the lower error, then the lower FCP_TAB_*; a dim-1 column thus never takes q8, 9
+ * bytes against 4); every table starts at float32; hull steps are taken in increasing order of error added per byte saved
+ * (ties: the lower table index) until the state fits the budget.  Every state reached minimises error + lambda * bytes for
+ * some lambda, so no assignment within the bytes used has a lower error.  kinds_out[n_tables] receives the FCP_TAB_* values,
+ * *bytes_out their bytes, *error_out the weighted error (either may be NULL).
+ *   FCP_ERR_INVALID_ARGUMENT  a null audits / rows / dims / kinds_out with n_tables > 0, n_tables < 0, budget_bytes < 0, a
+ *                             negative rows[t], dims[t] <= 0, a weight or a weighted error that is negative or not finite;
+ *   FCP_ERR_UNSUPPORTED       even the smallest admissible assignment exceeds the budget; fcp_last_error names the bytes it
+ *                             needs, and *bytes_out receives them. */
+int fcp_table_formats_choose(const fcp_table_audit_t *audits, const int64_t *rows, const int32_t *dims, int32_t n_tables,
+                             int64_t budget_bytes, uint32_t allowed_kinds, const double *table_weight, int32_t *kinds_out,
+                             int64_t *bytes_out, double *error_out);
 /* ---- placement gate (replaces check_table_size, cuda_emitter.cc:1080-1094) -------- */
 /* The reference keeps a column on the CPU when its table exceeds max_table_size =
  * 256 MiB (fc_optimize_pass.cc:71, RECOM_CPU_GPU_CO_RUN).  On MI355X the question is

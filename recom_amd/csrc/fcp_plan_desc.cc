@@ -1,9 +1,11 @@
 // fcp_plan_desc.cc — the descriptor level of libfcp_hip.so: descriptor validation, the refusals of the storage formats, the
-// plan-file parser (the one place in the library that reads untrusted text), the placement gate, and the thread's last-error
-// string.  Ordinary C++ without a GPU header (fcp_plan_desc.h); fcp_plan.hip builds the plan object from what this unit decides.
+// plan-file parser (the one place in the library that reads untrusted text), the placement gate, the choice of table formats by
+// budget (fcp_table_formats_choose), and the thread's last-error string.  Ordinary C++ without a GPU header (fcp_plan_desc.h);
+// fcp_plan.hip builds the plan object from what this unit decides.
 #include "fcp_plan_desc.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <utility>
@@ -609,6 +611,90 @@ int fcp_placement_assign(const int64_t *table_bytes, int32_t n_tables, int64_t h
 int fcp_placement_decide(const int64_t *table_bytes, int32_t n_tables, int64_t hbm_bytes, int64_t reserve_bytes,
                          int32_t world, int32_t prefer_mode, fcp_placement_t *out) {
   return fcp_placement_assign(table_bytes, n_tables, hbm_bytes, reserve_bytes, world, prefer_mode, nullptr, out);
+}
+
+// Formats by budget, from the audits of fcp_table_audit (fcp_table_audit.hip; here they are host memory).  Per table the lower
+// convex hull of (bytes, weighted error) over its admissible kinds, walked from float32 towards fewer bytes; all tables'
+// hull steps in one list ordered by error added per byte saved, taken until the budget holds.  Every prefix of that list
+// minimises error + lambda * bytes for the lambda of its last step, which is what makes the state optimal for the bytes it uses.
+int fcp_table_formats_choose(const fcp_table_audit_t *audits, const int64_t *rows, const int32_t *dims, int32_t n_tables,
+                             int64_t budget_bytes, uint32_t allowed_kinds, const double *table_weight, int32_t *kinds_out,
+                             int64_t *bytes_out, double *error_out) {
+  const char *who = "fcp_table_formats_choose: ";
+  if (n_tables < 0) return fail(FCP_ERR_INVALID_ARGUMENT, std::string(who) + "n_tables is negative");
+  if (n_tables > 0 && (!audits || !rows || !dims || !kinds_out))
+    return fail(FCP_ERR_INVALID_ARGUMENT, std::string(who) + "audits, rows, dims or kinds_out is null");
+  if (budget_bytes < 0) return fail(FCP_ERR_INVALID_ARGUMENT, std::string(who) + "budget_bytes is negative");
+  struct Point {
+    int kind;
+    int64_t bytes;
+    double err;
+  };
+  struct Step {
+    double slope; // weighted error added per byte saved
+    int32_t table, to;
+  };
+  std::vector<std::vector<Point>> hull(n_tables);
+  std::vector<Step> steps;
+  int64_t total = 0;
+  for (int32_t t = 0; t < n_tables; ++t) {
+    const std::string where = std::string(who) + "table " + std::to_string(t) + ": ";
+    if (rows[t] < 0) return fail(FCP_ERR_INVALID_ARGUMENT, where + "rows is negative");
+    if (dims[t] <= 0) return fail(FCP_ERR_INVALID_ARGUMENT, where + "dim must be positive");
+    const fcp_table_audit_t &a = audits[t];
+    // (a sum of squares so small that its reciprocal overflows is a table of zeros to every format: weight 0, as for 0)
+    const double w = table_weight ? table_weight[t] : (a.sum_sq > 0.0 && std::isfinite(1.0 / a.sum_sq) ? 1.0 / a.sum_sq : 0.0);
+    if (!(w >= 0.0) || !std::isfinite(w)) return fail(FCP_ERR_INVALID_ARGUMENT, where + "weight is negative or not finite");
+    std::vector<Point> pts;
+    for (int k = 0; k < fcpf::kTabKinds; ++k) {
+      int64_t bytes = 0;
+      if (__builtin_mul_overflow(rows[t], fcpf::row_bytes(k, dims[t]), &bytes))
+        return fail(FCP_ERR_INVALID_ARGUMENT, where + "rows x row bytes overflows 64 bits");
+      if (k == FCP_TAB_F32) {
+        pts.push_back({k, bytes, 0.0});
+        continue;
+      }
+      if (!(allowed_kinds >> k & 1) || a.rows_nonfinite > 0 || a.kind[k].rows_bad > 0) continue;
+      if (bytes >= pts[0].bytes) continue; // no smaller than float32, which loses nothing (q8 at dim 1 or 2)
+      const double err = w * a.kind[k].sum_sq_err; // NaN or inf here would leave the steps without an order
+      if (!(err >= 0.0) || !std::isfinite(err)) return fail(FCP_ERR_INVALID_ARGUMENT, where + "weight x sum_sq_err is negative or not finite");
+      pts.push_back({k, bytes, err});
+    }
+    // most bytes first; equal bytes: the lower error, then the lower FCP_TAB_*, and only that one stays
+    std::stable_sort(pts.begin(), pts.end(), [](const Point &p, const Point &q) {
+      return p.bytes != q.bytes ? p.bytes > q.bytes : p.err != q.err ? p.err < q.err : p.kind < q.kind;
+    });
+    std::vector<Point> &h = hull[t];
+    auto slope = [](const Point &p, const Point &q) { return (q.err - p.err) / (double)(p.bytes - q.bytes); };
+    for (const Point &p : pts) {
+      if (!h.empty() && p.bytes == h.back().bytes) continue;
+      while (h.size() >= 2 && slope(h[h.size() - 2], h.back()) >= slope(h.back(), p)) h.pop_back();
+      h.push_back(p);
+    }
+    for (size_t i = 1; i < h.size(); ++i) steps.push_back({slope(h[i - 1], h[i]), t, (int32_t)i});
+    if (__builtin_add_overflow(total, h[0].bytes, &total)) return fail(FCP_ERR_INVALID_ARGUMENT, std::string(who) + "the float32 tables' bytes overflow 64 bits");
+  }
+  // (a table's slopes rise along its hull, so its steps stay in order)
+  std::stable_sort(steps.begin(), steps.end(), [](const Step &p, const Step &q) {
+    return p.slope != q.slope ? p.slope < q.slope : p.table != q.table ? p.table < q.table : p.to < q.to;
+  });
+  std::vector<int32_t> at(n_tables, 0);
+  for (size_t i = 0; i < steps.size() && total > budget_bytes; ++i) {
+    const Step &s = steps[i];
+    total -= hull[s.table][s.to - 1].bytes - hull[s.table][s.to].bytes;
+    at[s.table] = s.to;
+  }
+  if (bytes_out) *bytes_out = total;
+  if (total > budget_bytes)
+    return fail(FCP_ERR_UNSUPPORTED, std::string(who) + "the smallest admissible assignment needs " + std::to_string(total) + " bytes, the budget is " +
+                                         std::to_string(budget_bytes));
+  double error = 0.0;
+  for (int32_t t = 0; t < n_tables; ++t) {
+    kinds_out[t] = hull[t][at[t]].kind;
+    error += hull[t][at[t]].err;
+  }
+  if (error_out) *error_out = error;
+  return FCP_OK;
 }
 
 } // extern "C"

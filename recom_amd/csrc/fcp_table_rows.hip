@@ -28,46 +28,11 @@
 
 #pragma clang fp contract(off)
 
+#include "fcp_table_walk.h" // (behind the pragma: its code rounds every operation once, too)
+
 static_assert(FCP_TAB_BF16 == FCP_OUT_BF16 && FCP_TAB_F16 == FCP_OUT_F16, "st_out_narrow takes the table kind as its output kind");
 
 namespace {
-
-constexpr int kQSlots = 4;                          // slots of a row a lane of a 64-lane group keeps in registers (fcp_convert.hip)
-constexpr int64_t kMaxLaunchThreads = 1ll << 30;    // per launch: in-launch indices fit 32 bits, grid x block < 2^32
-
-template <int V> __device__ __forceinline__ VF<V> ld_f32(const float *p) {
-  typedef typename VecType<V>::T T;
-  const T t = *as_global(reinterpret_cast<const T *>(p));
-  VF<V> r;
-  __builtin_memcpy(&r, &t, sizeof(T));
-  return r;
-}
-template <int V> __device__ __forceinline__ void st_f32(float *p, const VF<V> &v) {
-  typedef typename VecType<V>::T T;
-  T t;
-  __builtin_memcpy(&t, &v, sizeof(T));
-  *as_global(reinterpret_cast<T *>(p)) = t;
-}
-
-template <int V> __device__ __forceinline__ void minmax(const VF<V> &x, float &mn, float &mx) {
-#pragma unroll
-  for (int i = 0; i < V; ++i) {
-    mn = fminf(mn, x.v[i]);
-    mx = fmaxf(mx, x.v[i]);
-  }
-}
-
-// rint((x - mn) * inv), round-half-even (v_rndne_f32), each operation rounded once; element i in byte i
-template <int V> __device__ __forceinline__ void st_codes(char *p, const VF<V> &x, float mn, float inv) {
-  uint32_t c = 0;
-#pragma unroll
-  for (int i = 0; i < V; ++i) {
-    const float d = x.v[i] - mn;
-    const float q = __builtin_rintf(d * inv);
-    c |= ((uint32_t)(int32_t)q & 0xFFu) << (8 * i);
-  }
-  *as_global(reinterpret_cast<typename Q8Codes<V>::T *>(p)) = (typename Q8Codes<V>::T)c;
-}
 
 // One vector atomicAdd per wave at most: `mine` is set in the one lane that speaks for a skipped row.  Every lane of the wave
 // gets here (no lane has returned yet), so the wave's first lane is there to issue it.
@@ -83,7 +48,7 @@ template <int V, int G>
 __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
     fcp_update_q8_kernel(char *table, const int64_t *ids, const float *src, int32_t rows, int32_t dim, uint64_t table_rows,
                          unsigned long long *skipped) {
-  constexpr int S = G == 64 ? kQSlots : (G == 1 ? 3 : 1); // G == 1: dim 3 is three one-element slots of one lane
+  constexpr int S = slots_in_registers<G>();
   const int tid = threadIdx.x;
   const int lane = tid & (G - 1);
   const int64_t row = (int64_t)blockIdx.x * (FCP_BLOCK_THREADS / G) + tid / G;
@@ -184,8 +149,6 @@ __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
   st_f32<V>(dst + (uint64_t)i * V, x);
 }
 
-inline dim3 blocks_for(int64_t threads) { return dim3((uint32_t)((threads + FCP_BLOCK_THREADS - 1) / FCP_BLOCK_THREADS)); }
-
 template <int V, int G>
 void update_q8_rows(char *table, const int64_t *ids, const float *src, int64_t n, int dim, uint64_t table_rows,
                     unsigned long long *skipped, hipStream_t s) {
@@ -201,11 +164,7 @@ void update_q8_rows(char *table, const int64_t *ids, const float *src, int64_t n
 template <int V>
 void update_q8(char *table, const int64_t *ids, const float *src, int64_t n, int dim, uint64_t table_rows, unsigned long long *skipped,
                hipStream_t s) {
-  const int nslots = dim / V;
-  int g = 1;
-  if (dim > 4)
-    while (g < nslots && g < 64) g <<= 1;
-  switch (g) {
+  switch (group_of(dim, V)) {
   case 1: update_q8_rows<V, 1>(table, ids, src, n, dim, table_rows, skipped, s); break;
   case 2: update_q8_rows<V, 2>(table, ids, src, n, dim, table_rows, skipped, s); break;
   case 4: update_q8_rows<V, 4>(table, ids, src, n, dim, table_rows, skipped, s); break;
@@ -240,9 +199,6 @@ void read(float *dst, const void *table, int kind, const int64_t *ids, int64_t n
                        table_rows);
   }
 }
-
-int vec_of(int32_t dim) { return dim % 4 == 0 ? 4 : dim % 2 == 0 ? 2 : 1; }
-const char *kind_name(int32_t k) { return k == FCP_TAB_F32 ? "float32" : k == FCP_TAB_BF16 ? "bf16" : k == FCP_TAB_F16 ? "fp16" : "q8"; }
 
 // The argument checks both entries share, in the stated order; `who` is the entry's name.  The argument is named between
 // backquotes: `rows` is also part of two other arguments' names.

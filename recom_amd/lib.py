@@ -124,6 +124,18 @@ class Placement(C.Structure):
     _fields_ = [("mode", C.c_int32), ("min_world", C.c_int32), ("bytes_per_gpu", C.c_int64)]
 
 
+class TableAuditKind(C.Structure):
+    """fcp_table_audit_kind_t"""
+    _fields_ = [("rows_bad", C.c_int64), ("first_bad_row", C.c_int64), ("sum_sq_err", C.c_double), ("max_abs_err", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+class TableAudit(C.Structure):
+    """fcp_table_audit_t"""
+    _fields_ = [("rows", C.c_int64), ("rows_nonfinite", C.c_int64), ("first_nonfinite_row", C.c_int64), ("sum_sq", C.c_double),
+                ("kind", TableAuditKind * 4)]
+
+
 class PrivateStreamsStats(C.Structure):
     """fcp_private_streams_stats_t"""
     _fields_ = [("supervised_stream", C.c_void_p), ("requests", C.c_int64), ("lane_requests", C.c_int64), ("evaluations", C.c_int64),
@@ -171,6 +183,7 @@ EXPORTS = [
     "fcp_plan_out_dtype", "fcp_plan_last_dense_front", "fcp_plan_table_dtype",
     "fcp_table_row_bytes", "fcp_table_convert", "fcp_table_update_rows", "fcp_table_read_rows",
     "fcp_plan_table_kinds",
+    "fcp_table_audit_workspace_bytes", "fcp_table_audit", "fcp_table_formats_choose",
 ]
 
 _lib = None
@@ -330,6 +343,13 @@ def load() -> C.CDLL:
                                             C.c_void_p, C.c_int32, C.c_void_p]
         L.fcp_table_read_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
                                           C.c_int32, C.c_void_p]
+    if hasattr(L, "fcp_table_audit"):
+        L.fcp_table_audit_workspace_bytes.restype = C.c_int64
+        L.fcp_table_audit_workspace_bytes.argtypes = []
+        L.fcp_table_audit.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.fcp_table_formats_choose.argtypes = [C.POINTER(TableAudit), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.c_int64,
+                                               C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                               C.POINTER(C.c_double)]
     if L.fcp_abi_version() != FCP_ABI_VERSION:
         raise ImportError("libfcp_hip.so ABI version mismatch; rebuild")
     _lib = L

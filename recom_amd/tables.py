@@ -1,6 +1,8 @@
 """Table conversion on the device (``fcp_table_convert``, recom_amd/csrc/fcp_convert.hip): float32 embedding tables to the
 formats the plans read — bf16, fp16 and 8-bit row-quantised ("q8") — and back, on torch device tensors; and rows of such a
-table written and read back by id (``fcp_table_update_rows`` / ``fcp_table_read_rows``, recom_amd/csrc/fcp_table_rows.hip).
+table written and read back by id (``fcp_table_update_rows`` / ``fcp_table_read_rows``, recom_amd/csrc/fcp_table_rows.hip);
+and, in front of both, the audit of a float32 table against all three formats in one pass (``fcp_table_audit``,
+recom_amd/csrc/fcp_table_audit.hip) with the choice of one format per table from a byte budget (``fcp_table_formats_choose``).
 
 Plans do not quantise; this does, once, at load time.  The value model is the header's (include/fcp_hip.h): float32 -> q8 is
 exactly the tensor ``quantized::embedding_bag_byte_prepack`` returns, q8 -> float32 is ``fma(code, scale, bias)`` rounded
@@ -10,7 +12,8 @@ missing library or device is an error.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+import dataclasses
+from typing import Dict, Optional, Sequence
 
 from . import lib as _lib
 from .plan import FORM_GATHER, FORM_GATHER_SCATTER, FORM_SEGMENT_REDUCE, TABLE_FORMATS, PlanSpec
@@ -212,3 +215,103 @@ def update_from_host(table, ids_cpu, rows_cpu, chunk_rows: int = 1 << 16):
             staged_ids[:m].copy_(bounce_ids[:m], non_blocking=True)
             update_rows(table, staged_ids[:m], staged[:m], stream=stream.cuda_stream)
     return table
+
+
+# ---- audit and formats by budget (fcp_table_audit / fcp_table_formats_choose) ------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class KindAudit:
+    """fcp_table_audit_kind_t: one format's verdict on a float32 table."""
+    rows_bad: int          # finite rows the format cannot hold (an element rounds to +-inf; q8: max - min overflows)
+    first_bad_row: int     # -1 if none
+    sum_sq_err: float      # float64 sum over the good rows of e * e, e = x - rt(x) in float32
+    max_abs_err: float     # float32 max over the good rows of |e|
+
+
+@dataclasses.dataclass(frozen=True)
+class TableAudit:
+    """fcp_table_audit_t on the host.  ``kinds`` maps "f32" | "bf16" | "f16" | "q8" to its ``KindAudit``; ``raw`` is the C
+    struct (what ``choose_dtypes`` hands to the library)."""
+    rows: int
+    dim: int
+    rows_nonfinite: int
+    first_nonfinite_row: int
+    sum_sq: float
+    kinds: Dict[str, KindAudit]
+    raw: "_lib.TableAudit" = dataclasses.field(repr=False, compare=False, default=None)
+
+    def admissible(self, dtype: str) -> bool:
+        """Whether ``convert(table, dtype)`` holds every row of the table."""
+        return dtype == "f32" or (self.rows_nonfinite == 0 and self.kinds[dtype].rows_bad == 0)
+
+
+def _audit_of(raw: "_lib.TableAudit", dim: int) -> TableAudit:
+    kinds = {name: KindAudit(int(raw.kind[k].rows_bad), int(raw.kind[k].first_bad_row), float(raw.kind[k].sum_sq_err),
+                             float(raw.kind[k].max_abs_err)) for name, k in _lib.TABLE_KINDS.items()}
+    return TableAudit(int(raw.rows), int(dim), int(raw.rows_nonfinite), int(raw.first_nonfinite_row), float(raw.sum_sq), kinds, raw)
+
+
+def audit(table_or_rows, stream: Optional[int] = None) -> TableAudit:
+    """``fcp_table_audit``: what bf16, fp16 and q8 would do to the float32 ``[rows, dim]`` device tensor — a table before
+    ``convert``, or the rows of a delta before ``update_rows`` — judged in one pass on the device.  Allocates the result and
+    the workspace, runs on ``stream`` (torch's current stream of the device by default), synchronises it, and returns the
+    host ``TableAudit``."""
+    import torch
+    t = table_or_rows
+    name, dim = _kind_and_dim(t, "table_or_rows")
+    if name != "f32":
+        raise ValueError(f"audit takes a float32 table; this one is {name}")
+    L = _lib.load()
+    words = (C.sizeof(_lib.TableAudit) + 7) // 8
+    if stream is None:
+        stream = torch.cuda.current_stream(t.device).cuda_stream
+    # allocated as that stream's: a block the caching allocator hands out may still have work pending on the stream it was freed on
+    with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=t.device)):
+        out = torch.empty((words,), dtype=torch.int64, device=t.device)
+        workspace = torch.empty((int(L.fcp_table_audit_workspace_bytes()) // 8,), dtype=torch.int64, device=t.device)
+    status = L.fcp_table_audit(C.c_void_p(t.data_ptr()), int(t.shape[0]), dim, C.c_void_p(out.data_ptr()),
+                               C.c_void_p(workspace.data_ptr()), t.device.index or 0, C.c_void_p(stream))
+    _lib.check(status, "fcp_table_audit")
+    torch.cuda.ExternalStream(stream, device=t.device).synchronize()
+    raw = _lib.TableAudit.from_buffer_copy(out.cpu().numpy().tobytes()[:C.sizeof(_lib.TableAudit)])
+    return _audit_of(raw, dim)
+
+
+def audit_tables(spec: PlanSpec, tables: Sequence, stream: Optional[int] = None) -> list:
+    """One ``TableAudit`` per device input of ``spec``: every table a lookup column reads (a shared table once), ``None`` for
+    the inputs no column reads as a table.  The tables are float32."""
+    read = set(spec.read_inputs())
+    return [audit(t, stream=stream) if i in read else None for i, t in enumerate(tables)]
+
+
+def choose_dtypes(spec: PlanSpec, audits: Sequence, budget_bytes: int, allowed: Sequence[str] = ("f32", "bf16", "f16", "q8"),
+                  weights: Optional[Sequence[float]] = None):
+    """``fcp_table_formats_choose`` over the tables ``spec`` reads: the formats that minimise the weighted squared error
+    within ``budget_bytes`` of tables.  ``audits``: what ``audit_tables`` returned (one entry per device input).  ``weights``:
+    one per device input (entries of unread inputs ignored), default 1 / sum of squares of the table.  Returns
+    ``(dtypes, bytes, error)``: the tuple ``PlanSpec.with_table_dtypes`` takes — "-" for inputs no column reads —, the bytes
+    of the chosen tables and their weighted error.  A budget even the smallest admissible assignment exceeds raises
+    ``FcpError`` (FCP_ERR_UNSUPPORTED) naming the bytes needed."""
+    read = spec.read_inputs()
+    if len(audits) != spec.n_device_inputs:
+        raise ValueError(f"audits names {len(audits)} inputs, the plan has {spec.n_device_inputs} device inputs")
+    mask = 0
+    for name in allowed:
+        if name not in _lib.TABLE_KINDS:
+            raise ValueError(f"unknown table dtype {name!r}")
+        mask |= 1 << _lib.TABLE_KINDS[name]
+    for t in read:
+        if audits[t] is None:
+            raise ValueError(f"device input {t} is read as a table and has no audit")
+    n = len(read)
+    raw = (_lib.TableAudit * max(n, 1))(*[audits[t].raw for t in read])
+    rows = (C.c_int64 * max(n, 1))(*[audits[t].rows for t in read])
+    dims = (C.c_int32 * max(n, 1))(*[audits[t].dim for t in read])
+    w = None if weights is None else (C.c_double * max(n, 1))(*[float(weights[t]) for t in read])
+    kinds = (C.c_int32 * max(n, 1))()
+    nbytes, error = C.c_int64(0), C.c_double(0.0)
+    status = _lib.load().fcp_table_formats_choose(raw, rows, dims, n, int(budget_bytes), mask, w, kinds, C.byref(nbytes), C.byref(error))
+    _lib.check(status, "fcp_table_formats_choose")
+    names = ["-"] * spec.n_device_inputs
+    for i, t in enumerate(read):
+        names[t] = _lib.ALL_TABLE_DTYPES[kinds[i]]
+    return tuple(names), int(nbytes.value), float(error.value)
