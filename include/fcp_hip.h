@@ -581,6 +581,52 @@ typedef struct fcp_table_audit {
 int64_t fcp_table_audit_workspace_bytes(void);
 int fcp_table_audit(const float *src, int64_t rows, int32_t dim, fcp_table_audit_t *out, void *workspace, int32_t device,
                     void *stream);
+/* fcp_table_audit_weighted: fcp_table_audit with one count per row — how often requests read the row, as fcp_table_count_ids
+ * counts it.  `row_counts` is uint32 [rows] on the device.  With w_r = (double)row_counts[r] (exact) the three kinds of sums
+ * become traffic-weighted: sum_sq = sum of w_r * x * x, kind[k].sum_sq_err = sum of w_r * e * e, each term added as ONE
+ * fma(w_r, (double)e * (double)e, sum) — the square is exact in float64, the fused multiply-add rounds the running sum once, so
+ * the sums keep the audit's bound (non-negative terms, within n * 2^-53 of the exact sum, relative, in any order).  The order is
+ * the audit's own, fixed by (rows, dim), without atomics: two calls on the same input leave the same bytes, and with row_counts
+ * all ones `out` is byte for byte what fcp_table_audit writes.
+ * Everything that decides whether a format is ADMISSIBLE stays unweighted and equals fcp_table_audit's, field for field: rows,
+ * rows_nonfinite, first_nonfinite_row and per kind rows_bad, first_bad_row and max_abs_err.  Counts are a sample: a row nobody
+ * read yesterday must still not come back as +-inf tomorrow.  A row of count 0 adds +0 to the sums and still counts if it is
+ * bad; a bad or non-finite row is left out of the sums whatever its count, so no field is ever NaN; reserved stays 0.
+ * fcp_table_formats_choose takes such audits as they are: it minimises whatever sum_sq_err it is handed, and its default table
+ * weight, 1 / sum_sq, then makes every table's relative TRAFFIC-weighted squared error count alike.
+ * The struct, the workspace (fcp_table_audit_workspace_bytes), the arguments, alignment, limits, asynchrony and the status
+ * order are those of fcp_table_audit; `row_counts` joins the argument checks (FCP_ERR_INVALID_ARGUMENT): null with rows > 0
+ * (behind a null src), not 4-byte aligned (behind a misaligned src).  `row_counts` is only read. */
+int fcp_table_audit_weighted(const float *src, int64_t rows, int32_t dim, const uint32_t *row_counts, fcp_table_audit_t *out,
+                             void *workspace, int32_t device, void *stream);
+/* ---- table traffic: how often requests read each row ------------------------------------------------------------------------ */
+/* fcp_table_count_ids: add, to counts[r], the number of times r occurs among the `n` ids — the read counts of a table's rows,
+ * taken from sampled requests, for fcp_table_audit_weighted.  `counts` is uint32 [table_rows] on the device (the caller zeroes
+ * it once and may call any number of times); `ids` is int64 [n] (id_bytes 8) or int32 [n] (id_bytes 4, sign-extended) on the
+ * device — the two id formats a plan's request carries, so the id inputs of a request are counted as delivered.  Accumulation
+ * is modulo 2^32: the caller keeps a row below 4 G reads, or halves the array.  The ids are counted as handed over: a column
+ * whose plan transforms its ids (hash, bucketize, filter, slot offset) is counted from what the caller's pipeline holds after
+ * the transform.
+ *
+ * An id outside [0, table_rows) — the whole 64-bit value is compared, as the plans and fcp_table_update_rows compare ids —
+ * touches no memory and is counted in *skipped: an int64 counter on the device, increased by the number of such ids (the caller
+ * zeroes it); `skipped` may be NULL.
+ *
+ * Device to device on `device`, asynchronous on `stream` (a hipStream_t), no allocation, no synchronisation.  Concurrent calls
+ * on other streams into the same `counts` are allowed: integer adds commute, the result is exact and independent of any order.
+ * `counts` must not overlap `ids` (not checked).  Alignment: `counts` 4 bytes, `ids` id_bytes, `skipped` 8.  table_rows lies in
+ * [1, 2^32 - 3), the row limit of a plan's table.
+ *
+ * Status, decided in this order (the first two need no device), as in fcp_table_update_rows:
+ *   FCP_ERR_INVALID_ARGUMENT  n < 0, table_rows outside its range, an id_bytes that is neither 4 nor 8, a null counts or ids
+ *                             with n > 0, a misaligned counts / ids / skipped; fcp_last_error names the argument between
+ *                             backquotes;
+ *   FCP_OK                    n == 0: nothing is launched and no device is touched;
+ *   FCP_ERR_NO_DEVICE         no usable gfx950 device;
+ *   FCP_ERR_HIP               a kernel launch failed.
+ * No combination of valid arguments is FCP_ERR_UNSUPPORTED. */
+int fcp_table_count_ids(uint32_t *counts, int64_t table_rows, const void *ids, int32_t id_bytes, int64_t n, int64_t *skipped,
+                        int32_t device, void *stream);
 /* fcp_table_formats_choose: turn a byte budget into one format per table, from the tables' audits (copied to the host).  Host
  * only, no device.  Minimises  sum_t weight[t] * audits[t].kind[kinds_out[t]].sum_sq_err  subject to
  * sum_t rows[t] * fcp_table_row_bytes of kinds_out[t] and dims[t]  <=  budget_bytes.  table_weight NULL: 1 / sum_sq of the table

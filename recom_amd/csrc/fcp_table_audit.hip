@@ -1,9 +1,9 @@
-// fcp_table_audit.hip — fcp_table_audit / fcp_table_audit_workspace_bytes: what a float32 table (or the float32 rows of a delta)
+// fcp_table_audit.hip — fcp_table_audit / fcp_table_audit_weighted / fcp_table_audit_workspace_bytes: what a float32 table (or the float32 rows of a delta)
 // would lose in each of the compact formats the plans read (FCP_TAB_BF16 / _F16 / _Q8), and which of its rows a format
 // cannot hold at all, judged on the device in ONE pass over the source — before fcp_table_convert or fcp_table_update_rows
 // writes a single byte.  The reference reads float32 tables only and has no counterpart.
 //
-//   fcp_table_audit_kernel<V, G>   the row walk of fcp_quantize_q8_kernel<V, G> (fcp_convert.hip; fcp_table_walk.h) — the same 3 V x 7 G
+//   fcp_table_audit_kernel<V, G, WEIGHTED>   the row walk of fcp_quantize_q8_kernel<V, G> (fcp_convert.hip; fcp_table_walk.h) — the same 3 V x 7 G
 //                     matrix, the same power-of-two group of G <= 64 lanes per row, loads of V = 4 | 2 | 1 elements, the row
 //                     kept in registers between the two passes (kQSlots slots per lane of a 64-lane group; what lies beyond
 //                     is read a second time, as the quantiser reads it).  Pass one: min, max and the largest |x| as a bit
@@ -20,6 +20,10 @@
 //                     do not fill it); blocks walk the rows with a 64-bit grid-stride loop.  At the end a block folds its lanes
 //                     — butterflies inside a wave, its four waves through one record each in LDS, in wave order — and writes
 //                     ONE partial record to the workspace.
+//                     <V, G, WEIGHTED> (fcp_table_audit_weighted): the same kernel with each term of the sums multiplied by
+//                     the row's read count (uint32, what fcp_table_count_ids fills; exact in float64) inside the one
+//                     v_fma_f64 — flags, counts of bad rows, first rows and maxima untouched.  The unweighted instantiations
+//                     never read row_counts.
 //   fcp_table_audit_fold_kernel    one wave: lane l folds records l, l + 64, ... in block order, a butterfly joins the lanes,
 //                     lane 0 writes fcp_table_audit_t.  rows == 0 launches it alone (no record): zeros, every first_* -1.
 // No floating-point atomics, no atomics at all: which lane adds which row is a function of (rows, dim) alone, every sum has one
@@ -85,23 +89,30 @@ struct LaneSums {
   uint32_t first_nonfinite = kNoSuchRow, first_bad[3] = {kNoSuchRow, kNoSuchRow, kNoSuchRow};
 };
 
-// one term: the square is exact in float64, and the fused multiply-add rounds the sum once
-__device__ __forceinline__ void add_sq(double &sum, uint32_t *max_bits, float e) {
-  sum = __builtin_fma((double)e, (double)e, sum);
+// one term: the square is exact in float64, and the fused multiply-add rounds the sum once.  WEIGHTED: the term is w * e * e
+// with w the row's count (exact in float64), still ONE rounding of the sum — the product of the two squares' factors is formed
+// exactly first (contraction is off: the multiply stays a multiply), then fma(w, e * e, sum).  w == 1 gives the bits of the
+// unweighted form, w == 0 adds +0.  The maxima are never weighted.
+template <bool WEIGHTED> __device__ __forceinline__ void add_sq(double &sum, uint32_t *max_bits, float e, double w) {
+  if constexpr (WEIGHTED)
+    sum = __builtin_fma(w, (double)e * (double)e, sum);
+  else
+    sum = __builtin_fma((double)e, (double)e, sum);
   if (max_bits) *max_bits = max(*max_bits, __float_as_uint(e) & 0x7FFFFFFFu);
 }
 
 // good: bit k set = kind k holds this row; the row is finite (the caller skips the others)
-template <int V> __device__ __forceinline__ void judge(const VF<V> &x, uint32_t good, float mn, float scale, float inv, LaneSums &a) {
+template <int V, bool WEIGHTED>
+__device__ __forceinline__ void judge(const VF<V> &x, uint32_t good, float mn, float scale, float inv, double w, LaneSums &a) {
 #pragma unroll
   for (int i = 0; i < V; ++i) {
     const float v = x.v[i];
-    add_sq(a.sum_sq, nullptr, v);
-    if (good & 1) add_sq(a.sse[0], &a.max_err[0], v - rt_bf16(v));
-    if (good & 2) add_sq(a.sse[1], &a.max_err[1], v - rt_f16(v));
+    add_sq<WEIGHTED>(a.sum_sq, nullptr, v, w);
+    if (good & 1) add_sq<WEIGHTED>(a.sse[0], &a.max_err[0], v - rt_bf16(v), w);
+    if (good & 2) add_sq<WEIGHTED>(a.sse[1], &a.max_err[1], v - rt_f16(v), w);
     if (good & 4) {
       const float code = (float)q8_code(v, mn, inv);
-      add_sq(a.sse[2], &a.max_err[2], v - __builtin_fmaf(code, scale, mn));
+      add_sq<WEIGHTED>(a.sse[2], &a.max_err[2], v - __builtin_fmaf(code, scale, mn), w);
     }
   }
 }
@@ -157,8 +168,12 @@ __device__ __forceinline__ void wave_fold(AuditPartial &p) {
 // src: the table's base; rows: all of them (< 2^32 - 3).  Block = 256 / G rows per step of the stride loop; a group never
 // straddles a wave, and it is live or not as a whole — lanes of rows beyond the end take part in the butterflies and touch no
 // memory.  Every thread of a block takes the same number of steps.
-template <int V, int G>
-__global__ void __launch_bounds__(FCP_BLOCK_THREADS) fcp_table_audit_kernel(const float *src, int64_t rows, int32_t dim, AuditPartial *partials) {
+// WEIGHTED (fcp_table_audit_weighted): row_counts[row] weighs the row's terms of the sums and nothing else — every lane of the
+// group loads the same dword (one address, issued with the row's first loads); the flags, the counts of bad rows, the first
+// rows and the maxima are the unweighted kernel's.  The unweighted instantiations never read row_counts (the last argument).
+template <int V, int G, bool WEIGHTED>
+__global__ void __launch_bounds__(FCP_BLOCK_THREADS)
+    fcp_table_audit_kernel(const float *src, int64_t rows, int32_t dim, AuditPartial *partials, const uint32_t *row_counts) {
   constexpr int S = slots_in_registers<G>();
   constexpr int kRowsPerBlock = FCP_BLOCK_THREADS / G;
   const int tid = threadIdx.x;
@@ -169,6 +184,8 @@ __global__ void __launch_bounds__(FCP_BLOCK_THREADS) fcp_table_audit_kernel(cons
     const int64_t row = base + tid / G;
     const bool live = row < rows;
     const float *srow = src + row * dim;
+    double w = 1.0;
+    if constexpr (WEIGHTED) w = live ? (double)*as_global(row_counts + row) : 0.0;
 
     VF<V> x[S];
     float mn = __builtin_inff(), mx = -__builtin_inff();
@@ -216,11 +233,11 @@ __global__ void __launch_bounds__(FCP_BLOCK_THREADS) fcp_table_audit_kernel(cons
 #pragma unroll
       for (int k = 0; k < S; ++k) {
         const int slot = lane + k * G;
-        if (slot < nslots) judge<V>(x[k], good, mn, scale, inv, a);
+        if (slot < nslots) judge<V, WEIGHTED>(x[k], good, mn, scale, inv, w, a);
       }
       if constexpr (G == 64) {
         for (int slot = lane + S * G; slot < nslots; slot += G) // beyond the register cap: the row's tail is read again
-          judge<V>(ld_f32<V>(srow + (int64_t)slot * V), good, mn, scale, inv, a);
+          judge<V, WEIGHTED>(ld_f32<V>(srow + (int64_t)slot * V), good, mn, scale, inv, w, a);
       }
     }
   }
@@ -274,40 +291,47 @@ __global__ void __launch_bounds__(64) fcp_table_audit_fold_kernel(const AuditPar
   *out = r;
 }
 
-// blocks: what the rows fill of the fixed grid
-template <int V, int G> void audit_rows(const float *src, int64_t rows, int dim, int blocks, AuditPartial *partials, hipStream_t s) {
-  hipLaunchKernelGGL((fcp_table_audit_kernel<V, G>), dim3(blocks), dim3(FCP_BLOCK_THREADS), 0, s, src, rows, (int32_t)dim, partials);
+// blocks: what the rows fill of the fixed grid; row_counts: null = the unweighted kernels
+template <int V, int G>
+void audit_rows(const float *src, int64_t rows, int dim, int blocks, AuditPartial *partials, const uint32_t *row_counts, hipStream_t s) {
+  if (row_counts)
+    hipLaunchKernelGGL((fcp_table_audit_kernel<V, G, true>), dim3(blocks), dim3(FCP_BLOCK_THREADS), 0, s, src, rows, (int32_t)dim, partials,
+                       row_counts);
+  else
+    hipLaunchKernelGGL((fcp_table_audit_kernel<V, G, false>), dim3(blocks), dim3(FCP_BLOCK_THREADS), 0, s, src, rows, (int32_t)dim, partials,
+                       row_counts);
 }
 
-template <int V> void audit(const float *src, int64_t rows, int dim, int g, int blocks, AuditPartial *partials, hipStream_t s) {
+template <int V>
+void audit(const float *src, int64_t rows, int dim, int g, int blocks, AuditPartial *partials, const uint32_t *row_counts, hipStream_t s) {
   switch (g) {
-  case 1: audit_rows<V, 1>(src, rows, dim, blocks, partials, s); break;
-  case 2: audit_rows<V, 2>(src, rows, dim, blocks, partials, s); break;
-  case 4: audit_rows<V, 4>(src, rows, dim, blocks, partials, s); break;
-  case 8: audit_rows<V, 8>(src, rows, dim, blocks, partials, s); break;
-  case 16: audit_rows<V, 16>(src, rows, dim, blocks, partials, s); break;
-  case 32: audit_rows<V, 32>(src, rows, dim, blocks, partials, s); break;
-  default: audit_rows<V, 64>(src, rows, dim, blocks, partials, s); break;
+  case 1: audit_rows<V, 1>(src, rows, dim, blocks, partials, row_counts, s); break;
+  case 2: audit_rows<V, 2>(src, rows, dim, blocks, partials, row_counts, s); break;
+  case 4: audit_rows<V, 4>(src, rows, dim, blocks, partials, row_counts, s); break;
+  case 8: audit_rows<V, 8>(src, rows, dim, blocks, partials, row_counts, s); break;
+  case 16: audit_rows<V, 16>(src, rows, dim, blocks, partials, row_counts, s); break;
+  case 32: audit_rows<V, 32>(src, rows, dim, blocks, partials, row_counts, s); break;
+  default: audit_rows<V, 64>(src, rows, dim, blocks, partials, row_counts, s); break;
   }
 }
 
-} // namespace
-
-extern "C" int64_t fcp_table_audit_workspace_bytes(void) { return (int64_t)kAuditBlocks * (int64_t)sizeof(AuditPartial); }
-
-extern "C" int fcp_table_audit(const float *src, int64_t rows, int32_t dim, fcp_table_audit_t *out, void *workspace, int32_t device,
-                               void *stream) {
-  if (rows < 0) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_audit: rows is negative");
-  if (dim <= 0) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_audit: dim must be positive");
-  if (!out) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_audit: out is null");
-  if (!workspace) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_audit: workspace is null");
-  if (rows > 0 && !src) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_audit: src is null");
-  if (rows >= (1ll << 32) - 3) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_audit: rows must stay below 2^32 - 3, a plan's row limit");
+// Both entries: `who` names the entry in fcp_last_error; weighted: row_counts is an argument (checked, and handed to the kernels).
+int audit_entry(const char *who, const float *src, int64_t rows, int32_t dim, bool weighted, const uint32_t *row_counts,
+                fcp_table_audit_t *out, void *workspace, int32_t device, void *stream) {
+  const std::string w = std::string(who) + ": ";
+  if (rows < 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "rows is negative");
+  if (dim <= 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "dim must be positive");
+  if (!out) return fail(FCP_ERR_INVALID_ARGUMENT, w + "out is null");
+  if (!workspace) return fail(FCP_ERR_INVALID_ARGUMENT, w + "workspace is null");
+  if (rows > 0 && !src) return fail(FCP_ERR_INVALID_ARGUMENT, w + "src is null");
+  if (weighted && rows > 0 && !row_counts) return fail(FCP_ERR_INVALID_ARGUMENT, w + "row_counts is null");
+  if (rows >= (1ll << 32) - 3) return fail(FCP_ERR_INVALID_ARGUMENT, w + "rows must stay below 2^32 - 3, a plan's row limit");
   const int vec = vec_of(dim);
   if ((uintptr_t)src % (4 * vec))
-    return fail(FCP_ERR_INVALID_ARGUMENT, std::string("fcp_table_audit: src is not ") + std::to_string(4 * vec) + "-byte aligned (a float32 table of this dim)");
-  if ((uintptr_t)out % 8) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_audit: out is not 8-byte aligned");
-  if ((uintptr_t)workspace % 8) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_audit: workspace is not 8-byte aligned");
+    return fail(FCP_ERR_INVALID_ARGUMENT, w + "src is not " + std::to_string(4 * vec) + "-byte aligned (a float32 table of this dim)");
+  if (weighted && (uintptr_t)row_counts % 4) return fail(FCP_ERR_INVALID_ARGUMENT, w + "row_counts is not 4-byte aligned");
+  if ((uintptr_t)out % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + "out is not 8-byte aligned");
+  if ((uintptr_t)workspace % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + "workspace is not 8-byte aligned");
   DeviceGuard guard;
   const int rc = guard.enter(device);
   if (rc) return rc;
@@ -316,16 +340,31 @@ extern "C" int fcp_table_audit(const float *src, int64_t rows, int32_t dim, fcp_
   const int g = group_of(dim, vec);
   const int64_t rows_per_block = FCP_BLOCK_THREADS / g;
   const int blocks = (int)std::min<int64_t>(kAuditBlocks, (rows + rows_per_block - 1) / rows_per_block);
-  if (blocks > 0) {
+  if (blocks > 0) { // (rows > 0: a weighted call's row_counts is not null)
+    const uint32_t *counts = weighted ? row_counts : nullptr;
     if (vec == 4)
-      audit<4>(src, rows, dim, g, blocks, partials, s);
+      audit<4>(src, rows, dim, g, blocks, partials, counts, s);
     else if (vec == 2)
-      audit<2>(src, rows, dim, g, blocks, partials, s);
+      audit<2>(src, rows, dim, g, blocks, partials, counts, s);
     else
-      audit<1>(src, rows, dim, g, blocks, partials, s);
+      audit<1>(src, rows, dim, g, blocks, partials, counts, s);
   }
   hipLaunchKernelGGL(fcp_table_audit_fold_kernel, dim3(1), dim3(64), 0, s, partials, (int32_t)blocks, rows, out);
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail("fcp_table_audit: kernel launch", e);
+  if (e != hipSuccess) return hip_fail((w + "kernel launch").c_str(), e);
   return FCP_OK;
+}
+
+} // namespace
+
+extern "C" int64_t fcp_table_audit_workspace_bytes(void) { return (int64_t)kAuditBlocks * (int64_t)sizeof(AuditPartial); }
+
+extern "C" int fcp_table_audit(const float *src, int64_t rows, int32_t dim, fcp_table_audit_t *out, void *workspace, int32_t device,
+                               void *stream) {
+  return audit_entry("fcp_table_audit", src, rows, dim, false, nullptr, out, workspace, device, stream);
+}
+
+extern "C" int fcp_table_audit_weighted(const float *src, int64_t rows, int32_t dim, const uint32_t *row_counts, fcp_table_audit_t *out,
+                                        void *workspace, int32_t device, void *stream) {
+  return audit_entry("fcp_table_audit_weighted", src, rows, dim, true, row_counts, out, workspace, device, stream);
 }

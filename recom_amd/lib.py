@@ -184,6 +184,7 @@ EXPORTS = [
     "fcp_table_row_bytes", "fcp_table_convert", "fcp_table_update_rows", "fcp_table_read_rows",
     "fcp_plan_table_kinds",
     "fcp_table_audit_workspace_bytes", "fcp_table_audit", "fcp_table_formats_choose",
+    "fcp_table_audit_weighted", "fcp_table_count_ids",
 ]
 
 _lib = None
@@ -350,6 +351,9 @@ def load() -> C.CDLL:
         L.fcp_table_formats_choose.argtypes = [C.POINTER(TableAudit), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32, C.c_int64,
                                                C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                                C.POINTER(C.c_double)]
+    if hasattr(L, "fcp_table_count_ids"):
+        L.fcp_table_audit_weighted.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.fcp_table_count_ids.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
     if L.fcp_abi_version() != FCP_ABI_VERSION:
         raise ImportError("libfcp_hip.so ABI version mismatch; rebuild")
     _lib = L

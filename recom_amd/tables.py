@@ -2,7 +2,9 @@
 formats the plans read — bf16, fp16 and 8-bit row-quantised ("q8") — and back, on torch device tensors; and rows of such a
 table written and read back by id (``fcp_table_update_rows`` / ``fcp_table_read_rows``, recom_amd/csrc/fcp_table_rows.hip);
 and, in front of both, the audit of a float32 table against all three formats in one pass (``fcp_table_audit``,
-recom_amd/csrc/fcp_table_audit.hip) with the choice of one format per table from a byte budget (``fcp_table_formats_choose``).
+recom_amd/csrc/fcp_table_audit.hip) with the choice of one format per table from a byte budget (``fcp_table_formats_choose``);
+and the rows' read counts, taken from request ids on the device (``fcp_table_count_ids``, recom_amd/csrc/fcp_table_traffic.hip),
+by which the audit weighs its sums (``fcp_table_audit_weighted``).
 
 Plans do not quantise; this does, once, at load time.  The value model is the header's (include/fcp_hip.h): float32 -> q8 is
 exactly the tensor ``quantized::embedding_bag_byte_prepack`` returns, q8 -> float32 is ``fma(code, scale, bias)`` rounded
@@ -250,13 +252,64 @@ def _audit_of(raw: "_lib.TableAudit", dim: int) -> TableAudit:
     return TableAudit(int(raw.rows), int(dim), int(raw.rows_nonfinite), int(raw.first_nonfinite_row), float(raw.sum_sq), kinds, raw)
 
 
-def audit(table_or_rows, stream: Optional[int] = None) -> TableAudit:
+def _counts_dtypes(torch):
+    """the dtypes a count tensor may have: uint32 where the installed torch has it, and int32, whose bits are read as uint32"""
+    return tuple(d for d in (getattr(torch, "uint32", None), torch.int32) if d is not None)
+
+
+def _check_counts(torch, counts, what: str) -> int:
+    if counts.dtype not in _counts_dtypes(torch) or counts.dim() != 1 or not counts.is_contiguous():
+        raise ValueError(f"{what} is a contiguous 1-D uint32 tensor (or int32, its bits read as uint32): tables.new_counts")
+    return int(counts.shape[0])
+
+
+def new_counts(rows: int, device):
+    """A zeroed read-count tensor of ``rows`` cells on ``device`` for ``count_ids`` and ``audit(..., row_counts=)``: uint32
+    where the installed torch has that dtype, else int32 whose bits are read as uint32 (both are accepted wherever counts are)."""
+    import torch
+    return torch.zeros((int(rows),), dtype=_counts_dtypes(torch)[0], device=device)
+
+
+def count_ids(counts, ids, skipped=None, stream: Optional[int] = None):
+    """``fcp_table_count_ids``: add to ``counts[r]`` (``new_counts``; its length is the table's rows) the number of times ``r``
+    occurs in ``ids`` — an int32 or int64 device tensor of any shape, contiguous: the id input of a sampled request as
+    delivered.  Modulo 2^32.  Ids outside the table touch nothing; ``skipped``, an int64 device tensor of one element, is
+    increased by their number (the caller zeroes it).  Asynchronous on ``stream`` (torch's current stream of the device by
+    default).  Returns ``counts``."""
+    import torch
+    rows = _check_counts(torch, counts, "counts")
+    if not counts.is_cuda:
+        raise ValueError(f"counts: fcp_table_count_ids works on the device; the tensor is on {counts.device}")
+    if ids.dtype not in (torch.int32, torch.int64) or not ids.is_contiguous():
+        raise ValueError("ids is a contiguous int32 or int64 tensor")
+    if ids.device != counts.device:
+        raise ValueError(f"counts is on {counts.device}, ids on {ids.device}")
+    if skipped is not None:
+        if skipped.dtype != torch.int64 or skipped.numel() != 1 or skipped.device != counts.device:
+            raise ValueError("skipped is an int64 tensor of one element on the counts' device")
+    if stream is None:
+        stream = torch.cuda.current_stream(counts.device).cuda_stream
+    status = _lib.load().fcp_table_count_ids(C.c_void_p(counts.data_ptr()), rows, C.c_void_p(ids.data_ptr()), int(ids.element_size()),
+                                             int(ids.numel()), C.c_void_p(skipped.data_ptr()) if skipped is not None else None,
+                                             counts.device.index or 0, C.c_void_p(stream))
+    _lib.check(status, "fcp_table_count_ids")
+    return counts
+
+
+def audit(table_or_rows, row_counts=None, stream: Optional[int] = None) -> TableAudit:
     """``fcp_table_audit``: what bf16, fp16 and q8 would do to the float32 ``[rows, dim]`` device tensor — a table before
-    ``convert``, or the rows of a delta before ``update_rows`` — judged in one pass on the device.  Allocates the result and
+    ``convert``, or the rows of a delta before ``update_rows`` — judged in one pass on the device.  ``row_counts`` (what
+    ``count_ids`` filled: one cell per row, on the table's device) makes it ``fcp_table_audit_weighted``: ``sum_sq`` and every
+    ``sum_sq_err`` weigh a row by its count; the fields that decide admissibility stay unweighted.  Allocates the result and
     the workspace, runs on ``stream`` (torch's current stream of the device by default), synchronises it, and returns the
     host ``TableAudit``."""
     import torch
     t = table_or_rows
+    if row_counts is not None:          # (first: what can be seen of the pair wherever the two tensors live)
+        if _check_counts(torch, row_counts, "row_counts") != t.shape[0]:
+            raise ValueError(f"row_counts has {row_counts.shape[0]} cells, the table {t.shape[0]} rows")
+        if row_counts.device != t.device:
+            raise ValueError(f"the table is on {t.device}, row_counts on {row_counts.device}")
     name, dim = _kind_and_dim(t, "table_or_rows")
     if name != "f32":
         raise ValueError(f"audit takes a float32 table; this one is {name}")
@@ -268,19 +321,29 @@ def audit(table_or_rows, stream: Optional[int] = None) -> TableAudit:
     with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=t.device)):
         out = torch.empty((words,), dtype=torch.int64, device=t.device)
         workspace = torch.empty((int(L.fcp_table_audit_workspace_bytes()) // 8,), dtype=torch.int64, device=t.device)
-    status = L.fcp_table_audit(C.c_void_p(t.data_ptr()), int(t.shape[0]), dim, C.c_void_p(out.data_ptr()),
-                               C.c_void_p(workspace.data_ptr()), t.device.index or 0, C.c_void_p(stream))
-    _lib.check(status, "fcp_table_audit")
+    if row_counts is None:
+        status = L.fcp_table_audit(C.c_void_p(t.data_ptr()), int(t.shape[0]), dim, C.c_void_p(out.data_ptr()),
+                                   C.c_void_p(workspace.data_ptr()), t.device.index or 0, C.c_void_p(stream))
+        _lib.check(status, "fcp_table_audit")
+    else:
+        status = L.fcp_table_audit_weighted(C.c_void_p(t.data_ptr()), int(t.shape[0]), dim, C.c_void_p(row_counts.data_ptr()),
+                                            C.c_void_p(out.data_ptr()), C.c_void_p(workspace.data_ptr()), t.device.index or 0,
+                                            C.c_void_p(stream))
+        _lib.check(status, "fcp_table_audit_weighted")
     torch.cuda.ExternalStream(stream, device=t.device).synchronize()
     raw = _lib.TableAudit.from_buffer_copy(out.cpu().numpy().tobytes()[:C.sizeof(_lib.TableAudit)])
     return _audit_of(raw, dim)
 
 
-def audit_tables(spec: PlanSpec, tables: Sequence, stream: Optional[int] = None) -> list:
+def audit_tables(spec: PlanSpec, tables: Sequence, row_counts: Optional[Sequence] = None, stream: Optional[int] = None) -> list:
     """One ``TableAudit`` per device input of ``spec``: every table a lookup column reads (a shared table once), ``None`` for
-    the inputs no column reads as a table.  The tables are float32."""
+    the inputs no column reads as a table.  The tables are float32.  ``row_counts``: one entry per device input, a count
+    tensor (the table's audit is the weighted one) or ``None`` (unweighted)."""
+    if row_counts is not None and len(row_counts) != len(tables):
+        raise ValueError(f"row_counts names {len(row_counts)} inputs, tables {len(tables)}")
     read = set(spec.read_inputs())
-    return [audit(t, stream=stream) if i in read else None for i, t in enumerate(tables)]
+    return [audit(t, row_counts=None if row_counts is None else row_counts[i], stream=stream) if i in read else None
+            for i, t in enumerate(tables)]
 
 
 def choose_dtypes(spec: PlanSpec, audits: Sequence, budget_bytes: int, allowed: Sequence[str] = ("f32", "bf16", "f16", "q8"),
