@@ -627,6 +627,51 @@ int fcp_table_audit_weighted(const float *src, int64_t rows, int32_t dim, const 
  * No combination of valid arguments is FCP_ERR_UNSUPPORTED. */
 int fcp_table_count_ids(uint32_t *counts, int64_t table_rows, const void *ids, int32_t id_bytes, int64_t n, int64_t *skipped,
                         int32_t device, void *stream);
+/* ---- table traffic of a plan's request: the rows a request reads, counted through the plan's own id path ---------------------
+ * fcp_table_count_ids counts ids as handed over.  Most columns of a plan do not carry row ids: they bucketize float values,
+ * hash, select or filter.  These three entries count what one request — given exactly as fcp_process_feature_columns takes
+ * it — reads of every table, in ONE launch, with the id path the serving kernels themselves run (decode of int32 / int64 /
+ * Bucketize(float32) ids, hash, SELECT / FILTER, the 64-bit compare against the column's vocab).
+ *
+ * What is counted: every column of form GATHER, SEGMENT_REDUCE or GATHER_SCATTER, every position i < nnz of its id stream.
+ * The transformed id is a row: counts[table_input][row] += 1.  It was dropped by the column's FILTER: nothing.  It lies
+ * outside [0, vocab): no memory is touched, *skipped += 1.  This is the reference's GatherV2 — every id that reaches the
+ * lookup counts once: an overwritten id or a dropped row of a scatter column counts, an id of weight 0 counts, every id of a
+ * bag counts.  Columns that share a table add into one array.  On a row-sharded plan the GLOBAL row is counted, without a
+ * rank filter: every rank counts what the unsharded plan would.  The table format, output dtype, layout and kernel variant
+ * of the plan play no part, and the plan's own FCP_FLAG_COUNT_BAD_IDS counter is never touched.  Accumulation is modulo
+ * 2^32, exact, independent of any order and safe against concurrent counts into the same arrays, as in fcp_table_count_ids.
+ * Consequence: the counts equal fcp_table_count_ids applied, per column, to the column's transformed ids with table_rows =
+ * the column's vocab.
+ *
+ * fcp_plan_table_rows: per device input the rows of the UNSHARDED table — the largest `vocab` over the lookup columns that
+ * read the input (columns that share a table need not agree on it), -1 for an input no lookup column reads.  `rows`
+ * receives up to `capacity` values, *n the number of device inputs (either may be NULL), as fcp_plan_table_kinds; any plan,
+ * host-only ones too. */
+int fcp_plan_table_rows(const fcp_plan_t *plan, int64_t *rows, int32_t capacity, int32_t *n);
+/* fcp_plan_traffic_bind: counts[t] is a device uint32 [fcp_plan_table_rows()[t]] array for device input t (the caller zeroes
+ * it), NULL = do not count this table; n_counts must be the plan's number of device inputs; `skipped` is a device int64 (the
+ * caller zeroes it), or NULL.  The plan keeps the pointers (not the memory) until the next bind.  All counts NULL, or
+ * n_counts == 0, unbinds.  The call copies to the device and may synchronise it, as binding tables may: once per sampling
+ * period, not per request, and not concurrently with fcp_plan_traffic_count on the same plan.
+ *   FCP_ERR_INVALID_ARGUMENT  a null plan, n_counts < 0 or neither 0 nor the number of device inputs, a null `counts` with
+ *                             n_counts > 0, a counts[t] that is not 4-byte aligned, a `skipped` that is not 8-byte aligned;
+ *                             fcp_last_error names the argument between backquotes;
+ *   FCP_ERR_NO_DEVICE         a host-only plan (an unbind of one is FCP_OK), no usable device;
+ *   FCP_ERR_HIP               an allocation or copy failed. */
+int fcp_plan_traffic_bind(fcp_plan_t *plan, uint32_t *const *counts, int32_t n_counts, int64_t *skipped);
+/* fcp_plan_traffic_count: count one request.  Of `args` only concated_inputs, concated_bytes, concated_offsets,
+ * concated_shapes, symbols and stream are read: no table pointer, no allocator, no arena — the plan need never have served a
+ * request nor bound a table.  Asynchronous on args->stream, one kernel launch, nothing for a request without ids.  The
+ * request's descriptors are those fcp_process_feature_columns keeps per (shapes, stream): shapes that are resident cost
+ * nothing, new shapes cost what they cost a request (and the request that follows finds them resident); no allocation on
+ * this path.  Under stream capture the status is fcp_process_feature_columns' for the same residency.
+ *   FCP_ERR_INVALID_ARGUMENT  null plan / args, null offsets / shapes, missing symbols, a null blob for a request with ids,
+ *                             no counts bound (fcp_plan_traffic_bind);
+ *   FCP_ERR_SHAPE_MISMATCH    under the conditions, and with the messages, of fcp_process_feature_columns;
+ *   FCP_ERR_UNSUPPORTED       as fcp_process_feature_columns (a capture of shapes that are not resident, ...);
+ *   FCP_ERR_NO_DEVICE / FCP_ERR_HIP. */
+int fcp_plan_traffic_count(fcp_plan_t *plan, const fcp_process_args_t *args);
 /* fcp_table_formats_choose: turn a byte budget into one format per table, from the tables' audits (copied to the host).  Host
  * only, no device.  Minimises  sum_t weight[t] * audits[t].kind[kinds_out[t]].sum_sq_err  subject to
  * sum_t rows[t] * fcp_table_row_bytes of kinds_out[t] and dims[t]  <=  budget_bytes.  table_weight NULL: 1 / sum_sq of the table

@@ -70,6 +70,7 @@ struct DynMeta {
   int64_t arena_bytes = 0;
   int64_t csr_arena_off = 0;
   int32_t max_seg_nnz = 0;
+  int32_t max_lookup_nnz = 0; // longest id stream of a lookup column (GATHER, SEGMENT_REDUCE, GATHER_SCATTER): fcp_plan_traffic_count's grid
   int64_t seg_pairs = 0;   // sum of rows over the segment-id columns: cost of the in-block search
   bool seg_search = false; // this request: blocks search the segment ids (no pre-pass launch)
   bool plain = false;      // plain dense plan and at least 64 rows: the request takes fcp_dense_kernel_plain (its span image is built)
@@ -314,6 +315,12 @@ struct fcp_plan {
   float *d_zeros = nullptr;     // 256 zero bytes (a q8 plan: its longest row, rounded up): the row a skipped id of a bag reads (ld_slot_or_zero)
   std::vector<const void *> bound_tables;
   bool tables_bound = false;
+  // Traffic counting (fcp_plan_traffic_bind / fcp_plan_traffic_count, fcp_table_traffic.hip): the counted lookup columns in
+  // concat order with the count array of each one's table (device array of one entry per plan column, allocated by the first
+  // bind; the first traffic_n entries are live), and the caller's skipped counter.  Under the plan's mutex.
+  FcpTrafficCol *d_traffic = nullptr;
+  int32_t traffic_n = 0; // 0: nothing is bound
+  unsigned long long *traffic_skipped = nullptr;
 
   // How new shape-dependent descriptors reach the device (dynamic shapes: every
   // request).  With a large PCIe BAR the descriptor ring lives in fine-grained

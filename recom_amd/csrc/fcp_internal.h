@@ -185,6 +185,26 @@ struct FcpSegLaunch {
   int32_t skip_inverse;      // 1: leave the any-order scatter columns alone (fcp_shard_finalize only wants row lengths)
 };
 
+// ---- traffic of a request (fcp_table_traffic.hip: fcp_plan_traffic_count) ---------------------------------------------------
+// One entry per counted lookup column, in concat order: the plan-owned list fcp_plan_traffic_bind builds.  A block of the
+// count kernel serves one entry: it reads the column's static and dynamic records at `pos` and adds into `counts`.
+struct FcpTrafficCol {     // 16 bytes
+  uint32_t *counts;        // the read counts of the column's table (device, one cell per row of the unsharded table)
+  int32_t pos;             // the column's position in the plan's record arrays
+  int32_t pad_;
+};
+struct FcpTrafficLaunch {
+  const FcpTrafficCol *list;
+  const FcpColStatic *cols;
+  const FcpColDyn *dyn;
+  const FcpXform *xforms;      // per column (concat order), or null
+  const char *blob;
+  unsigned long long *skipped; // nullable
+};
+// grid: (n_list, tiles of the longest counted id stream); a hipError_t.  (fcp_table_traffic.hip)
+struct ihipStream_t;
+int fcp_launch_plan_traffic(const FcpTrafficLaunch &T, int n_list, int max_nnz, ihipStream_t *s);
+
 // ---- the variants of the fused kernels ------------------------------------------------------------------------------------
 // One per translation unit that instantiates the fused bodies (fcp_fused_bodies.h).  The same value is the template
 // parameter of the bodies, a field of the plan (fcp_plan::variant, decided when the plan is created) and the index of the

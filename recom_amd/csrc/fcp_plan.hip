@@ -95,6 +95,7 @@ int compute_dyn_slow(const fcp_plan *p, const int32_t *offsets, const int32_t *s
     }
   }
   m->max_seg_nnz = 0;
+  m->max_lookup_nnz = 0;
   m->seg_pairs = 0;
   for (int k = 0; k < nc; ++k) {
     const HostColumn &hc = p->cols[k];
@@ -123,6 +124,7 @@ int compute_dyn_slow(const fcp_plan *p, const int32_t *offsets, const int32_t *s
     } else {
       if (n_ids > 0x7fffffff) return fail(FCP_ERR_UNSUPPORTED, "more than 2^31 ids in one column");
       d.nnz = (int32_t)n_ids;
+      if (d.nnz > m->max_lookup_nnz) m->max_lookup_nnz = d.nnz;
       if (c.form == FCP_FORM_GATHER && n_ids != rows)
         return fail(FCP_ERR_SHAPE_MISMATCH, "gather column: ids count != rows");
       if (c.form != FCP_FORM_GATHER) {
@@ -303,7 +305,7 @@ int compute_dyn_fast(const fcp_plan *p, const int32_t *offsets, const int32_t *s
     m->group_base[g] = cursor;
     cursor += align128(rows * p->group_width[g] * p->out_elem);
   }
-  int32_t max_seg_nnz = 0;
+  int32_t max_seg_nnz = 0, max_lookup_nnz = 0;
   int64_t seg_pairs = 0;
   int64_t gathered = 0; // floats
   for (int i = 0; i < nc; ++i) {
@@ -324,6 +326,7 @@ int compute_dyn_fast(const fcp_plan *p, const int32_t *offsets, const int32_t *s
     if (c.form == FCP_FORM_GATHER) {
       if (n_ids != rows) return -1;
       d.nnz = (int32_t)n_ids;
+      if (d.nnz > max_lookup_nnz) max_lookup_nnz = d.nnz;
     } else if (external) {
       d.nnz = 0;
     } else if (c.form == FCP_FORM_PASSTHROUGH) {
@@ -337,6 +340,7 @@ int compute_dyn_fast(const fcp_plan *p, const int32_t *offsets, const int32_t *s
     } else {
       if (n_ids > 0x7fffffff) return -1;
       d.nnz = (int32_t)n_ids;
+      if (d.nnz > max_lookup_nnz) max_lookup_nnz = d.nnz;
       d.seg_off = offsets[c.seg_input];
       const int64_t n_seg = numel[c.seg_input];
       if (c.seg_kind == FCP_SEG_CSR_I32) {
@@ -351,6 +355,7 @@ int compute_dyn_fast(const fcp_plan *p, const int32_t *offsets, const int32_t *s
   }
   m->work_bytes = gathered * 4 + cursor;
   m->max_seg_nnz = max_seg_nnz;
+  m->max_lookup_nnz = max_lookup_nnz;
   m->seg_pairs = seg_pairs;
   m->seg_search = p->seg_search && seg_pairs <= p->env.seg_search_max_pairs;
   m->csr_arena_off = cursor;
@@ -534,6 +539,7 @@ void destroy_device(fcp_plan *p) {
   if (p->d_seg_cols) (void)hipFree(p->d_seg_cols);
   if (p->d_bad) (void)hipFree(p->d_bad);
   if (p->d_zeros) (void)hipFree(p->d_zeros);
+  if (p->d_traffic) (void)hipFree(p->d_traffic);
 }
 
 int init_device(fcp_plan *p) {
@@ -977,6 +983,21 @@ int fcp_plan_table_kinds(const fcp_plan_t *p, int32_t *kinds, int32_t capacity, 
   }
   for (int32_t t = 0; t < p->desc.n_device_inputs && t < capacity; ++t)
     if (kinds) kinds[t] = in_kind[t];
+  if (n) *n = p->desc.n_device_inputs;
+  return FCP_OK;
+}
+
+int fcp_plan_table_rows(const fcp_plan_t *p, int64_t *rows, int32_t capacity, int32_t *n) {
+  if (!p) return fail(FCP_ERR_INVALID_ARGUMENT, "null plan");
+  std::vector<int64_t> in_rows(p->desc.n_device_inputs, -1);
+  for (size_t k = 0; k < p->cols.size(); ++k) {
+    const int f = p->cols[k].d.form;
+    if (f != FCP_FORM_GATHER && f != FCP_FORM_SEGMENT_REDUCE && f != FCP_FORM_GATHER_SCATTER) continue;
+    int64_t &r = in_rows[p->cols[k].d.table_input];
+    r = std::max(r, p->cols[k].d.vocab); // (columns that share a table need not agree on vocab: the largest)
+  }
+  for (int32_t t = 0; t < p->desc.n_device_inputs && t < capacity; ++t)
+    if (rows) rows[t] = in_rows[t];
   if (n) *n = p->desc.n_device_inputs;
   return FCP_OK;
 }

@@ -510,4 +510,103 @@ int fcp_process_feature_columns(fcp_plan_t *p, const fcp_process_args_t *a, fcp_
   return process_on_private_streams(p, a, r); // (experimental: fcp_lanes.hip)
 }
 
+// ---- traffic of a request (the kernel: fcp_table_traffic.hip) ------------------------------------------------------------------
+// The plan-owned list of counted lookup columns: per column in concat order, the counts of its table_input.  Copies, and
+// drains the device when a list is already bound (a count in flight still reads it) — as binding tables does.
+int fcp_plan_traffic_bind(fcp_plan_t *p, uint32_t *const *counts, int32_t n_counts, int64_t *skipped) {
+  const std::string w = "fcp_plan_traffic_bind: ";
+  if (!p) return fail(FCP_ERR_INVALID_ARGUMENT, w + "null plan");
+  if (n_counts < 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`n_counts` is negative");
+  if (n_counts != 0 && n_counts != p->desc.n_device_inputs)
+    return fail(FCP_ERR_INVALID_ARGUMENT, w + "`n_counts` must be the plan's number of device inputs (" +
+                                              std::to_string(p->desc.n_device_inputs) + "), or 0 to unbind");
+  if (n_counts > 0 && !counts) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`counts` is null");
+  for (int32_t t = 0; t < n_counts; ++t)
+    if ((uintptr_t)counts[t] % 4) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`counts[" + std::to_string(t) + "]` is not 4-byte aligned");
+  if ((uintptr_t)skipped % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`skipped` is not 8-byte aligned");
+  std::vector<FcpTrafficCol> list;
+  for (size_t pos = 0; pos < p->cols.size() && n_counts > 0; ++pos) {
+    const fcp_column_desc_t &c = p->cols[p->order[pos]].d;
+    if (c.form != FCP_FORM_GATHER && c.form != FCP_FORM_SEGMENT_REDUCE && c.form != FCP_FORM_GATHER_SCATTER) continue;
+    if (counts[c.table_input]) list.push_back({counts[c.table_input], (int32_t)pos, 0});
+  }
+  if (p->host_only) {
+    if (list.empty()) return FCP_OK; // (an unbind: nothing was ever bound)
+    return fail(FCP_ERR_NO_DEVICE, w + "host-only plan cannot count");
+  }
+  DeviceGuard guard;
+  const int rc = guard.enter(p->desc.device);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lock(p->mu);
+  if (p->traffic_n > 0) HIP_TRY(hipDeviceSynchronize()); // counts in flight still read the old list
+  p->traffic_n = 0;                                       // until the upload below has succeeded
+  p->traffic_skipped = nullptr;
+  if (list.empty()) return FCP_OK;
+  if (!p->d_traffic) HIP_TRY(hipMalloc(&p->d_traffic, p->cols.size() * sizeof(FcpTrafficCol)));
+  HIP_TRY(hipMemcpy(p->d_traffic, list.data(), list.size() * sizeof(FcpTrafficCol), hipMemcpyHostToDevice));
+  p->traffic_n = (int32_t)list.size();
+  p->traffic_skipped = reinterpret_cast<unsigned long long *>(skipped);
+  return FCP_OK;
+}
+
+// The request's descriptors come from the slot cache exactly as a request's do (same key, compute_dyn, upload, `done`
+// protocol): a count of resident shapes installs nothing, a count of new shapes installs what the request itself would.
+// Tables are neither bound nor read, no allocator is called.  (A plain dense plan's span image is built with the table
+// addresses the plan holds, null before the first bind; bind_tables rewrites the images of all slots.)
+int fcp_plan_traffic_count(fcp_plan_t *p, const fcp_process_args_t *a) {
+  const std::string w = "fcp_plan_traffic_count: ";
+  if (!p || !a) return fail(FCP_ERR_INVALID_ARGUMENT, w + "null plan / args");
+  if ((!a->concated_offsets || !a->concated_shapes) && !p->ranks.empty())
+    return fail(FCP_ERR_INVALID_ARGUMENT, w + "null offsets / shapes");
+  if (p->desc.n_symbols > 0 && !a->symbols) return fail(FCP_ERR_INVALID_ARGUMENT, w + "plan needs symbols");
+  if (p->host_only) return fail(FCP_ERR_INVALID_ARGUMENT, w + "no counts are bound (a host-only plan cannot bind any): `fcp_plan_traffic_bind`");
+  DeviceGuard guard;
+  int rc = guard.enter(p->desc.device);
+  if (rc) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(a->stream);
+  DynSlot *slot = nullptr;
+  bool install = false;
+  thread_local std::vector<int32_t> key;
+  build_key(p, a, key);
+  const bool capturing = stream_is_capturing(stream);
+  FcpTrafficLaunch T;
+  int32_t n_list = 0;
+  {
+    std::unique_lock<std::mutex> lock(p->mu);
+    if (p->traffic_n == 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "no counts are bound: `fcp_plan_traffic_bind` first");
+    n_list = p->traffic_n;
+    T.list = p->d_traffic;
+    T.skipped = p->traffic_skipped;
+    while ((rc = find_or_reserve(p, key, &slot, &install, capturing)) == kAllSlotsBusy) {
+      lock.unlock();
+      std::this_thread::yield();
+      lock.lock();
+    }
+    if (rc == kNeedsInstall)
+      return fail(FCP_ERR_UNSUPPORTED, "stream capture of a request whose shapes are not resident: run it once on this stream "
+                                       "before capturing (descriptors cannot be installed inside a capture)");
+    if (rc) return rc;
+  }
+  SlotUnpin unpin{p, slot, false};
+  if (install) {
+    rc = install_slot(p, a, *slot); // on failure the slot stays invalid and is released by `unpin`
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(p->mu);
+    publish_slot(p, *slot, key, a->stream);
+  }
+  const DynMeta &m = slot->meta;
+  if (m.max_lookup_nnz > 0 && !a->concated_inputs) return fail(FCP_ERR_INVALID_ARGUMENT, w + "null blob");
+  T.cols = p->d_cols;
+  T.dyn = slot->d_dyn;
+  T.xforms = p->d_xforms;
+  T.blob = static_cast<const char *>(a->concated_inputs);
+  const int e = fcp_launch_plan_traffic(T, n_list, m.max_lookup_nnz, stream);
+  if (e) return hip_fail("traffic count kernel launch", (hipError_t)e);
+  if (install) { // first kernel on freshly installed descriptors: lets a later install reuse the slot precisely
+    HIP_TRY(hipEventRecord(slot->done, stream));
+    unpin.recorded = true;
+  }
+  return FCP_OK;
+}
+
 } // extern "C"

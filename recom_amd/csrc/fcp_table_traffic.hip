@@ -21,9 +21,27 @@
 //                     The table is as large as LDS allows — one block of 16 waves per CU, 128 KiB of cells — because what it
 //                     cannot hold costs a global atomic per read: rows of the warm middle of a Zipf distribution that find
 //                     their cells taken by cold rows.  profiles/table_traffic.txt has the sizes that were measured.
+//   fcp_plan_traffic_kernel<SLOTS>   fcp_plan_traffic_count: the rows ONE REQUEST of a plan reads, counted through the plan's own
+//                     id path.  A 2-D grid: blockIdx.x names an entry of the plan's list of counted lookup columns
+//                     (FcpTrafficCol: the column's position and its table's counts), blockIdx.y a tile of kTrafficTile
+//                     positions of that column's id stream (a stride loop over tiles where the stream has more than the
+//                     grid's y extent covers).  The block reads its column's static and dynamic records straight into
+//                     wave-uniform registers — one column per block: no span machinery, no LDS copy — and leaves at once,
+//                     before it touches LDS, when its first tile lies past the column's nnz (the grid's y extent is sized
+//                     by the longest stream).  Every position i < nnz goes through fetch_slot_offset<1, false> with
+//                     world = 1 — the id decoded from int32 / int64 / Bucketize(float32) (boundaries from global memory),
+//                     hashed, passed through SELECT / FILTER, compared against the column's vocab — exactly as the fused
+//                     bodies call it: a row adds 1 to counts[row], kFiltered adds nothing, kBadRow touches no memory and
+//                     is counted per wave by ballot and popcount, one 64-bit atomic per wave that saw any.  The plan's own
+//                     bad-id counter is never passed.
+//                     SLOTS > 0: the block's reads go through count_row's LDS table first (a block serves one column,
+//                     hence one table: the same {row, count} cells, SLOTS of them) and are flushed at the end.  SLOTS = 0:
+//                     one global atomic per counted id — built for the measurement only (FCP_TRAFFIC_SLOTS below; the
+//                     figures behind the choice: DESIGN.md 3, profiles/plan_traffic.txt).
 // Every atomic's result is unused except the compare-and-swap's: the global ones are the no-return vector forms
 // (global_atomic_add / global_atomic_add_x2), nothing scalar.  No scratch; LDS: the two arrays and the skipped cell
-// (128 KiB + 8 bytes: a CU holds one block, and the block waits for a CU whose LDS other kernels have left).
+// (fcp_table_count_ids: 128 KiB + 8 bytes — a CU holds one block, and the block waits for a CU whose LDS other kernels have
+// left; fcp_plan_traffic_kernel: its two arrays, 16 KiB).
 #include "fcp_fused_bodies.h"
 #include "fcp_host.h"
 
@@ -43,10 +61,12 @@ static_assert((kCountSlots & (kCountSlots - 1)) == 0 && kCountSlots % kCountThre
 typedef __attribute__((address_space(3))) uint32_t LdsU32;
 
 // one read of row r: into the block's cell for r, or — no cell within the probes — into counts[r] itself
+// (SLOTS: cells of the block's table, a power of two)
+template <int SLOTS = kCountSlots>
 __device__ __forceinline__ void count_row(uint32_t *counts, LdsU32 *s_key, LdsU32 *s_cnt, uint32_t r) {
 #pragma unroll
   for (int p = 0; p < kCountProbes; ++p) {
-    const uint32_t slot = (r + p) & (kCountSlots - 1);
+    const uint32_t slot = (r + p) & (SLOTS - 1);
     uint32_t k = __hip_atomic_load(&s_key[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (k == kEmptyCell) {
       // what the cell held: still empty = claimed for r
@@ -104,7 +124,86 @@ __global__ void __launch_bounds__(kCountThreads)
   if (tid == 0 && skipped && s_skipped != 0) atomicAdd(skipped, s_skipped);
 }
 
+
+// ---- one request of a plan ---------------------------------------------------------------------------------------------------
+constexpr int kTrafficThreads = 256;
+constexpr int kTrafficIdsPerThread = 4;
+constexpr int kTrafficTile = kTrafficThreads * kTrafficIdsPerThread; // positions of an id stream per block and step
+constexpr int kTrafficMaxTilesY = 65535;                             // the grid's y extent; longer streams: the stride loop
+
+template <int SLOTS>
+__global__ void __launch_bounds__(kTrafficThreads) fcp_plan_traffic_kernel(FcpTrafficLaunch T) {
+  static_assert((SLOTS & (SLOTS - 1)) == 0 && SLOTS % kTrafficThreads == 0, "slot masks and the flush loop");
+  __shared__ uint32_t s_key[SLOTS > 0 ? SLOTS : 1];
+  __shared__ uint32_t s_cnt[SLOTS > 0 ? SLOTS : 1];
+  const FcpTrafficCol tc = ld_rec(as_const(T.list) + blockIdx.x);
+  const FcpColDyn d = ld_rec(as_const(T.dyn) + tc.pos);
+  const int nnz = d.nnz;
+  if ((int64_t)blockIdx.y * kTrafficTile >= nnz) return; // (uniform: the whole block, before it touches LDS)
+  LdsCol c; // in registers, wave-uniform: what stage_col would put in LDS, less what the id path does not read
+  static_cast<FcpColStatic &>(c) = ld_rec(as_const(T.cols) + tc.pos);
+  c.ids = T.blob + d.ids_off;
+  c.csr = nullptr;
+  c.out_base = 0;
+  c.out_stride = 0;
+  c.nnz = nnz;
+  const FcpXform *xf = T.xforms + tc.pos; // (only dereferenced by a column with a transform: then the array exists)
+  uint32_t *counts = tc.counts;
+  const int tid = threadIdx.x;
+  if constexpr (SLOTS > 0) {
+    for (int i = tid; i < SLOTS; i += kTrafficThreads) {
+      s_key[i] = kEmptyCell;
+      s_cnt[i] = 0;
+    }
+    __syncthreads();
+  }
+
+  unsigned long long outside = 0; // of this wave: the same value in every lane
+  for (int64_t base = (int64_t)blockIdx.y * kTrafficTile; base < nnz; base += (int64_t)gridDim.y * kTrafficTile) {
+#pragma unroll
+    for (int k = 0; k < kTrafficIdsPerThread; ++k) {
+      const int64_t i = base + k * kTrafficThreads + tid;
+      bool bad = false;
+      uint32_t row = kFiltered;
+      if (i < nnz) row = fetch_slot_offset<1, false>(c, xf, i, nullptr, 0, 1, bad);
+      outside += (unsigned long long)__popcll(__ballot(row == kBadRow));
+      if (is_row(row)) {
+        if constexpr (SLOTS > 0)
+          count_row<SLOTS>(counts, (LdsU32 *)s_key, (LdsU32 *)s_cnt, row);
+        else
+          (void)__hip_atomic_fetch_add(as_global(counts + row), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+  if ((tid & 63) == 0 && outside != 0 && T.skipped)
+    (void)__hip_atomic_fetch_add(as_global(T.skipped), outside, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if constexpr (SLOTS > 0) {
+    __syncthreads();
+    for (int i = tid; i < SLOTS; i += kTrafficThreads) {
+      const uint32_t n = s_cnt[i];
+      // (n != 0: the cell was claimed, its key is a row < vocab)
+      if (n != 0) (void)__hip_atomic_fetch_add(as_global(counts + s_key[i]), n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
 } // namespace
+
+// Cells of a block's table in fcp_plan_traffic_kernel: 2048 (2 x 8 KiB of LDS) for a tile of 1024 ids.  -DFCP_TRAFFIC_SLOTS=0
+// builds the plainer kernel instead — one global atomic per counted id, no LDS — which the choice was measured against
+// (scripts/plan_traffic_cost.py --variant, profiles/plan_traffic.txt); the library is built with the default.
+#ifndef FCP_TRAFFIC_SLOTS
+#define FCP_TRAFFIC_SLOTS 2048
+#endif
+constexpr int kTrafficSlots = FCP_TRAFFIC_SLOTS;
+
+int fcp_launch_plan_traffic(const FcpTrafficLaunch &T, int n_list, int max_nnz, ihipStream_t *s) {
+  if (n_list <= 0 || max_nnz <= 0) return 0;
+  const int tiles = (int)std::min<int64_t>(((int64_t)max_nnz + kTrafficTile - 1) / kTrafficTile, kTrafficMaxTilesY);
+  const dim3 grid((unsigned)n_list, (unsigned)tiles);
+  hipLaunchKernelGGL(fcp_plan_traffic_kernel<kTrafficSlots>, grid, dim3(kTrafficThreads), 0, s, T);
+  return (int)hipGetLastError();
+}
 
 extern "C" int fcp_table_count_ids(uint32_t *counts, int64_t table_rows, const void *ids, int32_t id_bytes, int64_t n, int64_t *skipped,
                                    int32_t device, void *stream) {

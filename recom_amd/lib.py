@@ -185,6 +185,7 @@ EXPORTS = [
     "fcp_plan_table_kinds",
     "fcp_table_audit_workspace_bytes", "fcp_table_audit", "fcp_table_formats_choose",
     "fcp_table_audit_weighted", "fcp_table_count_ids",
+    "fcp_plan_table_rows", "fcp_plan_traffic_bind", "fcp_plan_traffic_count",
 ]
 
 _lib = None
@@ -354,6 +355,10 @@ def load() -> C.CDLL:
     if hasattr(L, "fcp_table_count_ids"):
         L.fcp_table_audit_weighted.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.fcp_table_count_ids.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
+    if hasattr(L, "fcp_plan_traffic_count"):
+        L.fcp_plan_table_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]
+        L.fcp_plan_traffic_bind.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]
+        L.fcp_plan_traffic_count.argtypes = [C.c_void_p, C.POINTER(ProcessArgs)]
     if L.fcp_abi_version() != FCP_ABI_VERSION:
         raise ImportError("libfcp_hip.so ABI version mismatch; rebuild")
     _lib = L

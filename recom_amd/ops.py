@@ -248,6 +248,66 @@ class Plan:
         _lib.check(self._L.fcp_plan_table_kinds(self.handle, kinds, n.value, None), "fcp_plan_table_kinds")
         return tuple("-" if kinds[t] < 0 else _lib.ALL_TABLE_DTYPES[kinds[t]] for t in range(n.value))
 
+    def table_rows(self) -> tuple:
+        """``fcp_plan_table_rows``: per device input the rows of the unsharded table (the largest ``vocab`` of the lookup
+        columns that read it), -1 for an input no lookup column reads — of any plan, host-only ones too."""
+        n = C.c_int32()
+        _lib.check(self._L.fcp_plan_table_rows(self.handle, None, 0, C.byref(n)), "fcp_plan_table_rows")
+        rows = (C.c_int64 * max(1, n.value))()
+        _lib.check(self._L.fcp_plan_table_rows(self.handle, rows, n.value, None), "fcp_plan_table_rows")
+        return tuple(int(rows[t]) for t in range(n.value))
+
+    def traffic_bind(self, counts, skipped=None) -> None:
+        """``fcp_plan_traffic_bind``: ``counts`` names, per device input, the count tensor (``tables.new_plan_counts``: one
+        cell per row of the unsharded table, on the plan's device) that ``traffic_count`` adds the table's reads to, or
+        ``None`` for a table that is not counted; ``skipped``: an int64 device tensor of one element that receives the ids
+        outside their column's vocab (the caller zeroes it), or ``None``.  ``counts=None``, or all entries ``None``,
+        unbinds.  The plan keeps the tensors alive until the next bind.  Copies to the device and may synchronise it."""
+        import torch
+        from . import tables as _tables
+        if counts is None:
+            _lib.check(self._L.fcp_plan_traffic_bind(self.handle, None, 0, None), "fcp_plan_traffic_bind")
+            self._traffic_keep = None
+            return
+        rows = self.table_rows()
+        if len(counts) != len(rows):
+            raise ValueError(f"counts names {len(counts)} inputs, the plan has {len(rows)} device inputs")
+        for t, c in enumerate(counts):
+            if c is None:
+                continue
+            if _tables._check_counts(torch, c, f"counts[{t}]") != rows[t]:
+                raise ValueError(f"counts[{t}] has {c.shape[0]} cells, the plan's table {t} has {rows[t]} rows (Plan.table_rows)")
+        for t, c in enumerate(counts):          # (behind what can be seen of the tensors wherever they live)
+            if c is None:
+                continue
+            if not c.is_cuda or (c.device.index or 0) != self.device:
+                raise ValueError(f"counts[{t}] is on {c.device}, the plan on cuda:{self.device}")
+        if skipped is not None:
+            if skipped.dtype != torch.int64 or skipped.numel() != 1 or not skipped.is_cuda or (skipped.device.index or 0) != self.device:
+                raise ValueError("skipped is an int64 tensor of one element on the plan's device")
+        ptrs = (C.c_void_p * max(1, len(counts)))(*[None if c is None else c.data_ptr() for c in counts])
+        _lib.check(self._L.fcp_plan_traffic_bind(self.handle, ptrs, len(counts), None if skipped is None else C.c_void_p(skipped.data_ptr())),
+                   "fcp_plan_traffic_bind")
+        self._traffic_keep = (list(counts), skipped)
+
+    def traffic_count(self, concated_inputs, concated_offsets, concated_shapes, symbols=None, stream: Optional[int] = None) -> None:
+        """``fcp_plan_traffic_count``: add the table rows this request reads — the request as ``FeatureColumnProcess`` takes
+        it: the device blob, its host offsets and shapes, the symbols — to the bound count tensors, through the plan's own id
+        path (bucketize, hash, select / filter, the vocab check), in one launch.  No tables, no arena.  Asynchronous on
+        ``stream`` (torch's current stream of the plan's device by default)."""
+        import torch
+        offs = np.ascontiguousarray(concated_offsets, np.int32)
+        shps = np.ascontiguousarray(concated_shapes, np.int32)
+        sym = None if symbols is None else np.ascontiguousarray(symbols, np.int32)
+        if stream is None:
+            stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+        a = _lib.ProcessArgs(
+            concated_inputs.data_ptr() if concated_inputs is not None and concated_inputs.numel() else None,
+            0 if concated_inputs is None else concated_inputs.numel() * concated_inputs.element_size(),
+            offs.ctypes.data_as(C.POINTER(C.c_int32)), shps.ctypes.data_as(C.POINTER(C.c_int32)), None, None,
+            None if sym is None else sym.ctypes.data_as(C.POINTER(C.c_int32)), stream)
+        _lib.check(self._L.fcp_plan_traffic_count(self.handle, C.byref(a)), "fcp_plan_traffic_count")
+
     def table_bytes(self):
         """``fcp_plan_table_bytes``: (bytes of tables this plan reads on its device, largest table unsharded)."""
         a, b = C.c_int64(), C.c_int64()
@@ -569,6 +629,20 @@ class FeatureColumnProcess:
                 off = ((_grp_ptrs[gi] or arena.data_ptr()) - arena.data_ptr()) // f.element_size()
                 groups.append(f[off:off + rows * width].view(rows, width))
         return ProcessOutputs(out_ptrs, out_shapes, strides, arena, groups, gshapes)
+
+    def table_rows(self) -> tuple:
+        """``Plan.table_rows``."""
+        return self.plan.table_rows()
+
+    def traffic_bind(self, counts, skipped=None) -> None:
+        """``Plan.traffic_bind``."""
+        self.plan.traffic_bind(counts, skipped)
+
+    def traffic_count(self, concated_inputs, concated_offsets, concated_shapes, inputs=None, symbols=None,
+                      stream: Optional[int] = None) -> None:
+        """``Plan.traffic_count`` with the arguments of ``__call__``: a sampled request is counted with the very arguments it
+        is served with.  ``inputs`` (the tables) is accepted and not looked at."""
+        self.plan.traffic_count(concated_inputs, concated_offsets, concated_shapes, symbols, stream)
 
     def shard_finalize(self, concated_inputs, concated_offsets, concated_shapes, inputs, symbols, group: int,
                        partial_slices, world: int, row_begin: int, row_count: int, stream: Optional[int] = None, out=None):

@@ -4,7 +4,8 @@ table written and read back by id (``fcp_table_update_rows`` / ``fcp_table_read_
 and, in front of both, the audit of a float32 table against all three formats in one pass (``fcp_table_audit``,
 recom_amd/csrc/fcp_table_audit.hip) with the choice of one format per table from a byte budget (``fcp_table_formats_choose``);
 and the rows' read counts, taken from request ids on the device (``fcp_table_count_ids``, recom_amd/csrc/fcp_table_traffic.hip),
-by which the audit weighs its sums (``fcp_table_audit_weighted``).
+by which the audit weighs its sums (``fcp_table_audit_weighted``); ``new_plan_counts`` makes the count tensors of a whole plan,
+which ``Plan.traffic_bind`` / ``Plan.traffic_count`` (recom_amd/ops.py) fill from requests through the plan's own id path.
 
 Plans do not quantise; this does, once, at load time.  The value model is the header's (include/fcp_hip.h): float32 -> q8 is
 exactly the tensor ``quantized::embedding_bag_byte_prepack`` returns, q8 -> float32 is ``fma(code, scale, bias)`` rounded
@@ -268,6 +269,21 @@ def new_counts(rows: int, device):
     where the installed torch has that dtype, else int32 whose bits are read as uint32 (both are accepted wherever counts are)."""
     import torch
     return torch.zeros((int(rows),), dtype=_counts_dtypes(torch)[0], device=device)
+
+
+def new_plan_counts(plan_or_spec, device) -> list:
+    """One zeroed ``new_counts`` per device input of a plan (an ``ops.Plan``, an op that holds one, or a ``PlanSpec``) — as many
+    cells as the unsharded table has rows, the largest ``vocab`` of the lookup columns that read the input — and ``None`` for
+    the inputs no lookup column reads: what ``Plan.traffic_bind`` takes, and, once ``Plan.traffic_count`` has filled it, what
+    ``audit_tables(spec, tables, row_counts=...)`` takes."""
+    if hasattr(plan_or_spec, "table_rows"):
+        rows = plan_or_spec.table_rows()
+    else:
+        rows = [-1] * plan_or_spec.n_device_inputs
+        for c in plan_or_spec.columns:
+            if c.form in _FORMS_WITH_TABLES:
+                rows[c.table_input] = max(rows[c.table_input], int(c.vocab))
+    return [None if r < 0 else new_counts(r, device) for r in rows]
 
 
 def count_ids(counts, ids, skipped=None, stream: Optional[int] = None):
