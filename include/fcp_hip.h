@@ -690,6 +690,80 @@ int fcp_plan_traffic_count(fcp_plan_t *plan, const fcp_process_args_t *args);
 int fcp_table_formats_choose(const fcp_table_audit_t *audits, const int64_t *rows, const int32_t *dims, int32_t n_tables,
                              int64_t budget_bytes, uint32_t allowed_kinds, const double *table_weight, int32_t *kinds_out,
                              int64_t *bytes_out, double *error_out);
+/* ---- table digest: is this table, byte for byte, the table I think it is? ------------------------------------------------------
+ * fcp_table_convert, fcp_table_update_rows and a loader that streams a checkpoint through a bounce buffer all promise BYTES.
+ * These entries let a deployment check the promise on the table it serves: an order-free 64-bit sum of row hashes, computed
+ * where the table lies, at memory speed, for a table of any row format (FCP_TAB_F32 / _BF16 / _F16 / _Q8).
+ *
+ * Value model (fixed; all arithmetic unsigned, modulo 2^64).  G = 0x9e3779b97f4a7c15.  mix(x) is the 64-bit finaliser
+ *   x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33      (mix(1) == 0xb456bcfc34c2cb2c).
+ * With rb = fcp_table_row_bytes(kind, dim): a row is its rb bytes as stored, taken as nw = ceil(rb / 8) little-endian 64-bit words
+ * w[0 .. nw), the last one zero-padded; salt = mix(((uint64)(kind + 1) << 32) | (uint32)dim); the hash of the row with GLOBAL
+ * index r is
+ *   H(r) = mix(salt + (r + 1) * G + sum over j of mix(w[j] ^ ((j + 1) * G)))
+ * and the digest of a set of rows is the sum of their H.  Local row i of the rows handed over has global index
+ * row0 + i * row_step.  So the digest depends on every byte and on where it lies (which word, which row, which kind and dim),
+ * and on nothing else: no order of summation, grid shape or chunking can change it.  Consequences:
+ *   sharding   rank g of a table row-sharded id % world (local row id / world) passes row0 = g, row_step = world: the ranks'
+ *              digests add up to the digest of the unsharded table;
+ *   chunking   a checkpoint digested chunk by chunk (row0 = the chunk's first row) adds up to the digest of the whole table;
+ *   deltas     new digest = old digest - (digest of the touched rows before) + (digest of the same rows after): a digest is
+ *              maintained across fcp_table_update_rows from the touched rows alone (fcp_table_digest_rows).
+ * The digest detects ACCIDENTS: a changed byte, swapped rows, swapped words, a row at the wrong index, the same bytes read as
+ * another kind or dim.  It is NOT a MAC and no cryptographic hash: whoever can choose the bytes can choose the sum.
+ *
+ * fcp_table_digest: the digest of `rows` rows that lie back to back from `first_row` — the table's base or ANY row of it, so
+ * that a range of rows or one chunk of a bounce buffer can be digested.  `first_row`, `out` and `workspace` are on the device;
+ * `workspace` holds fcp_table_digest_workspace_bytes bytes (a constant) and its content before and after the call means
+ * nothing.  Device to device on `device`, asynchronous on `stream` (a hipStream_t), no allocation, no synchronisation; no
+ * atomic operation, and two calls on the same input leave the same bytes.  Once the stream has run, `out` is
+ * {sum, rows, 0, 0}; rows == 0 gives zeros.  The table is only read, and no load touches a byte outside
+ * [first_row, first_row + rows * rb): the partial last word of a row is read with loads that stay inside the row.
+ * Alignment: `first_row` that of a row of the kind — 4 * V bytes for float32, 2 * V for bf16 / fp16, V the largest of 4 | 2 | 1
+ * that divides dim; ANY byte address for q8, whose rows of dim + 8 bytes start anywhere; `out` and `workspace` 8 bytes.  rows
+ * stays below 2^32 - 3, the row limit of a plan's table, and a row below 2 GiB.
+ *
+ * Status, decided in this order (the first needs no device):
+ *   FCP_ERR_INVALID_ARGUMENT  rows < 0 or beyond the row limit; dim <= 0; a kind that is no FCP_TAB_* row format; row0 < 0;
+ *                             row_step < 1; row0 + (rows - 1) * row_step overflowing int64; a null out or workspace; a null
+ *                             first_row with rows > 0; a misaligned first_row, out or workspace (in this order);
+ *                             fcp_last_error names the argument between backquotes;
+ *   FCP_ERR_NO_DEVICE         no usable gfx950 device (rows == 0 included: `out` is written on the device);
+ *   FCP_ERR_HIP               a kernel launch failed.
+ * No combination of valid arguments is FCP_ERR_UNSUPPORTED. */
+typedef struct fcp_table_digest {
+  uint64_t sum;     /* the digest: sum of H over the rows, modulo 2^64 */
+  int64_t rows;     /* rows that were summed */
+  int64_t skipped;  /* fcp_table_digest_rows: ids outside [0, table_rows); else 0 */
+  int64_t reserved; /* 0 */
+} fcp_table_digest_t; /* 32 bytes */
+int64_t fcp_table_digest_workspace_bytes(void);
+int fcp_table_digest(const void *first_row, int32_t kind, int64_t rows, int32_t dim, int64_t row0, int64_t row_step,
+                     fcp_table_digest_t *out, void *workspace, int32_t device, void *stream);
+/* fcp_table_digest_rows: the same sum over the rows `row_ids` names — int64 [n] on the device — of a table [table_rows, dim]
+ * whose BASE is `table`.  An id in [0, table_rows) adds H(row0 + id * row_step) of that row and counts in out->rows; any other
+ * id — the whole 64-bit value is compared, as fcp_table_update_rows compares ids — touches no memory, adds nothing and counts
+ * in out->skipped.  An id is summed as often as it occurs.  Delta bookkeeping (digest - before + after around
+ * fcp_table_update_rows) therefore needs the ids of one call pairwise distinct, as fcp_table_update_rows itself does; this is
+ * NOT checked.  The sum over the ids 0 .. table_rows - 1 is fcp_table_digest of the table.  Workspace, asynchrony and
+ * alignment are those of fcp_table_digest (`table` as first_row; `row_ids` 8 bytes); table_rows lies in [0, 2^32 - 3) and
+ * n < 2^32 - 3.
+ *
+ * Status, decided in this order (the first needs no device):
+ *   FCP_ERR_INVALID_ARGUMENT  n < 0 or beyond its limit; table_rows outside its range; dim <= 0; a kind that is no FCP_TAB_*
+ *                             row format; row0 < 0; row_step < 1; row0 + (table_rows - 1) * row_step overflowing int64; a
+ *                             null out or workspace; a null table with n > 0 and table_rows > 0; a null row_ids with n > 0; a
+ *                             misaligned table, row_ids, out or workspace (in this order); fcp_last_error names the argument
+ *                             between backquotes;
+ *   FCP_ERR_NO_DEVICE         no usable gfx950 device (n == 0 included: `out` is written on the device);
+ *   FCP_ERR_HIP               a kernel launch failed.
+ * No combination of valid arguments is FCP_ERR_UNSUPPORTED. */
+int fcp_table_digest_rows(const void *table, int32_t kind, int64_t table_rows, int32_t dim, int64_t row0, int64_t row_step,
+                          const int64_t *row_ids, int64_t n, fcp_table_digest_t *out, void *workspace, int32_t device, void *stream);
+/* fcp_table_digest_host: the same value from HOST memory — a checkpoint before it is loaded, a table copied back.  Host only:
+ * it never touches a device.  Rows may start at any byte.  Returns 0 for invalid arguments (those of fcp_table_digest without
+ * out and workspace), which is also the digest of no rows. */
+uint64_t fcp_table_digest_host(const void *first_row, int32_t kind, int64_t rows, int32_t dim, int64_t row0, int64_t row_step);
 /* ---- placement gate (replaces check_table_size, cuda_emitter.cc:1080-1094) -------- */
 /* The reference keeps a column on the CPU when its table exceeds max_table_size =
  * 256 MiB (fc_optimize_pass.cc:71, RECOM_CPU_GPU_CO_RUN).  On MI355X the question is

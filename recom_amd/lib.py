@@ -136,6 +136,11 @@ class TableAudit(C.Structure):
                 ("kind", TableAuditKind * 4)]
 
 
+class TableDigest(C.Structure):
+    """fcp_table_digest_t"""
+    _fields_ = [("sum", C.c_uint64), ("rows", C.c_int64), ("skipped", C.c_int64), ("reserved", C.c_int64)]
+
+
 class PrivateStreamsStats(C.Structure):
     """fcp_private_streams_stats_t"""
     _fields_ = [("supervised_stream", C.c_void_p), ("requests", C.c_int64), ("lane_requests", C.c_int64), ("evaluations", C.c_int64),
@@ -186,6 +191,7 @@ EXPORTS = [
     "fcp_table_audit_workspace_bytes", "fcp_table_audit", "fcp_table_formats_choose",
     "fcp_table_audit_weighted", "fcp_table_count_ids",
     "fcp_plan_table_rows", "fcp_plan_traffic_bind", "fcp_plan_traffic_count",
+    "fcp_table_digest_workspace_bytes", "fcp_table_digest", "fcp_table_digest_rows", "fcp_table_digest_host",
 ]
 
 _lib = None
@@ -359,6 +365,15 @@ def load() -> C.CDLL:
         L.fcp_plan_table_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]
         L.fcp_plan_traffic_bind.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]
         L.fcp_plan_traffic_count.argtypes = [C.c_void_p, C.POINTER(ProcessArgs)]
+    if hasattr(L, "fcp_table_digest"):
+        L.fcp_table_digest_workspace_bytes.restype = C.c_int64
+        L.fcp_table_digest_workspace_bytes.argtypes = []
+        L.fcp_table_digest.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                       C.c_int32, C.c_void_p]
+        L.fcp_table_digest_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                            C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.fcp_table_digest_host.restype = C.c_uint64
+        L.fcp_table_digest_host.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int64]
     if L.fcp_abi_version() != FCP_ABI_VERSION:
         raise ImportError("libfcp_hip.so ABI version mismatch; rebuild")
     _lib = L

@@ -5,7 +5,10 @@ and, in front of both, the audit of a float32 table against all three formats in
 recom_amd/csrc/fcp_table_audit.hip) with the choice of one format per table from a byte budget (``fcp_table_formats_choose``);
 and the rows' read counts, taken from request ids on the device (``fcp_table_count_ids``, recom_amd/csrc/fcp_table_traffic.hip),
 by which the audit weighs its sums (``fcp_table_audit_weighted``); ``new_plan_counts`` makes the count tensors of a whole plan,
-which ``Plan.traffic_bind`` / ``Plan.traffic_count`` (recom_amd/ops.py) fill from requests through the plan's own id path.
+which ``Plan.traffic_bind`` / ``Plan.traffic_count`` (recom_amd/ops.py) fill from requests through the plan's own id path;
+and the digest of a table of any format — an order-free 64-bit sum of row hashes, on the device (``fcp_table_digest`` /
+``fcp_table_digest_rows``, recom_amd/csrc/fcp_table_digest.hip) and from host memory (``fcp_table_digest_host``) — by which a
+deployment checks that a served table is, byte for byte, the table it should be, and keeps that check across ``update_rows``.
 
 Plans do not quantise; this does, once, at load time.  The value model is the header's (include/fcp_hip.h): float32 -> q8 is
 exactly the tensor ``quantized::embedding_bag_byte_prepack`` returns, q8 -> float32 is ``fma(code, scale, bias)`` rounded
@@ -394,3 +397,133 @@ def choose_dtypes(spec: PlanSpec, audits: Sequence, budget_bytes: int, allowed: 
     for i, t in enumerate(read):
         names[t] = _lib.ALL_TABLE_DTYPES[kinds[i]]
     return tuple(names), int(nbytes.value), float(error.value)
+
+
+# ---- digest (fcp_table_digest / fcp_table_digest_rows / fcp_table_digest_host) -------------------------------------------------
+def _digest_buffers(torch, L, device, stream: int, n_out: int = 1):
+    """``n_out`` result records and one workspace (calls on one stream run one after the other and may share it), allocated as
+    that stream's: a block the caching allocator hands out may still have work pending on the stream it was freed on"""
+    words = C.sizeof(_lib.TableDigest) // 8
+    with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device)):
+        outs = torch.empty((n_out, words), dtype=torch.int64, device=device)
+        workspace = torch.empty((int(L.fcp_table_digest_workspace_bytes()) // 8,), dtype=torch.int64, device=device)
+    return outs, workspace
+
+
+def _digests_of(outs) -> list:
+    size = C.sizeof(_lib.TableDigest)
+    raw = outs.cpu().numpy().tobytes()
+    return [_lib.TableDigest.from_buffer_copy(raw[k * size:(k + 1) * size]) for k in range(outs.shape[0])]
+
+
+def _enqueue_digest_rows(L, table, name: str, dim: int, row_ids, n: int, row0: int, row_step: int, out_ptr: int, workspace, stream: int):
+    status = L.fcp_table_digest_rows(C.c_void_p(table.data_ptr()), _lib.TABLE_KINDS[name], int(table.shape[0]), dim, int(row0),
+                                     int(row_step), C.c_void_p(row_ids.data_ptr()), n, C.c_void_p(out_ptr),
+                                     C.c_void_p(workspace.data_ptr()), table.device.index or 0, C.c_void_p(stream))
+    _lib.check(status, "fcp_table_digest_rows")
+
+
+def digest(table, row0: int = 0, row_step: int = 1, stream: Optional[int] = None) -> int:
+    """``fcp_table_digest``: the order-free 64-bit sum of row hashes of ``table`` — a device tensor in one of the four table
+    formats, or a row range of one (``table[a:b]``, with ``row0=a``): local row ``i`` has the global index
+    ``row0 + i * row_step``.  Chunks add up to the whole table, and the shards of a table row-sharded ``id % world`` — rank
+    ``g`` passes ``row0=g, row_step=world`` — add up to the unsharded table, both modulo 2^64.  Detects accidents; not a MAC.
+    Allocates the result and the workspace, runs on ``stream`` (torch's current stream of the device by default), synchronises
+    it, and returns the sum."""
+    import torch
+    name, dim = _kind_and_dim(table, "table")
+    L = _lib.load()
+    if stream is None:
+        stream = torch.cuda.current_stream(table.device).cuda_stream
+    outs, workspace = _digest_buffers(torch, L, table.device, stream)
+    status = L.fcp_table_digest(C.c_void_p(table.data_ptr()), _lib.TABLE_KINDS[name], int(table.shape[0]), dim, int(row0), int(row_step),
+                                C.c_void_p(outs.data_ptr()), C.c_void_p(workspace.data_ptr()), table.device.index or 0,
+                                C.c_void_p(stream))
+    _lib.check(status, "fcp_table_digest")
+    torch.cuda.ExternalStream(stream, device=table.device).synchronize()
+    return int(_digests_of(outs)[0].sum)
+
+
+def digest_rows(table, row_ids, row0: int = 0, row_step: int = 1, stream: Optional[int] = None):
+    """``fcp_table_digest_rows``: the same sum over the rows ``row_ids`` (int64 ``[n]`` on the table's device) names of the WHOLE
+    table ``table``: an id inside the table adds the hash of that row at global index ``row0 + id * row_step``, as often as it
+    occurs; any other id adds nothing.  Synchronises ``stream`` and returns ``(sum, rows, skipped)``."""
+    import torch
+    name, dim = _kind_and_dim(table, "table")
+    n = _ids_of(torch, table, row_ids)
+    L = _lib.load()
+    if stream is None:
+        stream = torch.cuda.current_stream(table.device).cuda_stream
+    outs, workspace = _digest_buffers(torch, L, table.device, stream)
+    _enqueue_digest_rows(L, table, name, dim, row_ids, n, row0, row_step, outs.data_ptr(), workspace, stream)
+    torch.cuda.ExternalStream(stream, device=table.device).synchronize()
+    d = _digests_of(outs)[0]
+    return int(d.sum), int(d.rows), int(d.skipped)
+
+
+def digest_host(array, dtype: str, dim: Optional[int] = None, row0: int = 0, row_step: int = 1) -> int:
+    """``fcp_table_digest_host``: the digest of table rows in HOST memory — a NumPy array or a torch CPU tensor that holds rows
+    of a ``dtype`` ("f32" | "bf16" | "f16" | "q8") table back to back; its own element type plays no part, only its bytes do
+    (NumPy has no bfloat16: hand over uint16 or uint8).  ``dim``: the table's width; by default that of a 2-D array whose
+    rows are the table's.  No device is touched."""
+    import numpy as np
+    if dtype not in _lib.TABLE_KINDS:
+        raise ValueError(f"unknown table dtype {dtype!r}")
+    if hasattr(array, "is_cuda"):
+        import torch
+        if array.is_cuda:
+            raise ValueError("digest_host takes host memory; tables.digest works on the device")
+        shape, item = tuple(array.shape), array.element_size()
+        array = array.contiguous().reshape(-1).view(torch.uint8).numpy()        # (bytes: NumPy has no bfloat16)
+        if len(shape) == 2:
+            array = array.reshape(shape[0], shape[1] * item)
+    else:
+        array = np.ascontiguousarray(array)
+    fmt = TABLE_FORMATS[dtype]
+    if dim is None:
+        if array.ndim != 2:
+            raise ValueError("digest_host needs dim= for anything but a 2-D array whose rows are the table's")
+        dim, odd = divmod(array.shape[1] * array.itemsize - fmt.row_tail, fmt.elem)
+        if odd or dim <= 0:
+            raise ValueError(f"rows of {array.shape[1] * array.itemsize} bytes are no rows of a {dtype} table")
+    if dim <= 0:
+        raise ValueError("dim must be positive")
+    rb = fmt.row_bytes(int(dim))
+    if array.nbytes % rb:
+        raise ValueError(f"{array.nbytes} bytes are no whole number of {dtype} rows of dim {dim} ({rb} bytes each)")
+    if row0 < 0 or row_step < 1:
+        raise ValueError("row0 must not be negative and row_step must be at least 1")
+    raw = array.reshape(-1).view(np.uint8)
+    return int(_lib.load().fcp_table_digest_host(C.c_void_p(raw.ctypes.data), _lib.TABLE_KINDS[dtype], raw.size // rb, int(dim),
+                                                 int(row0), int(row_step)))
+
+
+def digest_tables(spec: PlanSpec, tables: Sequence, stream: Optional[int] = None) -> list:
+    """One ``digest`` per device input of ``spec`` that a lookup column reads (a shared table once), ``None`` for the others.
+    The tables are the rank's own — any format — and ``row0 = spec.shard_rank, row_step = spec.shard_world``: the lists of the
+    ranks of a row-sharded plan add up, entry by entry modulo 2^64, to the unsharded plan's."""
+    read = set(spec.read_inputs())
+    return [digest(t, row0=spec.shard_rank, row_step=spec.shard_world, stream=stream) if i in read else None
+            for i, t in enumerate(tables)]
+
+
+def update_rows_tracked(table, row_ids, rows, digest: int, row0: int = 0, row_step: int = 1, skipped=None,
+                        stream: Optional[int] = None) -> int:
+    """``update_rows`` with the table's digest kept up to date from the touched rows alone: ``digest_rows`` of ``row_ids``
+    before, the update, ``digest_rows`` after — all on ``stream``, one synchronise at the end — and
+    ``(digest - before + after) mod 2^64`` is returned: the ``digest`` of the updated table when ``digest`` was that of the
+    table before and the ids are pairwise distinct (``update_rows`` asks the same; not checked)."""
+    import torch
+    name, dim = _kind_and_dim(table, "table")
+    n = _ids_of(torch, table, row_ids)
+    L = _lib.load()
+    if stream is None:
+        stream = torch.cuda.current_stream(table.device).cuda_stream
+    outs, workspace = _digest_buffers(torch, L, table.device, stream, n_out=2)
+    size = C.sizeof(_lib.TableDigest)
+    _enqueue_digest_rows(L, table, name, dim, row_ids, n, row0, row_step, outs.data_ptr(), workspace, stream)
+    update_rows(table, row_ids, rows, skipped=skipped, stream=stream)
+    _enqueue_digest_rows(L, table, name, dim, row_ids, n, row0, row_step, outs.data_ptr() + size, workspace, stream)
+    torch.cuda.ExternalStream(stream, device=table.device).synchronize()
+    before, after = _digests_of(outs)
+    return (int(digest) - int(before.sum) + int(after.sum)) % (1 << 64)
