@@ -3,7 +3,7 @@
 // this does.  The reference reads float32 tables only and has no counterpart.
 //
 // Four directions, one of the two kinds always float32:
-//   float32 -> q8     fcp_quantize_q8_kernel<V, G>: the real kernel.  Bit for bit what quantized::embedding_bag_byte_prepack
+//   float32 -> q8     fcp_quantize_q8_kernel<V, G>: the real kernel (quantize_row of fcp_table_walk.h per row).  Bit for bit what quantized::embedding_bag_byte_prepack
 //                     writes (fcp_hip.h spells the arithmetic out).  A row is handled by a power-of-two group of G <= 64
 //                     lanes, every lane owning V-element slots (V = 4 | 2 | 1, as on the read side): dim 64 is 16 lanes x
 //                     global_load_dwordx4 and four rows per wave, dims <= 4 are one row per lane.  The row stays in registers
@@ -35,55 +35,9 @@ namespace {
 // wave, and it is live or not as a whole — lanes of rows beyond the end take part in the butterflies and touch no memory.
 template <int V, int G>
 __global__ void __launch_bounds__(FCP_BLOCK_THREADS) fcp_quantize_q8_kernel(char *dst, const float *src, int32_t rows, int32_t dim) {
-  constexpr int S = slots_in_registers<G>();
   const int tid = threadIdx.x;
-  const int lane = tid & (G - 1);
   const int64_t row = (int64_t)blockIdx.x * (FCP_BLOCK_THREADS / G) + tid / G;
-  const bool live = row < rows;
-  const int nslots = dim / V;
-  const float *srow = src + row * dim;
-  char *drow = dst + row * ((int64_t)dim + 8);
-
-  VF<V> x[S];
-  float mn = __builtin_inff(), mx = -__builtin_inff();
-#pragma unroll
-  for (int k = 0; k < S; ++k) {
-    x[k] = vzero<V>();
-    const int slot = lane + k * G;
-    if (live && slot < nslots) {
-      x[k] = ld_f32<V>(srow + (int64_t)slot * V);
-      minmax<V>(x[k], mn, mx);
-    }
-  }
-  if constexpr (G == 64) {
-    if (live)
-      for (int slot = lane + S * G; slot < nslots; slot += G) {
-        const VF<V> t = ld_f32<V>(srow + (int64_t)slot * V);
-        minmax<V>(t, mn, mx);
-      }
-  }
-#pragma unroll
-  for (int m = G / 2; m >= 1; m >>= 1) {
-    mn = fminf(mn, __shfl_xor(mn, m, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, m, 64));
-  }
-  const float range = mx - mn;
-  const float scale = range / 255.0f;
-  const float inv = 255.0f / (range + 1e-8f);
-  if (!live) return;
-#pragma unroll
-  for (int k = 0; k < S; ++k) {
-    const int slot = lane + k * G;
-    if (slot < nslots) st_codes<V>(drow + (int64_t)slot * V, x[k], mn, inv);
-  }
-  if constexpr (G == 64) {
-    for (int slot = lane + S * G; slot < nslots; slot += G) // beyond the register cap: the row's tail is read again
-      st_codes<V>(drow + (int64_t)slot * V, ld_f32<V>(srow + (int64_t)slot * V), mn, inv);
-  }
-  if (lane == 0) {
-    const uint64_t pair = (uint64_t)__float_as_uint(scale) | ((uint64_t)__float_as_uint(mn) << 32);
-    *(FCP_GLOBAL typename Q8Pair<V>::T *)(drow + dim) = pair;
-  }
+  quantize_row<V, G>(dst + row * ((int64_t)dim + 8), src + row * dim, dim, tid & (G - 1), row < rows);
 }
 
 // n: slots of this launch (<= 2^30); src: the first row, its stride dim + 8 bytes; spr: slots per row, dim / V
@@ -113,26 +67,17 @@ __global__ void __launch_bounds__(FCP_BLOCK_THREADS) fcp_widen16_kernel(float *d
   st_f32<V>(dst + (uint64_t)i * V, widen16<V>(t, kind));
 }
 
-template <int V, int G> void quantize_rows(char *dst, const float *src, int64_t rows, int dim, hipStream_t s) {
-  const int64_t per_launch = kMaxLaunchThreads / G;
-  for (int64_t r0 = 0; r0 < rows; r0 += per_launch) {
-    const int64_t n = std::min(rows - r0, per_launch);
-    hipLaunchKernelGGL((fcp_quantize_q8_kernel<V, G>), blocks_for(n * G), dim3(FCP_BLOCK_THREADS), 0, s,
-                       dst + r0 * ((int64_t)dim + 8), src + r0 * dim, (int32_t)n, (int32_t)dim);
-  }
-}
-
 // G: 1 for dims <= 4, else the power of two that holds the row's slots, at most 64
 template <int V> void quantize(char *dst, const float *src, int64_t rows, int dim, hipStream_t s) {
-  switch (group_of(dim, V)) {
-  case 1: quantize_rows<V, 1>(dst, src, rows, dim, s); break;
-  case 2: quantize_rows<V, 2>(dst, src, rows, dim, s); break;
-  case 4: quantize_rows<V, 4>(dst, src, rows, dim, s); break;
-  case 8: quantize_rows<V, 8>(dst, src, rows, dim, s); break;
-  case 16: quantize_rows<V, 16>(dst, src, rows, dim, s); break;
-  case 32: quantize_rows<V, 32>(dst, src, rows, dim, s); break;
-  default: quantize_rows<V, 64>(dst, src, rows, dim, s); break;
-  }
+  with_group(group_of(dim, V), [&](auto g) {
+    constexpr int G = decltype(g)::value;
+    const int64_t per_launch = kMaxLaunchThreads / G;
+    for (int64_t r0 = 0; r0 < rows; r0 += per_launch) {
+      const int64_t n = std::min(rows - r0, per_launch);
+      hipLaunchKernelGGL((fcp_quantize_q8_kernel<V, G>), blocks_for(n * G), dim3(FCP_BLOCK_THREADS), 0, s,
+                         dst + r0 * ((int64_t)dim + 8), src + r0 * dim, (int32_t)n, (int32_t)dim);
+    }
+  });
 }
 
 template <int V> void dequantize(float *dst, const char *src, int64_t rows, int dim, hipStream_t s) {
@@ -182,7 +127,7 @@ extern "C" int fcp_table_convert(void *dst, int32_t dst_kind, int64_t dst_row0, 
   if (!fcpf::known_tab_kind(src_kind)) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: src_kind is no FCP_TAB_* value");
   if (rows > 0 && !dst) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: dst is null");
   if (rows > 0 && !src) return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: src is null");
-  if (rows + dst_row0 >= (1ll << 32) - 3 || rows >= (1ll << 32) - 3)
+  if (rows + dst_row0 >= fcpf::kRowLimit || rows >= fcpf::kRowLimit)
     return fail(FCP_ERR_INVALID_ARGUMENT, "fcp_table_convert: dst_row0 + rows must stay below 2^32 - 3, a plan's row limit");
   const int vec = vec_of(dim);
   if ((uintptr_t)dst % fcpf::base_alignment(dst_kind, vec))
@@ -197,18 +142,8 @@ extern "C" int fcp_table_convert(void *dst, int32_t dst_kind, int64_t dst_row0, 
     return fail(FCP_ERR_UNSUPPORTED, std::string("fcp_table_convert: ") + kind_name(src_kind) + " -> " + kind_name(dst_kind) +
                                          " is not implemented; convert through float32");
   if (rows == 0) return FCP_OK;
-  DeviceGuard guard;
-  const int rc = guard.enter(device);
-  if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   void *first = static_cast<char *>(dst) + dst_row0 * fcp_table_row_bytes(dst_kind, dim);
-  if (vec == 4)
-    convert<4>(first, dst_kind, src, src_kind, rows, dim, s);
-  else if (vec == 2)
-    convert<2>(first, dst_kind, src, src_kind, rows, dim, s);
-  else
-    convert<1>(first, dst_kind, src, src_kind, rows, dim, s);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail("fcp_table_convert: kernel launch", e);
-  return FCP_OK;
+  return on_device("fcp_table_convert", device, stream, [&](hipStream_t s) {
+    with_vec(vec, [&](auto v) { convert<decltype(v)::value>(first, dst_kind, src, src_kind, rows, dim, s); });
+  });
 }

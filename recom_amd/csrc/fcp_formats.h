@@ -19,6 +19,7 @@ constexpr Format kTab[kTabKinds] = {{"f32", 0, 4, 0}, {"bf16", FCP_FLAG_TABLES_B
 constexpr Format kOut[kOutKinds] = {{"f32", 0, 4, 0}, {"bf16", FCP_FLAG_OUT_BF16, 2, 0}, {"f16", FCP_FLAG_OUT_F16, 2, 0}};
 static_assert(FCP_TAB_F32 == 0 && FCP_TAB_BF16 == 1 && FCP_TAB_F16 == 2 && FCP_TAB_Q8 == 3 && FCP_OUT_F32 == 0 && FCP_OUT_BF16 == 1 && FCP_OUT_F16 == 2,
               "kTab is indexed by FCP_TAB_*, kOut by FCP_OUT_*");
+constexpr int64_t kRowLimit = (1ll << 32) - 3; // a plan's row limit: the rows of a table, and of one call of a table entry, stay below it
 constexpr uint32_t kTabFlags = FCP_FLAG_TABLES_BF16 | FCP_FLAG_TABLES_F16 | FCP_FLAG_TABLES_Q8, kOutFlags = FCP_FLAG_OUT_BF16 | FCP_FLAG_OUT_F16;
 
 inline bool known_tab_kind(int kind) { return kind >= 0 && kind < kTabKinds; } // (FCP_TAB_MIXED is no row format)

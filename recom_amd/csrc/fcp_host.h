@@ -389,6 +389,17 @@ struct DeviceGuard {
   }
 };
 
+// What the table entries do behind their argument checks: enter the device, enqueue(stream) — launches only — and report a
+// failed launch as "<who>: kernel launch".
+template <class F> int on_device(const char *who, int32_t device, void *stream, F enqueue) {
+  DeviceGuard guard;
+  const int rc = guard.enter(device);
+  if (rc) return rc;
+  enqueue(static_cast<hipStream_t>(stream));
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? FCP_OK : hip_fail((std::string(who) + ": kernel launch").c_str(), e);
+}
+
 // ---- functions that cross translation units -----------------------------------------------------------------------
 // fcp_plan.hip
 int compute_dyn(const fcp_plan *p, const int32_t *offsets, const int32_t *shapes, const int32_t *symbols, int64_t blob_bytes,

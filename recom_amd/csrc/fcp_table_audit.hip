@@ -3,10 +3,11 @@
 // cannot hold at all, judged on the device in ONE pass over the source — before fcp_table_convert or fcp_table_update_rows
 // writes a single byte.  The reference reads float32 tables only and has no counterpart.
 //
-//   fcp_table_audit_kernel<V, G, WEIGHTED>   the row walk of fcp_quantize_q8_kernel<V, G> (fcp_convert.hip; fcp_table_walk.h) — the same 3 V x 7 G
+//   fcp_table_audit_kernel<V, G, WEIGHTED>   walks a row through RowSlots<V, G> (fcp_table_walk.h), the walk quantize_row uses — so the same 3 V x 7 G
 //                     matrix, the same power-of-two group of G <= 64 lanes per row, loads of V = 4 | 2 | 1 elements, the row
 //                     kept in registers between the two passes (kQSlots slots per lane of a 64-lane group; what lies beyond
-//                     is read a second time, as the quantiser reads it).  Pass one: min, max and the largest |x| as a bit
+//                     is read a second time).  A lane meets its slots in the same order in both passes: increasing k, then
+//                     the tail in increasing slot.  Pass one (load): min, max and the largest |x| as a bit
 //                     pattern — it says whether an element is NaN or +-inf, whether one's bf16 image is +-inf, whether one's
 //                     fp16 image is —, joined over the group by __shfl_xor butterflies (order-free).  Pass two, per element x, all in
 //                     float32 with every operation rounded once:
@@ -174,7 +175,6 @@ __device__ __forceinline__ void wave_fold(AuditPartial &p) {
 template <int V, int G, bool WEIGHTED>
 __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
     fcp_table_audit_kernel(const float *src, int64_t rows, int32_t dim, AuditPartial *partials, const uint32_t *row_counts) {
-  constexpr int S = slots_in_registers<G>();
   constexpr int kRowsPerBlock = FCP_BLOCK_THREADS / G;
   const int tid = threadIdx.x;
   const int lane = tid & (G - 1);
@@ -187,22 +187,10 @@ __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
     double w = 1.0;
     if constexpr (WEIGHTED) w = live ? (double)*as_global(row_counts + row) : 0.0;
 
-    VF<V> x[S];
+    RowSlots<V, G> r;
     float mn = __builtin_inff(), mx = -__builtin_inff();
     uint32_t amax = 0;
-#pragma unroll
-    for (int k = 0; k < S; ++k) {
-      x[k] = vzero<V>();
-      const int slot = lane + k * G;
-      if (live && slot < nslots) {
-        x[k] = ld_f32<V>(srow + (int64_t)slot * V);
-        look<V>(x[k], mn, mx, amax);
-      }
-    }
-    if constexpr (G == 64) {
-      if (live)
-        for (int slot = lane + S * G; slot < nslots; slot += G) look<V>(ld_f32<V>(srow + (int64_t)slot * V), mn, mx, amax);
-    }
+    r.load(srow, nslots, lane, live, [&](const VF<V> &x) { look<V>(x, mn, mx, amax); });
 #pragma unroll
     for (int m = G / 2; m >= 1; m >>= 1) {
       mn = fminf(mn, __shfl_xor(mn, m, 64));
@@ -230,15 +218,7 @@ __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
           }
       }
       const uint32_t good = ~bad & 7u;
-#pragma unroll
-      for (int k = 0; k < S; ++k) {
-        const int slot = lane + k * G;
-        if (slot < nslots) judge<V, WEIGHTED>(x[k], good, mn, scale, inv, w, a);
-      }
-      if constexpr (G == 64) {
-        for (int slot = lane + S * G; slot < nslots; slot += G) // beyond the register cap: the row's tail is read again
-          judge<V, WEIGHTED>(ld_f32<V>(srow + (int64_t)slot * V), good, mn, scale, inv, w, a);
-      }
+      r.again(srow, nslots, lane, [&](int, const VF<V> &x) { judge<V, WEIGHTED>(x, good, mn, scale, inv, w, a); });
     }
   }
 
@@ -302,19 +282,6 @@ void audit_rows(const float *src, int64_t rows, int dim, int blocks, AuditPartia
                        row_counts);
 }
 
-template <int V>
-void audit(const float *src, int64_t rows, int dim, int g, int blocks, AuditPartial *partials, const uint32_t *row_counts, hipStream_t s) {
-  switch (g) {
-  case 1: audit_rows<V, 1>(src, rows, dim, blocks, partials, row_counts, s); break;
-  case 2: audit_rows<V, 2>(src, rows, dim, blocks, partials, row_counts, s); break;
-  case 4: audit_rows<V, 4>(src, rows, dim, blocks, partials, row_counts, s); break;
-  case 8: audit_rows<V, 8>(src, rows, dim, blocks, partials, row_counts, s); break;
-  case 16: audit_rows<V, 16>(src, rows, dim, blocks, partials, row_counts, s); break;
-  case 32: audit_rows<V, 32>(src, rows, dim, blocks, partials, row_counts, s); break;
-  default: audit_rows<V, 64>(src, rows, dim, blocks, partials, row_counts, s); break;
-  }
-}
-
 // Both entries: `who` names the entry in fcp_last_error; weighted: row_counts is an argument (checked, and handed to the kernels).
 int audit_entry(const char *who, const float *src, int64_t rows, int32_t dim, bool weighted, const uint32_t *row_counts,
                 fcp_table_audit_t *out, void *workspace, int32_t device, void *stream) {
@@ -325,34 +292,25 @@ int audit_entry(const char *who, const float *src, int64_t rows, int32_t dim, bo
   if (!workspace) return fail(FCP_ERR_INVALID_ARGUMENT, w + "workspace is null");
   if (rows > 0 && !src) return fail(FCP_ERR_INVALID_ARGUMENT, w + "src is null");
   if (weighted && rows > 0 && !row_counts) return fail(FCP_ERR_INVALID_ARGUMENT, w + "row_counts is null");
-  if (rows >= (1ll << 32) - 3) return fail(FCP_ERR_INVALID_ARGUMENT, w + "rows must stay below 2^32 - 3, a plan's row limit");
+  if (rows >= fcpf::kRowLimit) return fail(FCP_ERR_INVALID_ARGUMENT, w + "rows must stay below 2^32 - 3, a plan's row limit");
   const int vec = vec_of(dim);
   if ((uintptr_t)src % (4 * vec))
     return fail(FCP_ERR_INVALID_ARGUMENT, w + "src is not " + std::to_string(4 * vec) + "-byte aligned (a float32 table of this dim)");
   if (weighted && (uintptr_t)row_counts % 4) return fail(FCP_ERR_INVALID_ARGUMENT, w + "row_counts is not 4-byte aligned");
   if ((uintptr_t)out % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + "out is not 8-byte aligned");
   if ((uintptr_t)workspace % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + "workspace is not 8-byte aligned");
-  DeviceGuard guard;
-  const int rc = guard.enter(device);
-  if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   AuditPartial *partials = static_cast<AuditPartial *>(workspace);
   const int g = group_of(dim, vec);
   const int64_t rows_per_block = FCP_BLOCK_THREADS / g;
   const int blocks = (int)std::min<int64_t>(kAuditBlocks, (rows + rows_per_block - 1) / rows_per_block);
-  if (blocks > 0) { // (rows > 0: a weighted call's row_counts is not null)
-    const uint32_t *counts = weighted ? row_counts : nullptr;
-    if (vec == 4)
-      audit<4>(src, rows, dim, g, blocks, partials, counts, s);
-    else if (vec == 2)
-      audit<2>(src, rows, dim, g, blocks, partials, counts, s);
-    else
-      audit<1>(src, rows, dim, g, blocks, partials, counts, s);
-  }
-  hipLaunchKernelGGL(fcp_table_audit_fold_kernel, dim3(1), dim3(64), 0, s, partials, (int32_t)blocks, rows, out);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail((w + "kernel launch").c_str(), e);
-  return FCP_OK;
+  const uint32_t *counts = weighted ? row_counts : nullptr;
+  return on_device(who, device, stream, [&](hipStream_t s) {
+    if (blocks > 0) // (rows > 0: a weighted call's row_counts is not null)
+      with_vec(vec, [&](auto v) {
+        with_group(g, [&](auto gg) { audit_rows<decltype(v)::value, decltype(gg)::value>(src, rows, dim, blocks, partials, counts, s); });
+      });
+    hipLaunchKernelGGL(fcp_table_audit_fold_kernel, dim3(1), dim3(64), 0, s, partials, (int32_t)blocks, rows, out);
+  });
 }
 
 } // namespace

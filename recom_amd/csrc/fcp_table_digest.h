@@ -20,7 +20,7 @@
 namespace fcpd {
 
 constexpr uint64_t kGolden = 0x9e3779b97f4a7c15ull; // G
-constexpr int64_t kRowLimit = (1ll << 32) - 3;      // rows, n and table_rows stay below it: a plan's row limit
+using fcpf::kRowLimit;                              // rows, n and table_rows stay below it
 
 // the 64-bit finaliser; mix(1) == 0xb456bcfc34c2cb2c
 FCP_DIGEST_FN uint64_t mix(uint64_t x) {

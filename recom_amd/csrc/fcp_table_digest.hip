@@ -32,6 +32,10 @@
 #include "fcp_host.h"
 #include "fcp_table_digest.h"
 
+#pragma clang fp contract(off) // (the header's rule; nothing here is floating point)
+
+#include "fcp_table_walk.h" // with_group, with_one_of: the host's dispatch
+
 namespace {
 
 using fcpd::row_hash;
@@ -211,18 +215,6 @@ template <int A, int G> void launch_ag(const DigestLaunch &L, hipStream_t s) {
                        L.row0, L.row_step, L.row_ids, L.table_rows, L.partials);
 }
 
-template <int A> void launch_a(const DigestLaunch &L, int g, hipStream_t s) {
-  switch (g) {
-  case 1: launch_ag<A, 1>(L, s); break;
-  case 2: launch_ag<A, 2>(L, s); break;
-  case 4: launch_ag<A, 4>(L, s); break;
-  case 8: launch_ag<A, 8>(L, s); break;
-  case 16: launch_ag<A, 16>(L, s); break;
-  case 32: launch_ag<A, 32>(L, s); break;
-  default: launch_ag<A, 64>(L, s); break;
-  }
-}
-
 // G, the lanes that share a row: the largest power of two that is not above the row's words, at most 64 — a row of 9 words
 // (q8, dim 64) takes 8 lanes and two words in its first lane, not 16 lanes of which 7 idle
 int group_of_words(int64_t nw) {
@@ -235,10 +227,6 @@ int group_of_words(int64_t nw) {
 // lie back to back from `base`.
 int digest_entry(const char *who, const void *base, int32_t kind, int32_t dim, int64_t count, int64_t row0, int64_t row_step,
                  const int64_t *row_ids, int64_t table_rows, fcp_table_digest_t *out, void *workspace, int32_t device, void *stream) {
-  DeviceGuard guard;
-  const int rc = guard.enter(device);
-  if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   DigestLaunch L;
   L.base = static_cast<const char *>(base);
   L.count = count;
@@ -253,24 +241,17 @@ int digest_entry(const char *who, const void *base, int32_t kind, int32_t dim, i
   const int g = group_of_words((rb + 7) / 8);
   const int64_t rows_per_block = FCP_BLOCK_THREADS / g;
   L.blocks = (int)std::min<int64_t>(kDigestBlocks, (count + rows_per_block - 1) / rows_per_block);
-  if (L.blocks > 0) {
-    // what is known of every row's address: the base's low bits and the row bytes' (a q8 table of dim % 8 == 0 at an
-    // allocation's start takes the aligned loads)
-    const uintptr_t bits = (uintptr_t)base | (uintptr_t)rb | 8u;
-    const int a = (int)(bits & (~bits + 1));
-    if (a == 8)
-      launch_a<8>(L, g, s);
-    else if (a == 4)
-      launch_a<4>(L, g, s);
-    else if (a == 2)
-      launch_a<2>(L, g, s);
-    else
-      launch_a<1>(L, g, s);
-  }
-  hipLaunchKernelGGL(fcp_table_digest_fold_kernel, dim3(1), dim3(64), 0, s, L.partials, (int32_t)L.blocks, out);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail((std::string(who) + ": kernel launch").c_str(), e);
-  return FCP_OK;
+  // what is known of every row's address: the base's low bits and the row bytes' (a q8 table of dim % 8 == 0 at an
+  // allocation's start takes the aligned loads)
+  const uintptr_t bits = (uintptr_t)base | (uintptr_t)rb | 8u;
+  const int a = (int)(bits & (~bits + 1));
+  return on_device(who, device, stream, [&](hipStream_t s) {
+    if (L.blocks > 0)
+      with_one_of<8, 4, 2, 1>(a, [&](auto al) {
+        with_group(g, [&](auto gg) { launch_ag<decltype(al)::value, decltype(gg)::value>(L, s); });
+      });
+    hipLaunchKernelGGL(fcp_table_digest_fold_kernel, dim3(1), dim3(64), 0, s, L.partials, (int32_t)L.blocks, out);
+  });
 }
 
 } // namespace

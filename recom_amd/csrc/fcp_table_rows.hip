@@ -3,11 +3,10 @@
 // after the load: a trainer ships (row ids, float32 rows) deltas, and fcp_table_convert (fcp_convert.hip) writes contiguous runs
 // only.  The reference reads float32 tables only and has no counterpart.
 //
-//   update -> q8      fcp_update_q8_kernel<V, G>: the row quantiser of fcp_quantize_q8_kernel<V, G>, restated — the same 3 V x 7 G
-//                     matrix, the same group of G lanes per row, the row kept in registers (kQSlots slots per lane of a 64-lane
-//                     group, the tail beyond read a second time), min and max by __shfl_xor butterflies, the two correctly
-//                     rounded divisions, rint to even, nothing contracted — with the destination row taken from the row's id
-//                     instead of its index.  Every lane of a group loads the same id (one address).  A group is live when its
+//   update -> q8      fcp_update_q8_kernel<V, G>: the row quantiser fcp_quantize_q8_kernel<V, G> calls, quantize_row<V, G> of
+//                     fcp_table_walk.h — the one text, so the same 3 V x 7 G matrix, group of G lanes per row, register cap,
+//                     butterflies, divisions and rounding — with the destination row taken from the row's id instead of its
+//                     index.  Every lane of a group loads the same id (one address).  A group is live when its
 //                     row exists and (uint64_t)id < table_rows; lanes of dead groups take part in the exchanges and touch no
 //                     memory.  Codes leave V bytes at a time, scale and bias as one pair (Q8Pair<V>) from the group's first lane:
 //                     id * (dim + 8) keeps the alignment dst_row0 * (dim + 8) has in fcp_convert.hip, a multiple of V.
@@ -48,7 +47,6 @@ template <int V, int G>
 __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
     fcp_update_q8_kernel(char *table, const int64_t *ids, const float *src, int32_t rows, int32_t dim, uint64_t table_rows,
                          unsigned long long *skipped) {
-  constexpr int S = slots_in_registers<G>();
   const int tid = threadIdx.x;
   const int lane = tid & (G - 1);
   const int64_t row = (int64_t)blockIdx.x * (FCP_BLOCK_THREADS / G) + tid / G;
@@ -56,50 +54,7 @@ __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
   const uint64_t id = have ? (uint64_t)*as_global(ids + row) : ~0ull; // the whole group: one address
   const bool live = have && id < table_rows;
   count_skipped(skipped, have && !live && lane == 0);
-  const int nslots = dim / V;
-  const float *srow = src + row * dim;
-  char *drow = table + (live ? id : 0) * ((uint64_t)dim + 8);
-
-  VF<V> x[S];
-  float mn = __builtin_inff(), mx = -__builtin_inff();
-#pragma unroll
-  for (int k = 0; k < S; ++k) {
-    x[k] = vzero<V>();
-    const int slot = lane + k * G;
-    if (live && slot < nslots) {
-      x[k] = ld_f32<V>(srow + (int64_t)slot * V);
-      minmax<V>(x[k], mn, mx);
-    }
-  }
-  if constexpr (G == 64) {
-    if (live)
-      for (int slot = lane + S * G; slot < nslots; slot += G) {
-        const VF<V> t = ld_f32<V>(srow + (int64_t)slot * V);
-        minmax<V>(t, mn, mx);
-      }
-  }
-#pragma unroll
-  for (int m = G / 2; m >= 1; m >>= 1) {
-    mn = fminf(mn, __shfl_xor(mn, m, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, m, 64));
-  }
-  const float range = mx - mn;
-  const float scale = range / 255.0f;
-  const float inv = 255.0f / (range + 1e-8f);
-  if (!live) return;
-#pragma unroll
-  for (int k = 0; k < S; ++k) {
-    const int slot = lane + k * G;
-    if (slot < nslots) st_codes<V>(drow + (int64_t)slot * V, x[k], mn, inv);
-  }
-  if constexpr (G == 64) {
-    for (int slot = lane + S * G; slot < nslots; slot += G) // beyond the register cap: the row's tail is read again
-      st_codes<V>(drow + (int64_t)slot * V, ld_f32<V>(srow + (int64_t)slot * V), mn, inv);
-  }
-  if (lane == 0) {
-    const uint64_t pair = (uint64_t)__float_as_uint(scale) | ((uint64_t)__float_as_uint(mn) << 32);
-    *(FCP_GLOBAL typename Q8Pair<V>::T *)(drow + dim) = pair;
-  }
+  quantize_row<V, G>(table + (live ? id : 0) * ((uint64_t)dim + 8), src + row * dim, dim, lane, live);
 }
 
 // n: slots of this launch (<= 2^30, one row of more: < 2^31); ids / src: the first row of this launch; spr: slots per row,
@@ -149,30 +104,19 @@ __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
   st_f32<V>(dst + (uint64_t)i * V, x);
 }
 
-template <int V, int G>
-void update_q8_rows(char *table, const int64_t *ids, const float *src, int64_t n, int dim, uint64_t table_rows,
-                    unsigned long long *skipped, hipStream_t s) {
-  const int64_t per_launch = kMaxLaunchThreads / G;
-  for (int64_t r0 = 0; r0 < n; r0 += per_launch) {
-    const int64_t rows = std::min(n - r0, per_launch);
-    hipLaunchKernelGGL((fcp_update_q8_kernel<V, G>), blocks_for(rows * G), dim3(FCP_BLOCK_THREADS), 0, s, table, ids + r0,
-                       src + r0 * dim, (int32_t)rows, (int32_t)dim, table_rows, skipped);
-  }
-}
-
-// G: 1 for dims <= 4, else the power of two that holds the row's slots, at most 64 (fcp_convert.hip)
+// G: 1 for dims <= 4, else the power of two that holds the row's slots, at most 64 (group_of)
 template <int V>
 void update_q8(char *table, const int64_t *ids, const float *src, int64_t n, int dim, uint64_t table_rows, unsigned long long *skipped,
                hipStream_t s) {
-  switch (group_of(dim, V)) {
-  case 1: update_q8_rows<V, 1>(table, ids, src, n, dim, table_rows, skipped, s); break;
-  case 2: update_q8_rows<V, 2>(table, ids, src, n, dim, table_rows, skipped, s); break;
-  case 4: update_q8_rows<V, 4>(table, ids, src, n, dim, table_rows, skipped, s); break;
-  case 8: update_q8_rows<V, 8>(table, ids, src, n, dim, table_rows, skipped, s); break;
-  case 16: update_q8_rows<V, 16>(table, ids, src, n, dim, table_rows, skipped, s); break;
-  case 32: update_q8_rows<V, 32>(table, ids, src, n, dim, table_rows, skipped, s); break;
-  default: update_q8_rows<V, 64>(table, ids, src, n, dim, table_rows, skipped, s); break;
-  }
+  with_group(group_of(dim, V), [&](auto g) {
+    constexpr int G = decltype(g)::value;
+    const int64_t per_launch = kMaxLaunchThreads / G;
+    for (int64_t r0 = 0; r0 < n; r0 += per_launch) {
+      const int64_t rows = std::min(n - r0, per_launch);
+      hipLaunchKernelGGL((fcp_update_q8_kernel<V, G>), blocks_for(rows * G), dim3(FCP_BLOCK_THREADS), 0, s, table, ids + r0,
+                         src + r0 * dim, (int32_t)rows, (int32_t)dim, table_rows, skipped);
+    }
+  });
 }
 
 template <int V>
@@ -206,8 +150,8 @@ int check_args(const char *who, const void *table, int32_t kind, int64_t table_r
                int64_t n, const void *skipped) {
   const std::string w = std::string(who) + ": ";
   if (n < 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`n` is negative");
-  if (n >= (1ll << 32) - 3) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`n` must stay below 2^32 - 3");
-  if (table_rows < 1 || table_rows >= (1ll << 32) - 3)
+  if (n >= fcpf::kRowLimit) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`n` must stay below 2^32 - 3");
+  if (table_rows < 1 || table_rows >= fcpf::kRowLimit)
     return fail(FCP_ERR_INVALID_ARGUMENT, w + "`table_rows` must lie in [1, 2^32 - 3), a plan's row limit");
   if (dim <= 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`dim` must be positive");
   if (!fcpf::known_tab_kind(kind)) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`kind` is no FCP_TAB_* value");
@@ -232,21 +176,10 @@ extern "C" int fcp_table_update_rows(void *table, int32_t kind, int64_t table_ro
   int rc = check_args("fcp_table_update_rows", table, kind, table_rows, dim, row_ids, rows, n, skipped);
   if (rc) return rc;
   if (n == 0) return FCP_OK;
-  DeviceGuard guard;
-  rc = guard.enter(device);
-  if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   unsigned long long *sk = reinterpret_cast<unsigned long long *>(skipped);
-  const int vec = vec_of(dim);
-  if (vec == 4)
-    update<4>(table, kind, row_ids, rows, n, dim, (uint64_t)table_rows, sk, s);
-  else if (vec == 2)
-    update<2>(table, kind, row_ids, rows, n, dim, (uint64_t)table_rows, sk, s);
-  else
-    update<1>(table, kind, row_ids, rows, n, dim, (uint64_t)table_rows, sk, s);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail("fcp_table_update_rows: kernel launch", e);
-  return FCP_OK;
+  return on_device("fcp_table_update_rows", device, stream, [&](hipStream_t s) {
+    with_vec(vec_of(dim), [&](auto v) { update<decltype(v)::value>(table, kind, row_ids, rows, n, dim, (uint64_t)table_rows, sk, s); });
+  });
 }
 
 extern "C" int fcp_table_read_rows(float *rows, const void *table, int32_t kind, int64_t table_rows, int32_t dim,
@@ -254,18 +187,7 @@ extern "C" int fcp_table_read_rows(float *rows, const void *table, int32_t kind,
   int rc = check_args("fcp_table_read_rows", table, kind, table_rows, dim, row_ids, rows, n, nullptr);
   if (rc) return rc;
   if (n == 0) return FCP_OK;
-  DeviceGuard guard;
-  rc = guard.enter(device);
-  if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int vec = vec_of(dim);
-  if (vec == 4)
-    read<4>(rows, table, kind, row_ids, n, dim, (uint64_t)table_rows, s);
-  else if (vec == 2)
-    read<2>(rows, table, kind, row_ids, n, dim, (uint64_t)table_rows, s);
-  else
-    read<1>(rows, table, kind, row_ids, n, dim, (uint64_t)table_rows, s);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail("fcp_table_read_rows: kernel launch", e);
-  return FCP_OK;
+  return on_device("fcp_table_read_rows", device, stream, [&](hipStream_t s) {
+    with_vec(vec_of(dim), [&](auto v) { read<decltype(v)::value>(rows, table, kind, row_ids, n, dim, (uint64_t)table_rows, s); });
+  });
 }

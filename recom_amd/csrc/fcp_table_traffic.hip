@@ -209,7 +209,7 @@ extern "C" int fcp_table_count_ids(uint32_t *counts, int64_t table_rows, const v
                                    int32_t device, void *stream) {
   const std::string w = "fcp_table_count_ids: ";
   if (n < 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`n` is negative");
-  if (table_rows < 1 || table_rows >= (1ll << 32) - 3)
+  if (table_rows < 1 || table_rows >= fcpf::kRowLimit)
     return fail(FCP_ERR_INVALID_ARGUMENT, w + "`table_rows` must lie in [1, 2^32 - 3), a plan's row limit");
   if (id_bytes != 4 && id_bytes != 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`id_bytes` is 4 (int32 ids) or 8 (int64 ids)");
   if (n > 0 && !counts) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`counts` is null");
@@ -219,19 +219,14 @@ extern "C" int fcp_table_count_ids(uint32_t *counts, int64_t table_rows, const v
     return fail(FCP_ERR_INVALID_ARGUMENT, w + "`ids` is not " + std::to_string(id_bytes) + "-byte aligned");
   if ((uintptr_t)skipped % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`skipped` is not 8-byte aligned");
   if (n == 0) return FCP_OK;
-  DeviceGuard guard;
-  const int rc = guard.enter(device);
-  if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   unsigned long long *sk = reinterpret_cast<unsigned long long *>(skipped);
   const int blocks = (int)std::min<int64_t>(kCountBlocks, n / kTileIds + (n % kTileIds != 0));
-  if (id_bytes == 8)
-    hipLaunchKernelGGL(fcp_table_count_ids_kernel<int64_t>, dim3(blocks), dim3(kCountThreads), 0, s, counts, (uint64_t)table_rows,
-                       static_cast<const int64_t *>(ids), n, sk);
-  else
-    hipLaunchKernelGGL(fcp_table_count_ids_kernel<int32_t>, dim3(blocks), dim3(kCountThreads), 0, s, counts, (uint64_t)table_rows,
-                       static_cast<const int32_t *>(ids), n, sk);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail("fcp_table_count_ids: kernel launch", e);
-  return FCP_OK;
+  return on_device("fcp_table_count_ids", device, stream, [&](hipStream_t s) {
+    if (id_bytes == 8)
+      hipLaunchKernelGGL(fcp_table_count_ids_kernel<int64_t>, dim3(blocks), dim3(kCountThreads), 0, s, counts, (uint64_t)table_rows,
+                         static_cast<const int64_t *>(ids), n, sk);
+    else
+      hipLaunchKernelGGL(fcp_table_count_ids_kernel<int32_t>, dim3(blocks), dim3(kCountThreads), 0, s, counts, (uint64_t)table_rows,
+                         static_cast<const int32_t *>(ids), n, sk);
+  });
 }

@@ -95,6 +95,64 @@ def test_status_codes_arrive_in_the_stated_order():
             assert _audit(*args)[0] == NODEV, args
 
 
+# ---- code object -----------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def audit_asm(tmp_path_factory):
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not (os.path.exists(hipcc) or shutil.which("hipcc")):
+        pytest.skip("no hipcc")
+    asm = tmp_path_factory.mktemp("asm") / "fcp_table_audit.s"
+    proc = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "-O3", "--offload-device-only", "-S",
+                           os.path.join(CSRC, "fcp_table_audit.hip"), "-o", str(asm)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    return asm.read_text()
+
+
+def test_code_object_of_the_audit_kernels(audit_asm):
+    """fcp_table_audit.hip compiles for gfx950: 3 V x 7 G x {unweighted, weighted} audit kernels and the fold; no scratch; LDS
+    only for the four wave records of a block's fold (384 bytes), none in the fold kernel; denormals kept, IEEE mode.  A lane
+    passes n = V * (S + 1 if G == 64 else S) elements per row through `judge` (S: slots_in_registers; the + 1: the tail loop's
+    body) and loads S + (2 if G == 64 else 0) slots (the tail in both passes); a weighted kernel loads the row's count besides
+    and nothing else.  Each element is one float64 fused multiply-add into each of the four sums (nothing else is fused in
+    float64: the fold adds), and ONE float32 fma, ld_q8's — every other float32 fma belongs to the two divisions' expansions
+    (five each, as in fcp_convert.hip): nothing is contracted, nothing packed."""
+    kernels = {m.group(1): m.group(2) for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", audit_asm, re.S)}
+    field = lambda desc, name: int(re.search(r"\.amdhsa_" + name + r" (\d+)", desc).group(1))
+
+    def body(name):
+        label = re.search(r"^" + re.escape(name) + r":", audit_asm, re.M)
+        assert label, name
+        text = audit_asm[label.end():audit_asm.find(".amdhsa_kernel " + name)]
+        code = (ln.split(";")[0].split() for ln in text.splitlines() if ln.startswith("\t"))        # (labels start in column 0)
+        return [words[0] for words in code if words and not words[0].startswith(".")]
+
+    audit = {k for k in kernels if "fcp_table_audit_kernel" in k}
+    (fold,) = [k for k in kernels if "fcp_table_audit_fold_kernel" in k]
+    assert len(audit) == 42 and len(kernels) == 43, sorted(kernels)
+    for name, desc in sorted(kernels.items()):
+        assert field(desc, "private_segment_fixed_size") == 0, f"{name}: uses scratch"
+        assert field(desc, "group_segment_fixed_size") == (0 if name == fold else 384), name
+        assert re.search(r"\.amdhsa_float_denorm_mode_32 3\b", desc), f"{name}: fp32 subnormals are flushed"
+        assert re.search(r"\.amdhsa_float_denorm_mode_16_64 3\b", desc), f"{name}: fp16 / fp64 subnormals are flushed"
+        assert re.search(r"\.amdhsa_ieee_mode 1\b", desc), f"{name}: not in IEEE mode"
+        assert not any(op.startswith("scratch_") for op in body(name)), name
+    for v in (1, 2, 4):
+        for g in (1, 2, 4, 8, 16, 32, 64):
+            ops = {}
+            for weighted in (0, 1):
+                (name,) = [k for k in audit if f"fcp_table_audit_kernelILi{v}ELi{g}ELb{weighted}EE" in k]
+                ops[weighted] = body(name)
+            kept = 4 if g == 64 else 3 if g == 1 else 1
+            loads = [sum(op.startswith("global_load") for op in ops[w]) for w in (0, 1)]
+            assert loads == [kept + (2 if g == 64 else 0), kept + (2 if g == 64 else 0) + 1], (v, g, loads)
+            n = v * (kept + (g == 64))
+            for w in (0, 1):
+                assert sum(bool(re.match(r"v_fmac?_f64", op)) for op in ops[w]) == 4 * n, (v, g, w)
+                assert not any(re.match(r"v_pk_fma_f32|v_mac_f32|v_mad_f32", op) for op in ops[w]), (v, g, w)
+                assert ops[w].count("v_div_fixup_f32") == 2 and ops[w].count("v_div_fmas_f32") == 2, (v, g, w)
+                assert sum(bool(re.match(r"v_fmac?_f32", op)) for op in ops[w]) == 5 * 2 + n, (v, g, w)
+
+
 # ---- the chooser ---------------------------------------------------------------------------------------------------------------
 def _raw_audits(inst):
     arr = (_lib.TableAudit * len(inst["tables"]))()
