@@ -536,6 +536,60 @@ int fcp_table_update_rows(void *table, int32_t kind, int64_t table_rows, int32_t
  * status order are those of fcp_table_update_rows. */
 int fcp_table_read_rows(float *rows, const void *table, int32_t kind, int64_t table_rows, int32_t dim, const int64_t *row_ids,
                         int64_t n, int32_t device, void *stream);
+/* ---- a delta's ids made distinct: the last occurrence of an id wins ---------------------------------------------------------- */
+/* fcp_table_update_rows and fcp_table_digest_rows ask that the ids of one call be pairwise distinct and do not check.  Deltas
+ * do repeat ids: two incremental checkpoints concatenated before they are applied, a parameter stream replayed after a
+ * reconnect, a trainer that logs a row each time it touches it.  fcp_table_delta_distinct is the check ("is this delta
+ * distinct?") and the fix ("make it distinct, the last write wins") in one entry, on the device, with neither a sort nor a lock:
+ * the winner of a row is the maximum of the positions that name it, and a maximum commutes.
+ *
+ * `row_ids` is int64 [n] (id_bytes 8) or int32 [n] (id_bytes 4, sign-extended), as fcp_table_count_ids takes ids; `rows` is
+ * float32 [n, dim], or NULL for ids only — then `rows_out` must be NULL too and `dim` is not read.  Everything is on the device.
+ *
+ * Who wins.  An id is inside the table when its whole 64-bit value, compared unsigned, is below table_rows (the rule of the
+ * plans and of fcp_table_update_rows).  Position i WINS if its id is inside the table and no position j > i holds the same id.
+ * With the winners p_0 < p_1 < ... < p_(m-1) — ascending position: the result is stable —
+ *   ids_out[k]     = the id at p_k for k < m, and -1 for m <= k < n;                             int64 [n]
+ *   pos_out[k]     = p_k for k < m, and -1 for m <= k < n;                                       int64 [n]; may be NULL
+ *   rows_out[k, :] = the dim 32-bit words of rows[p_k, :] for k < m, copied as BITS (NaN payloads and -0.0 survive); rows
+ *                    k >= m of rows_out are not touched;                                         float32 [n, dim]
+ *   *report        = {n, m, duplicates, skipped}, as declared below; n == distinct + duplicates + skipped.
+ * A delta that is already distinct and inside the table comes out byte for byte as it went in, with duplicates == 0: that is
+ * the check.
+ *
+ * Chaining without the host.  The -1 tail lets (ids_out, rows_out, n) go straight into fcp_table_update_rows and
+ * fcp_table_digest_rows on the same stream; no host read of m is needed.  Both skip -1 and touch no memory for it; their
+ * `skipped` counters then count the n - m ids of the tail too (the delta's own ids outside the table are report->skipped).
+ *
+ * Device to device on `device`, asynchronous on `stream` (a hipStream_t), no allocation, no synchronisation.  `workspace` holds
+ * fcp_table_delta_workspace_bytes of n bytes; its content before and after the call means nothing.  Every output byte is a
+ * function of the arguments alone — not of the grid, of the hash, of the order of any atomic operation or of what the workspace
+ * held: two calls leave the same bytes.  Inputs are only read; outputs must not overlap the inputs or each other (not
+ * checked).  n < 2^32 - 3, and table_rows lies in [1, 2^32 - 3).  Alignment: `row_ids` id_bytes; `rows` and `rows_out` that of a
+ * float32 table of this dim (4 * V bytes, V the largest of 4 | 2 | 1 that divides dim); `ids_out`, `pos_out`, `report` and
+ * `workspace` 8 bytes.
+ *
+ * The workspace size depends on n only: a multiple of 8, non-decreasing in n, at most 40 * n + 2^20; -1 for n < 0 or n beyond
+ * its limit.
+ *
+ * Status, decided in this order (the first needs no device), as in fcp_table_digest_rows:
+ *   FCP_ERR_INVALID_ARGUMENT  n < 0 or beyond its limit; table_rows outside its range; an id_bytes that is neither 4 nor 8;
+ *                             dim <= 0 with rows; a rows_out without rows, or rows without a rows_out; a null report or
+ *                             workspace; a null row_ids or ids_out with n > 0; a misaligned row_ids, rows, ids_out, rows_out,
+ *                             pos_out, report or workspace (in this order); fcp_last_error names the argument between backquotes;
+ *   FCP_ERR_NO_DEVICE         no usable gfx950 device (n == 0 included: `report` is written on the device);
+ *   FCP_ERR_HIP               a kernel launch failed.
+ * No combination of valid arguments is FCP_ERR_UNSUPPORTED. */
+typedef struct fcp_table_delta_report {
+  int64_t n;          /* ids handed over */
+  int64_t distinct;   /* rows kept: one per distinct id inside the table */
+  int64_t duplicates; /* occurrences dropped because a LATER position names the same row */
+  int64_t skipped;    /* ids outside [0, table_rows); n == distinct + duplicates + skipped */
+} fcp_table_delta_report_t; /* 32 bytes */
+int64_t fcp_table_delta_workspace_bytes(int64_t n);
+int fcp_table_delta_distinct(const void *row_ids, int32_t id_bytes, const float *rows, int32_t dim, int64_t n, int64_t table_rows,
+                             int64_t *ids_out, float *rows_out, int64_t *pos_out, fcp_table_delta_report_t *report, void *workspace,
+                             int32_t device, void *stream);
 /* ---- table audit: what each compact format would do to a float32 table, before anything is written --------------------------- */
 /* fcp_table_audit: judge `rows` float32 rows of width `dim` — a table before fcp_table_convert, or the rows of a delta before
  * fcp_table_update_rows — against FCP_TAB_BF16, FCP_TAB_F16 and FCP_TAB_Q8 at once, reading every source element once (the

@@ -1,0 +1,431 @@
+// fcp_table_delta.hip — fcp_table_delta_distinct / fcp_table_delta_workspace_bytes: make the ids of a delta pairwise distinct on
+// the device, the LAST occurrence of an id winning, before fcp_table_update_rows (fcp_table_rows.hip) and fcp_table_digest_rows
+// (fcp_table_digest.hip) see it — both ask for distinct ids and neither checks.  No sort and no lock: the winner of a row is the
+// MAXIMUM of the positions that name it, and a maximum commutes.  The reference has no counterpart.
+//
+// The workspace holds, in this order: kDeltaBlocks + 1 records of 32 bytes (one per block of the fixed grid, and the totals),
+// an open-addressed hash table of `cells` {uint32 row, uint32 pos1} cells — cells a power of two, at least 2 n and at least
+// kDeltaMinCells, so the load stays at or below 0.5 and an empty cell always exists — and one flag byte per position.  A row's
+// home cell is the top bits of row * kDeltaHashMul (64-bit, Fibonacci hashing: ids that share low bits, as the ids of one
+// shard do, still spread); probing is linear.  The phases are separate launches; launch boundaries order them, no block ever
+// waits for another, and every probe loop is bounded by the number of cells.
+//
+//   fcp_delta_clear_kernel      every cell {kEmptyCell, 0}: one 8-byte store per cell (what the workspace is aligned to), a stride loop.
+//   fcp_delta_insert_kernel<SLOTS>   the grid of fcp_plan_traffic_kernel: 256 threads, tiles of kDeltaInsertTile positions, 4 per
+//                     thread kDeltaThreads apart, a stride loop over tiles.  An id is widened to 64 bits (int32: sign-extended)
+//                     and compared unsigned against table_rows; an id outside touches nothing.  insert_global: walk from the
+//                     home cell, claim an empty cell's key with a compare-and-swap (a key never changes once claimed, so a
+//                     relaxed load that sees a stale EMPTY only costs the compare-and-swap that tells the truth), then
+//                     atomicMax(pos1, i + 1).  SLOTS > 0: the block first resolves its share in LDS — count_row's scheme
+//                     (fcp_table_traffic.hip) with max in place of add: SLOTS {row, pos1} cells, home row mod SLOTS,
+//                     kDeltaProbes probes, else straight to insert_global — and flushes one insert_global per occupied
+//                     cell: a row that every position names costs one global atomic per block, not one per position.
+//                     SLOTS == 0 (-DFCP_DELTA_SLOTS=0): one insert_global per position — built for the measurement only: it
+//                     is as fast on distinct ids and 7x (Zipf) to 260x (one row) slower on repeated ones
+//                     (profiles/table_delta.txt).
+//   fcp_delta_classify_kernel   kDeltaBlocks blocks at the most, block b owns the contiguous chunk [b * chunk, (b + 1) * chunk) of
+//                     positions, chunk a multiple of kDeltaTile.  Position i with an id inside the table looks its row up (the
+//                     row is there: the insert phase has run) and WINS when the cell's pos1 is i + 1.  One flag byte per
+//                     position (1: wins), and ONE partial record per block: winners, duplicates, skipped.
+//   fcp_delta_fold_kernel       one wave: exclusive offsets of the blocks' winners into their records, the totals record, the report.
+//   fcp_delta_compact_kernel<V, G>   the classify grid again.  Per tile of kDeltaTile positions: winners are ranked by ballot and
+//                     popcount inside a wave and a scan of the four wave counts, so winner number k of the call — in ascending
+//                     position: stable — writes ids_out[k] and pos_out[k]; positions i >= m write the -1 tails.  V > 0: the
+//                     tile's winners' rows are then copied by power-of-two groups of G lanes, V 32-bit words per load and
+//                     store (integer vectors: bits, not floats), rows[p_k] -> rows_out[k].  V == 0: ids only.
+// Every output byte is a function of the arguments alone: the hash, the grid and the order of the atomics decide only WHERE a
+// row's cell lies and WHEN its maximum is reached.  Nothing is dereferenced by an id's value but the cell it maps to.
+// All global atomics are vector forms at agent scope, results unused except the compare-and-swap's; nothing scalar.
+// No scratch (-Rpass-analysis=kernel-resource-usage: ScratchSize 0 for every kernel); LDS: the insert kernel's two arrays
+// (16 KiB at SLOTS 2048), the compact kernel's winner list and wave counts (1 KiB + 16 bytes), the classify kernel's fold (48 bytes).
+#include "fcp_fused_bodies.h"
+#include "fcp_host.h"
+
+#pragma clang fp contract(off) // (fcp_table_walk.h's rule; nothing here is floating point)
+
+#include "fcp_table_walk.h" // vec_of, group_of, with_vec, with_group: the rows' V and G, the host's dispatch
+
+// Cells of a block's LDS table in fcp_delta_insert_kernel (a power of two; 2 x 8 KiB of LDS at 2048, for a tile of 1024
+// positions, as fcp_plan_traffic_kernel is sized).  -DFCP_DELTA_SLOTS=0 builds the plain kernel instead — one global claim and
+// max per position, no LDS — which the choice was measured against (scripts/table_delta_cost.py --variant,
+// profiles/table_delta.txt); the library is built with the default.
+#ifndef FCP_DELTA_SLOTS
+#define FCP_DELTA_SLOTS 2048
+#endif
+
+namespace {
+
+constexpr int kDeltaThreads = FCP_BLOCK_THREADS;
+constexpr int kDeltaTile = kDeltaThreads;           // positions of one step of a classify / compact block
+constexpr int kDeltaBlocks = 1024;                  // the fixed grid of classify / compact; also the partial records
+constexpr int kDeltaMinChunkTiles = 4;              // a block's chunk is at least this many tiles
+constexpr int kDeltaInsertIdsPerThread = 4;
+constexpr int kDeltaInsertTile = kDeltaThreads * kDeltaInsertIdsPerThread;
+constexpr int kDeltaInsertMaxBlocks = 65535;        // longer deltas: the stride loop
+constexpr int kDeltaClearBlocks = 4096;
+constexpr int kDeltaSlots = FCP_DELTA_SLOTS;
+constexpr int kDeltaProbes = 4;                     // LDS cells a row looks at, from its home slot on
+constexpr int64_t kDeltaMinCells = 64;
+constexpr uint64_t kDeltaHashMul = 0x9E3779B97F4A7C15ull;
+constexpr uint32_t kEmptyCell = 0xFFFFFFFFu;        // table_rows < 2^32 - 3: a row index fits 32 bits, and this is none
+static_assert(kDeltaThreads == 256, "four waves per block: the compact kernel's scan of wave counts");
+static_assert((kDeltaSlots & (kDeltaSlots - 1)) == 0 && kDeltaSlots % kDeltaThreads == 0, "slot masks and the flush loop");
+
+typedef __attribute__((address_space(3))) uint32_t LdsU32;
+
+// What a block of the classify phase counted, and, once the fold has run, where its winners go.  32 bytes.
+struct DeltaPartial {
+  int64_t winners, duplicates, skipped;
+  int64_t offset; // winners of the blocks before this one (the totals record: unused)
+};
+static_assert(sizeof(DeltaPartial) == 32 && sizeof(fcp_table_delta_report_t) == 32, "records of 32 bytes");
+
+struct DeltaTable {
+  uint32_t *cells; // cell c: key at cells[2 c], pos1 at cells[2 c + 1]
+  uint64_t mask;   // cells - 1
+  int32_t shift;   // 64 - log2(cells)
+};
+
+__device__ __forceinline__ uint64_t ld_id(const void *ids, int64_t i, bool is64) {
+  return is64 ? (uint64_t)*as_global(static_cast<const int64_t *>(ids) + i)
+              : (uint64_t)(int64_t)*as_global(static_cast<const int32_t *>(ids) + i);
+}
+
+__device__ __forceinline__ uint64_t home_of(const DeltaTable &T, uint32_t row) { return ((uint64_t)row * kDeltaHashMul) >> T.shift; }
+
+// pos1 into the cell of `row`, claiming one if the row has none yet.  At most `cells` steps; the load is at or below 0.5.
+__device__ __forceinline__ void insert_global(const DeltaTable &T, uint32_t row, uint32_t pos1) {
+  uint64_t c = home_of(T, row);
+  for (uint64_t step = 0; step <= T.mask; ++step, c = (c + 1) & T.mask) {
+    uint32_t *key = T.cells + 2 * c;
+    uint32_t k = __hip_atomic_load(as_global(key), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (k == kEmptyCell) {
+      uint32_t seen = kEmptyCell; // what the cell held: still empty = claimed for row
+      __hip_atomic_compare_exchange_strong(as_global(key), &seen, row, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      k = seen == kEmptyCell ? row : seen;
+    }
+    if (k == row) {
+      (void)__hip_atomic_fetch_max(as_global(key + 1), pos1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return;
+    }
+  }
+}
+
+// the pos1 of `row`'s cell; 0 if the row has none (the insert phase gave every row inside the table one)
+__device__ __forceinline__ uint32_t lookup_global(const DeltaTable &T, uint32_t row) {
+  uint64_t c = home_of(T, row);
+  for (uint64_t step = 0; step <= T.mask; ++step, c = (c + 1) & T.mask) {
+    const uint64_t cell = *as_global(reinterpret_cast<const uint64_t *>(T.cells + 2 * c)); // key in the low half, pos1 in the high
+    if ((uint32_t)cell == row) return (uint32_t)(cell >> 32);
+    if ((uint32_t)cell == kEmptyCell) return 0;
+  }
+  return 0;
+}
+
+// one cell per 8-byte store (the workspace is 8-byte aligned, no more)
+__global__ void __launch_bounds__(kDeltaThreads) fcp_delta_clear_kernel(uint32_t *cells, uint64_t n_cells) {
+  const uint64_t empty = (uint64_t)kEmptyCell; // key in the low half, pos1 = 0 in the high
+  for (uint64_t i = (uint64_t)blockIdx.x * kDeltaThreads + threadIdx.x; i < n_cells; i += (uint64_t)gridDim.x * kDeltaThreads)
+    *as_global(reinterpret_cast<uint64_t *>(cells) + i) = empty;
+}
+
+// one position of row r into the block's LDS table, or — no cell within the probes — into the global one
+template <int SLOTS>
+__device__ __forceinline__ void insert_row(const DeltaTable &T, LdsU32 *s_key, LdsU32 *s_pos, uint32_t r, uint32_t pos1) {
+  if constexpr (SLOTS > 0) {
+#pragma unroll
+    for (int p = 0; p < kDeltaProbes; ++p) {
+      const uint32_t slot = (r + p) & (SLOTS - 1);
+      uint32_t k = __hip_atomic_load(&s_key[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (k == kEmptyCell) {
+        uint32_t seen = kEmptyCell;
+        __hip_atomic_compare_exchange_strong(&s_key[slot], &seen, r, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        k = seen == kEmptyCell ? r : seen;
+      }
+      if (k == r) {
+        (void)__hip_atomic_fetch_max(&s_pos[slot], pos1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        return;
+      }
+    }
+  }
+  insert_global(T, r, pos1);
+}
+
+template <int SLOTS>
+__global__ void __launch_bounds__(kDeltaThreads)
+    fcp_delta_insert_kernel(DeltaTable T, const void *ids, int32_t is64, int64_t n, uint64_t table_rows) {
+  __shared__ uint32_t s_key[SLOTS > 0 ? SLOTS : 1];
+  __shared__ uint32_t s_pos[SLOTS > 0 ? SLOTS : 1];
+  const int tid = threadIdx.x;
+  if constexpr (SLOTS > 0) {
+    for (int i = tid; i < SLOTS; i += kDeltaThreads) {
+      s_key[i] = kEmptyCell;
+      s_pos[i] = 0;
+    }
+    __syncthreads();
+  }
+  for (int64_t base = (int64_t)blockIdx.x * kDeltaInsertTile; base < n; base += (int64_t)gridDim.x * kDeltaInsertTile) {
+    uint64_t id[kDeltaInsertIdsPerThread];
+#pragma unroll
+    for (int k = 0; k < kDeltaInsertIdsPerThread; ++k) {
+      const int64_t i = base + k * kDeltaThreads + tid;
+      id[k] = i < n ? ld_id(ids, i, is64 != 0) : ~0ull; // (~0: outside every table)
+    }
+#pragma unroll
+    for (int k = 0; k < kDeltaInsertIdsPerThread; ++k) {
+      const int64_t i = base + k * kDeltaThreads + tid;
+      if (id[k] < table_rows) insert_row<SLOTS>(T, (LdsU32 *)s_key, (LdsU32 *)s_pos, (uint32_t)id[k], (uint32_t)(i + 1));
+    }
+  }
+  if constexpr (SLOTS > 0) {
+    __syncthreads();
+    for (int i = tid; i < SLOTS; i += kDeltaThreads) {
+      const uint32_t r = s_key[i];
+      if (r != kEmptyCell) insert_global(T, r, s_pos[i]); // (a claimed cell's pos1 is at least 1)
+    }
+  }
+}
+
+// chunk: positions of a block, a multiple of kDeltaTile; every thread of a block takes the same number of steps
+__global__ void __launch_bounds__(kDeltaThreads)
+    fcp_delta_classify_kernel(DeltaTable T, const void *ids, int32_t is64, int64_t n, int64_t chunk, uint64_t table_rows, uint8_t *flags,
+                              DeltaPartial *partials) {
+  const int tid = threadIdx.x;
+  const int64_t c0 = (int64_t)blockIdx.x * chunk;
+  const int64_t c1 = c0 + chunk < n ? c0 + chunk : n;
+  uint32_t winners = 0, duplicates = 0, skipped = 0; // (a chunk stays below 2^23 positions)
+  for (int64_t t0 = c0; t0 < c1; t0 += kDeltaTile) {
+    const int64_t i = t0 + tid;
+    if (i < c1) {
+      const uint64_t id = ld_id(ids, i, is64 != 0);
+      bool win = false;
+      if (id < table_rows) {
+        win = lookup_global(T, (uint32_t)id) == (uint32_t)(i + 1);
+        winners += win;
+        duplicates += !win;
+      } else {
+        ++skipped;
+      }
+      *as_global(flags + i) = win ? 1 : 0;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    winners += __shfl_xor(winners, m, 64);
+    duplicates += __shfl_xor(duplicates, m, 64);
+    skipped += __shfl_xor(skipped, m, 64);
+  }
+  __shared__ uint32_t s_wave[kDeltaThreads / 64][3];
+  if ((tid & 63) == 0) {
+    s_wave[tid / 64][0] = winners;
+    s_wave[tid / 64][1] = duplicates;
+    s_wave[tid / 64][2] = skipped;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    DeltaPartial p = {0, 0, 0, 0};
+    for (int w = 0; w < kDeltaThreads / 64; ++w) {
+      p.winners += s_wave[w][0];
+      p.duplicates += s_wave[w][1];
+      p.skipped += s_wave[w][2];
+    }
+    partials[blockIdx.x] = p;
+  }
+}
+
+// one wave; lane l owns the records [l * per, (l + 1) * per) of the nblocks the classify phase wrote (0: it was not launched)
+__global__ void __launch_bounds__(64)
+    fcp_delta_fold_kernel(DeltaPartial *partials, int32_t nblocks, int64_t n, fcp_table_delta_report_t *report) {
+  constexpr int per = kDeltaBlocks / 64;
+  const int lane = threadIdx.x;
+  const int b0 = lane * per, b1 = b0 + per < nblocks ? b0 + per : nblocks;
+  int64_t winners = 0, duplicates = 0, skipped = 0;
+  for (int b = b0; b < b1; ++b) {
+    winners += partials[b].winners;
+    duplicates += partials[b].duplicates;
+    skipped += partials[b].skipped;
+  }
+  int64_t before = winners; // inclusive scan of the lanes' winners, then made exclusive
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int64_t up = __shfl_up(before, d, 64);
+    if (lane >= d) before += up;
+  }
+  before -= winners;
+  for (int b = b0; b < b1; ++b) {
+    partials[b].offset = before;
+    before += partials[b].winners;
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    winners += __shfl_xor(winners, m, 64);
+    duplicates += __shfl_xor(duplicates, m, 64);
+    skipped += __shfl_xor(skipped, m, 64);
+  }
+  if (lane != 0) return;
+  partials[kDeltaBlocks] = DeltaPartial{winners, duplicates, skipped, 0};
+  fcp_table_delta_report_t r;
+  r.n = n;
+  r.distinct = winners;
+  r.duplicates = duplicates;
+  r.skipped = skipped;
+  *report = r;
+}
+
+// V 32-bit words as one load / store at the rows' alignment 4 * V
+template <int V> struct DeltaWords;
+template <> struct DeltaWords<4> { typedef uint32_t __attribute__((ext_vector_type(4))) T; };
+template <> struct DeltaWords<2> { typedef uint32_t __attribute__((ext_vector_type(2))) T; };
+template <> struct DeltaWords<1> { typedef uint32_t T; };
+
+struct DeltaCompact {
+  const void *ids;
+  const float *rows;
+  const uint8_t *flags;
+  const DeltaPartial *partials;
+  int64_t *ids_out, *pos_out; // pos_out may be null
+  float *rows_out;
+  int64_t n, chunk;
+  int32_t is64, dim;
+};
+
+// V == 0: ids only (rows and rows_out are null and never read); else G lanes copy a winner's row, V words at a time
+template <int V, int G> __global__ void __launch_bounds__(kDeltaThreads) fcp_delta_compact_kernel(const DeltaCompact A) {
+  __shared__ uint32_t s_list[kDeltaTile]; // the tile's winners, by rank: their thread
+  __shared__ uint32_t s_count[kDeltaThreads / 64];
+  const int tid = threadIdx.x;
+  const int wave = tid / 64;
+  const int64_t c0 = (int64_t)blockIdx.x * A.chunk;
+  const int64_t c1 = c0 + A.chunk < A.n ? c0 + A.chunk : A.n;
+  const int64_t m = A.partials[kDeltaBlocks].winners;
+  int64_t k0 = A.partials[blockIdx.x].offset; // the output index of the tile's first winner
+  for (int64_t t0 = c0; t0 < c1; t0 += kDeltaTile) {
+    const int64_t i = t0 + tid;
+    const bool have = i < c1;
+    const bool win = have && *as_global(A.flags + i) != 0;
+    const uint64_t id = have ? ld_id(A.ids, i, A.is64 != 0) : 0;
+    const unsigned long long ballot = __ballot(win);
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+    if ((tid & 63) == 0) s_count[wave] = (uint32_t)__popcll(ballot);
+    __syncthreads();
+    uint32_t rank = below, total = 0;
+#pragma unroll
+    for (int w = 0; w < kDeltaThreads / 64; ++w) {
+      const uint32_t c = s_count[w];
+      if (w < wave) rank += c;
+      total += c;
+    }
+    if (win) {
+      *as_global(A.ids_out + (k0 + rank)) = (int64_t)id;
+      if (A.pos_out) *as_global(A.pos_out + (k0 + rank)) = i;
+      if constexpr (V > 0) s_list[rank] = (uint32_t)tid;
+    }
+    if (have && i >= m) { // the tails: indices no winner has
+      *as_global(A.ids_out + i) = -1;
+      if (A.pos_out) *as_global(A.pos_out + i) = -1;
+    }
+    __syncthreads(); // s_list is whole; s_count may be written again
+    if constexpr (V > 0) {
+      typedef typename DeltaWords<V>::T W;
+      const int lane = tid & (G - 1);
+      const int nslots = A.dim / V;
+      for (uint32_t j = (uint32_t)(tid / G); j < total; j += kDeltaThreads / G) {
+        const FCP_GLOBAL W *src = as_global(reinterpret_cast<const W *>(A.rows + (t0 + (int64_t)s_list[j]) * A.dim));
+        FCP_GLOBAL W *dst = as_global(reinterpret_cast<W *>(A.rows_out + (k0 + (int64_t)j) * A.dim));
+        for (int slot = lane; slot < nslots; slot += G) dst[slot] = src[slot];
+      }
+      __syncthreads(); // the copies have read s_list
+    }
+    k0 += total;
+  }
+}
+
+int64_t cells_for(int64_t n) {
+  int64_t cells = kDeltaMinCells;
+  while (cells < 2 * n) cells <<= 1;
+  return cells;
+}
+int64_t partial_bytes() { return (int64_t)(kDeltaBlocks + 1) * (int64_t)sizeof(DeltaPartial); }
+
+} // namespace
+
+extern "C" int64_t fcp_table_delta_workspace_bytes(int64_t n) {
+  if (n < 0 || n >= fcpf::kRowLimit) return -1;
+  return partial_bytes() + cells_for(n) * 8 + (n + 7) / 8 * 8;
+}
+
+extern "C" int fcp_table_delta_distinct(const void *row_ids, int32_t id_bytes, const float *rows, int32_t dim, int64_t n, int64_t table_rows,
+                                        int64_t *ids_out, float *rows_out, int64_t *pos_out, fcp_table_delta_report_t *report,
+                                        void *workspace, int32_t device, void *stream) {
+  const std::string w = "fcp_table_delta_distinct: ";
+  if (n < 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`n` is negative");
+  if (n >= fcpf::kRowLimit) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`n` must stay below 2^32 - 3");
+  if (table_rows < 1 || table_rows >= fcpf::kRowLimit)
+    return fail(FCP_ERR_INVALID_ARGUMENT, w + "`table_rows` must lie in [1, 2^32 - 3), a plan's row limit");
+  if (id_bytes != 4 && id_bytes != 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`id_bytes` is 4 (int32 ids) or 8 (int64 ids)");
+  if (rows && dim <= 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`dim` must be positive");
+  if (rows_out && !rows) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`rows_out` without `rows`: ids only takes both null");
+  if (rows && !rows_out) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`rows_out` is null and `rows` is not");
+  if (!report) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`report` is null");
+  if (!workspace) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`workspace` is null");
+  if (n > 0 && !row_ids) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`row_ids` is null");
+  if (n > 0 && !ids_out) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`ids_out` is null");
+  const int vec = rows ? vec_of(dim) : 1;
+  const auto misaligned = [&](const char *name, const void *p, int align, const char *what) {
+    return fail(FCP_ERR_INVALID_ARGUMENT, w + "`" + name + "` is not " + std::to_string(align) + "-byte aligned" + what);
+  };
+  if ((uintptr_t)row_ids % (uintptr_t)id_bytes) return misaligned("row_ids", row_ids, id_bytes, "");
+  if ((uintptr_t)rows % (4 * vec)) return misaligned("rows", rows, 4 * vec, " (float32 rows of this dim)");
+  if ((uintptr_t)ids_out % 8) return misaligned("ids_out", ids_out, 8, "");
+  if ((uintptr_t)rows_out % (4 * vec)) return misaligned("rows_out", rows_out, 4 * vec, " (float32 rows of this dim)");
+  if ((uintptr_t)pos_out % 8) return misaligned("pos_out", pos_out, 8, "");
+  if ((uintptr_t)report % 8) return misaligned("report", report, 8, "");
+  if ((uintptr_t)workspace % 8) return misaligned("workspace", workspace, 8, "");
+
+  DeltaPartial *partials = static_cast<DeltaPartial *>(workspace);
+  const int64_t cells = cells_for(n);
+  DeltaTable T;
+  T.cells = reinterpret_cast<uint32_t *>(static_cast<char *>(workspace) + partial_bytes());
+  T.mask = (uint64_t)cells - 1;
+  T.shift = 64 - __builtin_ctzll((unsigned long long)cells);
+  uint8_t *flags = reinterpret_cast<uint8_t *>(T.cells) + cells * 8;
+  // the classify / compact grid: chunks of whole tiles, at least kDeltaMinChunkTiles of them, at most kDeltaBlocks chunks
+  const int64_t tiles = (n + kDeltaTile - 1) / kDeltaTile;
+  const int64_t chunk = std::max<int64_t>(kDeltaMinChunkTiles, (tiles + kDeltaBlocks - 1) / kDeltaBlocks) * kDeltaTile;
+  const int nblocks = (int)((n + chunk - 1) / chunk);
+  const int64_t insert_tiles = (n + kDeltaInsertTile - 1) / kDeltaInsertTile;
+  DeltaCompact A;
+  A.ids = row_ids;
+  A.rows = rows;
+  A.flags = flags;
+  A.partials = partials;
+  A.ids_out = ids_out;
+  A.pos_out = pos_out;
+  A.rows_out = rows_out;
+  A.n = n;
+  A.chunk = chunk;
+  A.is64 = id_bytes == 8;
+  A.dim = dim;
+  return on_device("fcp_table_delta_distinct", device, stream, [&](hipStream_t s) {
+    const dim3 threads(kDeltaThreads);
+    if (n > 0) {
+      const unsigned clear_blocks = (unsigned)std::min<int64_t>(kDeltaClearBlocks, (cells + kDeltaThreads - 1) / kDeltaThreads);
+      hipLaunchKernelGGL(fcp_delta_clear_kernel, dim3(clear_blocks), threads, 0, s, T.cells, (uint64_t)cells);
+      hipLaunchKernelGGL(fcp_delta_insert_kernel<kDeltaSlots>, dim3((unsigned)std::min<int64_t>(insert_tiles, kDeltaInsertMaxBlocks)), threads,
+                         0, s, T, row_ids, A.is64, n, (uint64_t)table_rows);
+      hipLaunchKernelGGL(fcp_delta_classify_kernel, dim3(nblocks), threads, 0, s, T, row_ids, A.is64, n, chunk, (uint64_t)table_rows, flags,
+                         partials);
+    }
+    hipLaunchKernelGGL(fcp_delta_fold_kernel, dim3(1), dim3(64), 0, s, partials, (int32_t)nblocks, n, report);
+    if (n == 0) return;
+    if (!rows) {
+      hipLaunchKernelGGL((fcp_delta_compact_kernel<0, 1>), dim3(nblocks), threads, 0, s, A);
+      return;
+    }
+    with_vec(vec, [&](auto v) {
+      with_group(group_of(dim, vec), [&](auto g) {
+        hipLaunchKernelGGL((fcp_delta_compact_kernel<decltype(v)::value, decltype(g)::value>), dim3(nblocks), threads, 0, s, A);
+      });
+    });
+  });
+}

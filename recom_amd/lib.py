@@ -141,6 +141,11 @@ class TableDigest(C.Structure):
     _fields_ = [("sum", C.c_uint64), ("rows", C.c_int64), ("skipped", C.c_int64), ("reserved", C.c_int64)]
 
 
+class TableDeltaReport(C.Structure):
+    """fcp_table_delta_report_t"""
+    _fields_ = [("n", C.c_int64), ("distinct", C.c_int64), ("duplicates", C.c_int64), ("skipped", C.c_int64)]
+
+
 class PrivateStreamsStats(C.Structure):
     """fcp_private_streams_stats_t"""
     _fields_ = [("supervised_stream", C.c_void_p), ("requests", C.c_int64), ("lane_requests", C.c_int64), ("evaluations", C.c_int64),
@@ -192,6 +197,7 @@ EXPORTS = [
     "fcp_table_audit_weighted", "fcp_table_count_ids",
     "fcp_plan_table_rows", "fcp_plan_traffic_bind", "fcp_plan_traffic_count",
     "fcp_table_digest_workspace_bytes", "fcp_table_digest", "fcp_table_digest_rows", "fcp_table_digest_host",
+    "fcp_table_delta_workspace_bytes", "fcp_table_delta_distinct",
 ]
 
 _lib = None
@@ -374,6 +380,11 @@ def load() -> C.CDLL:
                                             C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.fcp_table_digest_host.restype = C.c_uint64
         L.fcp_table_digest_host.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int64]
+    if hasattr(L, "fcp_table_delta_distinct"):
+        L.fcp_table_delta_workspace_bytes.restype = C.c_int64
+        L.fcp_table_delta_workspace_bytes.argtypes = [C.c_int64]
+        L.fcp_table_delta_distinct.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     if L.fcp_abi_version() != FCP_ABI_VERSION:
         raise ImportError("libfcp_hip.so ABI version mismatch; rebuild")
     _lib = L

@@ -8,7 +8,10 @@ by which the audit weighs its sums (``fcp_table_audit_weighted``); ``new_plan_co
 which ``Plan.traffic_bind`` / ``Plan.traffic_count`` (recom_amd/ops.py) fill from requests through the plan's own id path;
 and the digest of a table of any format — an order-free 64-bit sum of row hashes, on the device (``fcp_table_digest`` /
 ``fcp_table_digest_rows``, recom_amd/csrc/fcp_table_digest.hip) and from host memory (``fcp_table_digest_host``) — by which a
-deployment checks that a served table is, byte for byte, the table it should be, and keeps that check across ``update_rows``.
+deployment checks that a served table is, byte for byte, the table it should be, and keeps that check across ``update_rows``;
+and, for deltas that name a row more than once, the ids made distinct on the device with the last occurrence winning
+(``fcp_table_delta_distinct``, recom_amd/csrc/fcp_table_delta.hip), in front of ``update_rows`` and the digest bookkeeping, which
+both ask for distinct ids and do not check (``apply_delta``).
 
 Plans do not quantise; this does, once, at load time.  The value model is the header's (include/fcp_hip.h): float32 -> q8 is
 exactly the tensor ``quantized::embedding_bag_byte_prepack`` returns, q8 -> float32 is ``fma(code, scale, bias)`` rounded
@@ -527,3 +530,122 @@ def update_rows_tracked(table, row_ids, rows, digest: int, row0: int = 0, row_st
     torch.cuda.ExternalStream(stream, device=table.device).synchronize()
     before, after = _digests_of(outs)
     return (int(digest) - int(before.sum) + int(after.sum)) % (1 << 64)
+
+
+# ---- a delta's ids made distinct (fcp_table_delta_distinct) ---------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class DeltaReport:
+    """fcp_table_delta_report_t on the host; ``n == distinct + duplicates + skipped``."""
+    n: int             # ids handed over
+    distinct: int      # rows kept: one per distinct id inside the table
+    duplicates: int    # occurrences dropped because a later position names the same row
+    skipped: int       # ids outside [0, table_rows)
+
+
+def _report_of(report_t) -> DeltaReport:
+    return DeltaReport(*(int(v) for v in report_t.cpu().tolist()))
+
+
+def _delta_ids_of(torch, row_ids) -> int:
+    if row_ids.dtype not in (torch.int32, torch.int64) or row_ids.dim() != 1 or not row_ids.is_contiguous():
+        raise ValueError("row_ids is a contiguous int64 or int32 [n] tensor")
+    if not row_ids.is_cuda:
+        raise ValueError(f"row_ids: fcp_table_delta_distinct works device to device; the tensor is on {row_ids.device}")
+    return int(row_ids.shape[0])
+
+
+def delta_distinct_async(row_ids, rows=None, table_rows: Optional[int] = None, pos: bool = False, stream: Optional[int] = None):
+    """``fcp_table_delta_distinct`` enqueued on ``stream`` (torch's current stream of the device by default), nothing
+    synchronised: returns ``(ids, rows, report)`` — plus ``pos`` when asked — at their full length ``n``: the winners in front,
+    in ascending position, ``-1`` behind them in ``ids`` and ``pos``, rows behind them uninitialised; ``report`` is the int64
+    ``[4]`` device tensor ``(n, distinct, duplicates, skipped)``.  The padded ``(ids, rows)`` go straight into ``update_rows`` /
+    ``digest_rows`` on the same stream, which skip ``-1``.  Outputs and workspace are allocated as that stream's."""
+    import torch
+    n = _delta_ids_of(torch, row_ids)
+    if table_rows is None:
+        raise ValueError("table_rows= is needed: the rows of the table the delta is for")
+    dim = 0
+    if rows is not None:
+        if rows.dtype != torch.float32 or rows.dim() != 2 or not rows.is_contiguous():
+            raise ValueError("rows is a contiguous float32 [n, dim] tensor")
+        if rows.device != row_ids.device:
+            raise ValueError(f"row_ids is on {row_ids.device}, rows on {rows.device}")
+        if rows.shape[0] != n:
+            raise ValueError(f"rows has {rows.shape[0]} rows, row_ids names {n}")
+        dim = int(rows.shape[1])
+    L = _lib.load()
+    device = row_ids.device
+    need = int(L.fcp_table_delta_workspace_bytes(n))
+    if need < 0:
+        raise ValueError(f"row_ids names {n} ids; a delta stays below 2^32 - 3")
+    if stream is None:
+        stream = torch.cuda.current_stream(device).cuda_stream
+    with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device)):
+        ids_out = torch.empty((n,), dtype=torch.int64, device=device)
+        pos_out = torch.empty((n,), dtype=torch.int64, device=device) if pos else None
+        rows_out = torch.empty_like(rows) if rows is not None else None
+        report = torch.empty((C.sizeof(_lib.TableDeltaReport) // 8,), dtype=torch.int64, device=device)
+        workspace = torch.empty((need // 8,), dtype=torch.int64, device=device)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+    status = L.fcp_table_delta_distinct(ptr(row_ids), int(row_ids.element_size()), ptr(rows), dim, n, int(table_rows), ptr(ids_out),
+                                        ptr(rows_out), ptr(pos_out), ptr(report), ptr(workspace), device.index or 0, C.c_void_p(stream))
+    _lib.check(status, "fcp_table_delta_distinct")
+    return (ids_out, rows_out, report, pos_out) if pos else (ids_out, rows_out, report)
+
+
+def delta_distinct(row_ids, rows=None, table_rows: Optional[int] = None, pos: bool = False, stream: Optional[int] = None):
+    """``fcp_table_delta_distinct``: the delta ``(row_ids, rows)`` — int64 or int32 ids ``[n]`` and float32 rows ``[n, dim]`` on
+    the device, or ids alone — with every id inside ``[0, table_rows)`` kept ONCE, at its LAST position, the kept positions in
+    ascending order; rows are copied as bits.  Runs on ``stream`` (torch's current stream of the device by default),
+    synchronises it, and returns ``(ids[:m], rows[:m] or None, report)`` — plus ``pos[:m]``, the kept positions, when ``pos`` —
+    with ``report`` a ``DeltaReport``.  ``report.duplicates == 0`` and ``report.skipped == 0`` say the delta was distinct and
+    inside the table as it stood: it comes back byte for byte."""
+    import torch
+    out = delta_distinct_async(row_ids, rows, table_rows=table_rows, pos=pos, stream=stream)
+    if stream is None:
+        stream = torch.cuda.current_stream(row_ids.device).cuda_stream
+    torch.cuda.ExternalStream(stream, device=row_ids.device).synchronize()
+    report = _report_of(out[2])
+    m = report.distinct
+    head = (out[0][:m], out[1][:m] if out[1] is not None else None, report)
+    return head + (out[3][:m],) if pos else head
+
+
+def apply_delta(table, row_ids, rows, digest: Optional[int] = None, row0: int = 0, row_step: int = 1, skipped=None,
+                stream: Optional[int] = None):
+    """``update_rows`` for a delta whose ids may REPEAT, in every table format: ``delta_distinct_async``, then ``update_rows`` of
+    the padded outputs — the table ends up, byte for byte, as if the rows had been written one after the other in position
+    order.  With ``digest`` (that of the table before; ``row0`` / ``row_step`` as in ``digest``) the ``digest_rows`` bookkeeping
+    of ``update_rows_tracked`` runs around the update.  ``skipped``, an int64 device tensor of one element, is increased by the
+    delta's own ids outside the table (not by the ``-1`` padding).  All on ``stream``, one synchronise at the end.  Returns the
+    ``DeltaReport``, or ``(report, new digest)`` when ``digest`` was given."""
+    import torch
+    name, dim = _kind_and_dim(table, "table")
+    n = _delta_ids_of(torch, row_ids)
+    if row_ids.device != table.device:
+        raise ValueError(f"table is on {table.device}, row_ids on {row_ids.device}")
+    _rows_of(torch, table, dim, n, rows, "rows")
+    if skipped is not None:
+        if skipped.dtype != torch.int64 or skipped.numel() != 1 or skipped.device != table.device:
+            raise ValueError("skipped is an int64 tensor of one element on the table's device")
+    L = _lib.load()
+    if stream is None:
+        stream = torch.cuda.current_stream(table.device).cuda_stream
+    ids_d, rows_d, report_t = delta_distinct_async(row_ids, rows, table_rows=int(table.shape[0]), stream=stream)
+    if digest is not None:
+        outs, workspace = _digest_buffers(torch, L, table.device, stream, n_out=2)
+        size = C.sizeof(_lib.TableDigest)
+        _enqueue_digest_rows(L, table, name, dim, ids_d, n, row0, row_step, outs.data_ptr(), workspace, stream)
+    update_rows(table, ids_d, rows_d, stream=stream)      # (its own skipped counter would count the padding too)
+    if digest is not None:
+        _enqueue_digest_rows(L, table, name, dim, ids_d, n, row0, row_step, outs.data_ptr() + size, workspace, stream)
+    ext = torch.cuda.ExternalStream(stream, device=table.device)
+    if skipped is not None:
+        with torch.cuda.stream(ext):
+            skipped.view(-1).add_(report_t[3:4])
+    ext.synchronize()
+    report = _report_of(report_t)
+    if digest is None:
+        return report
+    before, after = _digests_of(outs)
+    return report, (int(digest) - int(before.sum) + int(after.sum)) % (1 << 64)
