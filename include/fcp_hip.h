@@ -818,6 +818,75 @@ int fcp_table_digest_rows(const void *table, int32_t kind, int64_t table_rows, i
  * it never touches a device.  Rows may start at any byte.  Returns 0 for invalid arguments (those of fcp_table_digest without
  * out and workspace), which is also the digest of no rows. */
 uint64_t fcp_table_digest_host(const void *first_row, int32_t kind, int64_t rows, int32_t dim, int64_t row0, int64_t row_step);
+/* ---- outputs compare: what two requests' outputs differ by, per column ------------------------------------------------------- */
+/* The audits predict what a table ROW loses in a format.  fcp_outputs_compare measures what a request's OUTPUT lost: two plans —
+ * float32 tables and the formats fcp_table_formats_choose picked, a plan before and after a delta, two kernel variants — serve
+ * the same request into two arenas, and this one call, in stream order behind them, leaves one record per column and one for
+ * all columns together.  It answers: which column moved and by how much, is the output bit for bit what it was, does it hold
+ * NaN or +-inf.  In pooled columns the errors of a bag's rows add up or cancel, and a narrow output rounds once more: neither
+ * shows in an audit.
+ *
+ * `ptrs_*`, `row_strides_*` (in elements) and `shapes` (rows, dim per column) are HOST arrays of n_columns entries (shapes: 2 *
+ * n_columns), exactly what fcp_process_result_t carries as output_ptrs, output_row_strides and output_shapes: a side's columns
+ * may lie in a concat matrix (stride = the group's width) or in the per-column layout (stride = dim), the two sides may differ
+ * in strides, layout and element kind, and they share `shapes`.  out_kind_* is FCP_OUT_F32, FCP_OUT_BF16 or FCP_OUT_F16, the
+ * element kind of that side's plan; all nine pairs are served.  The arrays are read before the call returns and may be freed
+ * then.  A side that is the result of a private-stream request is waited for on `stream`, as fcp_concat_outputs does.
+ *
+ * Value model.  A 16-bit element is widened to float32 exactly (as the plans read 16-bit tables).  For a pair (a, b) of
+ * column k — element (row, j) of side A and of side B:
+ *   differ     the float32 bit patterns differ: +0 against -0 differs, a NaN against the same NaN does not;
+ *   finite     neither a nor b is NaN or +-inf.  A non-finite pair counts in `nonfinite` (and in `differ` and
+ *              first_differ_row if its patterns differ) and enters no sum and no maximum, so no field is ever NaN;
+ *   e = b - a  ONE float32 subtraction (it may overflow to +-inf: max_abs_err and sum_sq_err are then +inf); (double)e * e
+ *              and (double)a * a are exact, each is added to its float64 sum by one fused multiply-add; |e| and |a| join
+ *              float32 maxima.
+ * Denormals are kept, every operation rounds once.  The sums' order is fixed by (shapes, n_columns, the alignment of strides
+ * and pointers); there is no atomic operation, and two calls on the same input leave the same bytes in `out`.  A float64 sum
+ * of n non-negative terms lies within n * 2^-53 of the exact sum, relative, in any order.
+ *
+ * out[k], k < n_columns, is column k's record; out[n_columns] is the record of all columns together: counts and sums of the
+ * column records folded in one fixed order (a function of n_columns alone), the maxima joined, first_differ_row the smallest
+ * of the columns'.  A column with rows == 0 gets zeros with first_differ_row -1; n_columns == 0 writes that one record.
+ * `out` (n_columns + 1 records) and `workspace` (fcp_outputs_compare_workspace_bytes of n_columns bytes; its content before
+ * and after the call means nothing) are on the device, 8-byte aligned.  Asynchronous on `stream` (a hipStream_t), no
+ * allocation on the device, no synchronisation: `out` is read after the stream has reached the call's end.  Both arenas are
+ * only read.  Concurrent calls with workspaces of their own are allowed.
+ *
+ * The workspace size depends on n_columns alone: a multiple of 8, non-decreasing, -1 for a negative argument.
+ *
+ * Stream capture: a call with n_columns > 0 installs its column descriptors from the host (a pinned ring and an upload kernel,
+ * as the request path installs shapes that are not resident), which a replay would not repeat: FCP_ERR_UNSUPPORTED while
+ * `stream` is capturing.  n_columns == 0 installs nothing and may be captured.
+ *
+ * Status, decided in this order (none of the first group needs a device or dereferences a column pointer):
+ *   FCP_ERR_INVALID_ARGUMENT  with n_columns != 0, a null ptrs_a, row_strides_a, ptrs_b, row_strides_b or shapes (in this
+ *                             order); an out_kind_a, then an out_kind_b, that is no FCP_OUT_* kind; n_columns < 0; then, each
+ *                             over the columns in ascending order: negative rows or dim <= 0; a row_strides_a, then a
+ *                             row_strides_b, below dim; a null ptrs_a[k], then ptrs_b[k], where rows > 0; a ptrs_a[k], then
+ *                             ptrs_b[k], not aligned to its element size; then a null out, a null workspace, a misaligned
+ *                             out, a misaligned workspace.  (rows at or above 2^32 - 3, the plans' row limit, would follow:
+ *                             int32 shapes cannot hold such a value.)  fcp_last_error names the argument between backquotes
+ *                             and, for the per-column conditions, the column;
+ *   FCP_ERR_NO_DEVICE         no usable gfx950 device (n_columns == 0 included: `out` is written on the device);
+ *   FCP_ERR_UNSUPPORTED       n_columns > 0 on a capturing stream — the only case;
+ *   FCP_ERR_HIP               a runtime call or a kernel launch failed. */
+typedef struct fcp_output_error {
+  int64_t elems;            /* rows * dim pairs of this column */
+  int64_t differ;           /* pairs whose float32 bit patterns (after exact widening of 16-bit elements) differ */
+  int64_t nonfinite;        /* pairs in which a or b is NaN or +-inf: they enter no sum and no maximum */
+  int64_t first_differ_row; /* smallest row holding a differing pair, -1: none */
+  double sum_sq_ref;        /* sum of a*a over the finite pairs */
+  double sum_sq_err;        /* sum of e*e, e = b - a in float32 (one rounding), over the finite pairs */
+  float max_abs_err;        /* largest |e| over the finite pairs, 0 if none */
+  float max_abs_ref;        /* largest |a| over the finite pairs, 0 if none */
+  int64_t reserved;         /* 0 */
+} fcp_output_error_t; /* 64 bytes */
+int64_t fcp_outputs_compare_workspace_bytes(int32_t n_columns);
+int fcp_outputs_compare(const void *const *ptrs_a, const int64_t *row_strides_a, int32_t out_kind_a, const void *const *ptrs_b,
+                        const int64_t *row_strides_b, int32_t out_kind_b,
+                        const int32_t *shapes /* host int32[2*n_columns]: rows, dim */, int32_t n_columns,
+                        fcp_output_error_t *out /* device [n_columns + 1] */, void *workspace, int32_t device, void *stream);
 /* ---- placement gate (replaces check_table_size, cuda_emitter.cc:1080-1094) -------- */
 /* The reference keeps a column on the CPU when its table exceeds max_table_size =
  * 256 MiB (fc_optimize_pass.cc:71, RECOM_CPU_GPU_CO_RUN).  On MI355X the question is

@@ -146,6 +146,13 @@ class TableDeltaReport(C.Structure):
     _fields_ = [("n", C.c_int64), ("distinct", C.c_int64), ("duplicates", C.c_int64), ("skipped", C.c_int64)]
 
 
+class OutputError(C.Structure):
+    """fcp_output_error_t"""
+    _fields_ = [("elems", C.c_int64), ("differ", C.c_int64), ("nonfinite", C.c_int64), ("first_differ_row", C.c_int64),
+                ("sum_sq_ref", C.c_double), ("sum_sq_err", C.c_double), ("max_abs_err", C.c_float), ("max_abs_ref", C.c_float),
+                ("reserved", C.c_int64)]
+
+
 class PrivateStreamsStats(C.Structure):
     """fcp_private_streams_stats_t"""
     _fields_ = [("supervised_stream", C.c_void_p), ("requests", C.c_int64), ("lane_requests", C.c_int64), ("evaluations", C.c_int64),
@@ -198,6 +205,7 @@ EXPORTS = [
     "fcp_plan_table_rows", "fcp_plan_traffic_bind", "fcp_plan_traffic_count",
     "fcp_table_digest_workspace_bytes", "fcp_table_digest", "fcp_table_digest_rows", "fcp_table_digest_host",
     "fcp_table_delta_workspace_bytes", "fcp_table_delta_distinct",
+    "fcp_outputs_compare_workspace_bytes", "fcp_outputs_compare",
 ]
 
 _lib = None
@@ -385,6 +393,11 @@ def load() -> C.CDLL:
         L.fcp_table_delta_workspace_bytes.argtypes = [C.c_int64]
         L.fcp_table_delta_distinct.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    if hasattr(L, "fcp_outputs_compare"):
+        L.fcp_outputs_compare_workspace_bytes.restype = C.c_int64
+        L.fcp_outputs_compare_workspace_bytes.argtypes = [C.c_int32]
+        L.fcp_outputs_compare.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     if L.fcp_abi_version() != FCP_ABI_VERSION:
         raise ImportError("libfcp_hip.so ABI version mismatch; rebuild")
     _lib = L

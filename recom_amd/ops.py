@@ -466,6 +466,98 @@ def _typed_arena(torch, arena, dtype):
     return arena[:arena.numel() // 2 * 2].view(dtype)
 
 
+# ----------------------------------------------------------------------------
+# fcp_outputs_compare: what two requests' outputs differ by, per column
+# ----------------------------------------------------------------------------
+OUTPUT_ERROR_DTYPE = np.dtype([("elems", "<i8"), ("differ", "<i8"), ("nonfinite", "<i8"), ("first_differ_row", "<i8"),
+                               ("sum_sq_ref", "<f8"), ("sum_sq_err", "<f8"), ("max_abs_err", "<f4"), ("max_abs_ref", "<f4"),
+                               ("reserved", "<i8")])   # fcp_output_error_t, 64 bytes
+
+_compare_workspaces: dict = {}   # (device index, stream) -> torch.int64 workspace: calls on one stream run one after the other
+
+
+@dataclass
+class OutputErrors:
+    """``fcp_outputs_compare``'s records on the host: ``columns[k]`` is column k's, ``total`` that of all columns together
+    (a NumPy record array of ``OUTPUT_ERROR_DTYPE`` and one record of it: fields by name or as attributes)."""
+    columns: np.ndarray
+    total: np.record
+
+    def rel_rms(self, k: Optional[int] = None) -> float:
+        """sqrt(sum_sq_err / sum_sq_ref) of column ``k``, or of all columns together for ``None``; 0.0 where both sums are 0."""
+        r = self.total if k is None else self.columns[k]
+        if r["sum_sq_ref"] == 0.0:
+            return 0.0 if r["sum_sq_err"] == 0.0 else float("inf")
+        return float(np.sqrt(r["sum_sq_err"] / r["sum_sq_ref"]))
+
+    @property
+    def identical(self) -> bool:
+        """Every pair of elements has the same bit pattern."""
+        return int(self.total["differ"]) == 0
+
+
+def _out_kind(torch, outputs: ProcessOutputs) -> int:
+    dtype = outputs.groups[0].dtype if outputs.groups else torch.float32
+    return {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}[dtype]   # FCP_OUT_*
+
+
+def _same_request(a: ProcessOutputs, b: ProcessOutputs) -> np.ndarray:
+    """the output_shapes the two results share, or ValueError"""
+    sa, sb = np.asarray(a.output_shapes, np.int32), np.asarray(b.output_shapes, np.int32)
+    if sa.size != sb.size:
+        raise ValueError(f"compare_outputs: {sa.size // 2} columns against {sb.size // 2}")
+    if not np.array_equal(sa, sb):
+        k = int(np.flatnonzero(sa != sb)[0]) // 2
+        raise ValueError(f"compare_outputs: column {k} is [{sa[2 * k]}, {sa[2 * k + 1]}] in a and [{sb[2 * k]}, {sb[2 * k + 1]}] in b: "
+                         "the two results are not of the same request")
+    return sa
+
+
+def compare_outputs_async(a: ProcessOutputs, b: ProcessOutputs, stream: Optional[int] = None):
+    """``fcp_outputs_compare`` of two results of the SAME request (two plans, two arenas), enqueued on ``stream`` (default:
+    torch's current stream of ``a``'s device) behind whatever wrote them there: returns a device tensor ``[n_columns + 1, 8]``
+    of int64 words — one 64-byte ``fcp_output_error_t`` per column, then the one of all columns together — that is valid once
+    the stream has reached this point (``OutputErrors`` of it: ``compare_outputs``).  Nothing blocks.  Each side's element kind
+    is that of its ``groups[0]`` (float32 for a per-column result); layouts, strides and kinds of the two may differ, their
+    ``output_shapes`` must be equal (``ValueError`` naming the first column that differs)."""
+    import torch
+    sa = _same_request(a, b)
+    n = sa.size // 2
+    device = a.buffer.device
+    if b.buffer.device != device:
+        raise ValueError(f"compare_outputs: a lies on {device}, b on {b.buffer.device}")
+    L = _lib.load()
+    if stream is None:
+        stream = torch.cuda.current_stream(device).cuda_stream
+    need = int(L.fcp_outputs_compare_workspace_bytes(n))
+    key = (device.index or 0, int(stream))
+    with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device)):
+        out = torch.empty((n + 1, OUTPUT_ERROR_DTYPE.itemsize // 8), dtype=torch.int64, device=device)
+        workspace = _compare_workspaces.get(key)
+        if workspace is None or workspace.numel() * 8 < need:
+            workspace = _compare_workspaces[key] = torch.empty((need // 8,), dtype=torch.int64, device=device)
+    pa, pb = np.ascontiguousarray(a.output_ptrs, np.int64), np.ascontiguousarray(b.output_ptrs, np.int64)
+    ta, tb = np.ascontiguousarray(a.output_row_strides, np.int64), np.ascontiguousarray(b.output_row_strides, np.int64)
+    shapes = np.ascontiguousarray(sa)
+    status = L.fcp_outputs_compare(pa.ctypes.data, ta.ctypes.data, _out_kind(torch, a), pb.ctypes.data, tb.ctypes.data,
+                                   _out_kind(torch, b), shapes.ctypes.data, n, out.data_ptr(), workspace.data_ptr(),
+                                   device.index or 0, C.c_void_p(stream))
+    _lib.check(status, "fcp_outputs_compare")
+    return out
+
+
+def compare_outputs(a: ProcessOutputs, b: ProcessOutputs, stream: Optional[int] = None) -> OutputErrors:
+    """``compare_outputs_async``, then a synchronise of ``stream`` and the records on the host."""
+    import torch
+    _same_request(a, b)
+    if stream is None:
+        stream = torch.cuda.current_stream(a.buffer.device).cuda_stream
+    out = compare_outputs_async(a, b, stream)
+    torch.cuda.ExternalStream(stream, device=a.buffer.device).synchronize()
+    records = np.frombuffer(out.cpu().numpy().tobytes(), OUTPUT_ERROR_DTYPE).copy().view(np.recarray)
+    return OutputErrors(records[:-1], records[-1])
+
+
 class FeatureColumnProcess:
     """``Addons>FeatureColumnProcess[WithSymbols]``.
 
