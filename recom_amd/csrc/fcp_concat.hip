@@ -38,30 +38,6 @@ int check_scatter_args(const void *const *inputs, const int32_t *dims, const int
   }
   return FCP_OK;
 }
-
-// Pinned staging for Addons>ConcatOutputs host inputs: a small ring per device, grown on demand.  A slot is
-// reused once the copy that read it has completed (its event), so the call never waits for the GPU in the
-// steady state and never hands pageable memory to an asynchronous copy.
-struct HostStageSlot {
-  char *buf = nullptr;
-  char *buf_dev = nullptr; // device mapping of buf
-  size_t cap = 0;
-  hipEvent_t copied = nullptr;
-  bool busy = false; // reserved by a call that is packing into it / enqueueing its reader (guarded by the ring mutex)
-};
-struct HostStageRing {
-  std::mutex mu; // covers `next` and the slots' `busy` flags only: callers pack and launch outside it
-  HostStageSlot slots[4];
-  size_t next = 0;
-};
-HostStageRing *host_stage_ring(int device) {
-  static std::mutex mu;
-  static std::vector<HostStageRing *> rings;
-  std::lock_guard<std::mutex> lock(mu);
-  if ((int)rings.size() <= device) rings.resize(device + 1, nullptr);
-  if (!rings[device]) rings[device] = new HostStageRing(); // lives as long as the process (pinned memory is freed at exit)
-  return rings[device];
-}
 } // namespace
 
 int fcp_concat_outputs_scatter_strided(const void *const *inputs, const int32_t *dims, const int32_t *in_strides,
@@ -108,47 +84,12 @@ int fcp_concat_outputs_host(const void *const *host_inputs, const int32_t *dims,
   // Large ones keep the H2D copy (the scatter would hold its CUs for the length of the PCIe transfer).
   const bool direct = total <= ((size_t)1 << 20);
   if (!direct && !malloc_temp) return fail(FCP_ERR_INVALID_ARGUMENT, "malloc_temp callback is required for payloads that are copied to the device");
-  HostStageRing *ring = host_stage_ring(device);
-  // Reserve a slot under the ring lock, then pack (the reference: one memcpy per input into a std::vector,
-  // concat_outputs_op_gpu.cu.cc:195-201), wait for the slot's previous reader if it is still running, and enqueue
-  // OUTSIDE it: concurrent serve workers (models E / F) only meet on the bookkeeping.
-  HostStageSlot *slp = nullptr;
-  for (;;) {
-    {
-      std::lock_guard<std::mutex> lock(ring->mu);
-      for (int t = 0; t < 4 && !slp; ++t) {
-        HostStageSlot &c = ring->slots[(ring->next + t) % 4];
-        if (!c.busy) {
-          c.busy = true;
-          ring->next = (ring->next + t + 1) % 4;
-          slp = &c;
-        }
-      }
-    }
-    if (slp) break;
-    std::this_thread::yield(); // more than four calls in flight on this device
-  }
-  HostStageSlot &sl = *slp;
-  struct Release {
-    HostStageRing *r;
-    HostStageSlot *s;
-    ~Release() {
-      std::lock_guard<std::mutex> lock(r->mu);
-      s->busy = false;
-    }
-  } release{ring, slp};
-  if (sl.copied && hipEventQuery(sl.copied) != hipSuccess) HIP_TRY(hipEventSynchronize(sl.copied));
-  if (sl.cap < total) {
-    if (sl.buf) HIP_TRY(hipHostFree(sl.buf));
-    sl.buf = nullptr;
-    sl.buf_dev = nullptr;
-    sl.cap = 0;
-    const size_t cap = std::max<size_t>(total, 1 << 16);
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sl.buf), cap, hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&sl.buf_dev), sl.buf, 0));
-    sl.cap = cap;
-  }
-  if (!sl.copied) HIP_TRY(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
+  // Reserve a slot of this entry's pinned ring (StageRings, fcp_host.h), then pack (the reference: one memcpy per input into a
+  // std::vector, concat_outputs_op_gpu.cu.cc:195-201) and enqueue OUTSIDE its lock: concurrent serve workers (models E / F)
+  // only meet on the bookkeeping, and no pageable memory is handed to an asynchronous copy.
+  static StageRings rings;
+  StageRings::Lease sl;
+  if ((rc = rings.acquire(device, total, &sl))) return rc;
   for (int32_t k = 0; k < n; ++k) std::memcpy(sl.buf + at[k], host_inputs[k], (size_t)prefix_size * dims[k] * 4);
   const char *src = sl.buf_dev;
   if (!direct) {
@@ -163,8 +104,7 @@ int fcp_concat_outputs_host(const void *const *host_inputs, const int32_t *dims,
   for (int32_t k = 0; k < n; ++k) d_in[k] = src + at[k];
   const int e = fcp_launch_concat_outputs(d_in.data(), dims, col_offsets, nullptr, n, prefix_size, out_width, 0, out, stream);
   if (e) return hip_fail("concat-outputs launch", (hipError_t)e);
-  HIP_TRY(hipEventRecord(sl.copied, stream)); // the slot is free once its last reader (copy or scatter) has run
-  return FCP_OK;
+  return sl.record(stream); // the slot is free once its last reader (copy or scatter) has run
 }
 
 // ---- row-shard finalize -------------------------------------------------------------

@@ -400,6 +400,86 @@ template <class F> int on_device(const char *who, int32_t device, void *stream, 
   return e == hipSuccess ? FCP_OK : hip_fail((std::string(who) + ": kernel launch").c_str(), e);
 }
 
+// Pinned, mapped staging that an entry fills on the host and a kernel (or a copy) of its stream reads: a ring of four slots per
+// device, each grown on demand from a 64 KiB floor.  A slot is free again once the reader that was enqueued behind it has run
+// (its event, recorded by Lease::record), so the caller's host arrays may go as soon as the call returns and the call never
+// waits for the GPU in the steady state.  The TYPE is shared; every entry that stages keeps an object of its own, so the calls
+// in flight that one entry admits do not depend on another's (fcp_concat_outputs_host, fcp_outputs_compare).
+struct StageRings {
+  struct Slot {
+    char *buf = nullptr, *buf_dev = nullptr; // buf_dev: the device mapping of buf
+    size_t cap = 0;
+    hipEvent_t read = nullptr;
+    bool busy = false; // reserved by a call that is filling it / enqueueing its reader (under the ring's mutex)
+  };
+  struct Ring {
+    std::mutex mu; // covers `next` and the slots' `busy` flags only: callers fill and launch outside it
+    Slot slots[4];
+    size_t next = 0;
+  };
+  // A reserved slot; gives it back when it goes.
+  struct Lease {
+    char *buf = nullptr, *buf_dev = nullptr;
+    Ring *ring = nullptr;
+    Slot *slot = nullptr;
+    // behind the slot's last reader on `stream`: the slot is free once that has run
+    int record(hipStream_t stream) {
+      HIP_TRY(hipEventRecord(slot->read, stream));
+      return FCP_OK;
+    }
+    ~Lease() {
+      if (!slot) return;
+      std::lock_guard<std::mutex> lock(ring->mu);
+      slot->busy = false;
+    }
+  };
+  std::mutex mu;
+  std::vector<Ring *> rings; // by device; a ring lives as long as the process (pinned memory is freed at exit)
+
+  // Reserve a slot of `device`'s ring (yielding while all four are taken), wait for its previous reader if that is still
+  // running, and make it hold `bytes`.  The caller has entered the device.
+  int acquire(int device, size_t bytes, Lease *lease) {
+    {
+      std::lock_guard<std::mutex> lock(mu);
+      if ((int)rings.size() <= device) rings.resize(device + 1, nullptr);
+      if (!rings[device]) rings[device] = new Ring();
+      lease->ring = rings[device];
+    }
+    Ring *ring = lease->ring;
+    for (;;) {
+      {
+        std::lock_guard<std::mutex> lock(ring->mu);
+        for (int t = 0; t < 4 && !lease->slot; ++t) {
+          Slot &c = ring->slots[(ring->next + t) % 4];
+          if (!c.busy) {
+            c.busy = true;
+            ring->next = (ring->next + t + 1) % 4;
+            lease->slot = &c;
+          }
+        }
+      }
+      if (lease->slot) break;
+      std::this_thread::yield(); // more than four calls in flight on this device
+    }
+    Slot &sl = *lease->slot;
+    if (sl.read && hipEventQuery(sl.read) != hipSuccess) HIP_TRY(hipEventSynchronize(sl.read));
+    if (sl.cap < bytes) {
+      if (sl.buf) HIP_TRY(hipHostFree(sl.buf));
+      sl.buf = nullptr;
+      sl.buf_dev = nullptr;
+      sl.cap = 0;
+      const size_t cap = std::max<size_t>(bytes, 1 << 16);
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sl.buf), cap, hipHostMallocMapped));
+      HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&sl.buf_dev), sl.buf, 0));
+      sl.cap = cap;
+    }
+    if (!sl.read) HIP_TRY(hipEventCreateWithFlags(&sl.read, hipEventDisableTiming));
+    lease->buf = sl.buf;
+    lease->buf_dev = sl.buf_dev;
+    return FCP_OK;
+  }
+};
+
 // ---- functions that cross translation units -----------------------------------------------------------------------
 // fcp_plan.hip
 int compute_dyn(const fcp_plan *p, const int32_t *offsets, const int32_t *shapes, const int32_t *symbols, int64_t blob_bytes,

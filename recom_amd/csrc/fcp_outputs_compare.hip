@@ -57,6 +57,8 @@
 
 #pragma clang fp contract(off)
 
+#include "fcp_block_fold.h" // wave_fold, block_fold, kNoSuchRow: the fold of a lane's record into the block's, in one fixed order
+
 static_assert(FCP_OUT_BF16 == FCP_TAB_BF16 && FCP_OUT_F16 == FCP_TAB_F16, "widen16 takes FCP_TAB_*: the output kinds carry the same numbers");
 static_assert(sizeof(fcp_output_error_t) == 64, "fcp_output_error_t is 64 bytes");
 static_assert((int64_t)INT32_MAX < fcpf::kRowLimit, "shapes are int32: rows stay below the row limit by their type");
@@ -65,7 +67,6 @@ namespace {
 
 constexpr int kTargetBlocks = 4096; // what the grid aims at: 16 blocks of 256 threads for each of 256 CUs
 constexpr int kMaxTiles = 64;       // T's upper end: a one-column call is 64 blocks
-constexpr uint32_t kNoSuchRow = 0xFFFFFFFFu; // rows < 2^31: a row index fits 32 bits, and this is none
 
 // tiles per column: a function of n_columns alone
 int tiles_of(int32_t n) { return n <= 0 ? 1 : std::min(kMaxTiles, std::max(1, (kTargetBlocks + n - 1) / n)); }
@@ -115,22 +116,6 @@ __device__ __forceinline__ CmpPartial nothing_seen() {
   p.max_err = p.max_ref = 0.0f;
   p.pad = 0;
   return p;
-}
-
-// the 64 lanes of a wave into every lane: one fixed order
-__device__ __forceinline__ void wave_fold(CmpPartial &p) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    CmpPartial o;
-    o.sum_sq_ref = __shfl_xor(p.sum_sq_ref, m, 64);
-    o.sum_sq_err = __shfl_xor(p.sum_sq_err, m, 64);
-    o.differ = __shfl_xor(p.differ, m, 64);
-    o.nonfinite = __shfl_xor(p.nonfinite, m, 64);
-    o.first_differ = __shfl_xor(p.first_differ, m, 64);
-    o.max_err = __shfl_xor(p.max_err, m, 64);
-    o.max_ref = __shfl_xor(p.max_ref, m, 64);
-    fold(p, o);
-  }
 }
 
 // V elements of kind K at byte address p (V elements aligned), widened exactly
@@ -223,15 +208,7 @@ __global__ void __launch_bounds__(FCP_BLOCK_THREADS) fcp_outputs_compare_kernel(
   p.max_err = __uint_as_float(s.max_err);
   p.max_ref = __uint_as_float(s.max_ref);
   p.pad = 0;
-  wave_fold(p);
-  __shared__ CmpPartial s_wave[FCP_BLOCK_THREADS / 64];
-  const int tid = threadIdx.x;
-  if ((tid & 63) == 0) s_wave[tid / 64] = p;
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < FCP_BLOCK_THREADS / 64; ++w) fold(p, s_wave[w]);
-    partials[blockIdx.x] = p;
-  }
+  block_fold(p, partials);
 }
 
 __device__ __forceinline__ void write_record(fcp_output_error_t *out, int64_t elems, const CmpPartial &p) {
@@ -345,29 +322,6 @@ int check_args(const void *const *ptrs_a, const int64_t *row_strides_a, int32_t 
   return FCP_OK;
 }
 
-// Pinned, mapped staging for the descriptor image: a small ring per device, grown on demand, as fcp_concat_outputs_host keeps
-// one for its inputs.  A slot is free again once the upload kernel that read it has run (its event), so the host arrays of a
-// call may go as soon as it returns and the call never waits for the GPU in the steady state.
-struct DescSlot {
-  char *buf = nullptr, *buf_dev = nullptr;
-  size_t cap = 0;
-  hipEvent_t read = nullptr;
-  bool busy = false; // reserved by a call that is filling it / enqueueing its reader (under the ring's mutex)
-};
-struct DescRing {
-  std::mutex mu; // covers `next` and the slots' `busy` flags only
-  DescSlot slots[4];
-  size_t next = 0;
-};
-DescRing *desc_ring(int device) {
-  static std::mutex mu;
-  static std::vector<DescRing *> rings;
-  std::lock_guard<std::mutex> lock(mu);
-  if ((int)rings.size() <= device) rings.resize(device + 1, nullptr);
-  if (!rings[device]) rings[device] = new DescRing(); // lives as long as the process
-  return rings[device];
-}
-
 // the widest V every address of the column is aligned for, on both sides
 int vec_of_column(const CmpColumn &c, int ea, int eb) {
   int v = 4;
@@ -411,44 +365,10 @@ extern "C" int fcp_outputs_compare(const void *const *ptrs_a, const int64_t *row
   CmpColumn *d_cols = reinterpret_cast<CmpColumn *>(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
   CmpPartial *d_partials = reinterpret_cast<CmpPartial *>(reinterpret_cast<char *>(d_cols) + image_bytes);
 
-  DescRing *ring = desc_ring(device);
-  DescSlot *slp = nullptr;
-  for (;;) {
-    {
-      std::lock_guard<std::mutex> lock(ring->mu);
-      for (int t = 0; t < 4 && !slp; ++t) {
-        DescSlot &c = ring->slots[(ring->next + t) % 4];
-        if (!c.busy) {
-          c.busy = true;
-          ring->next = (ring->next + t + 1) % 4;
-          slp = &c;
-        }
-      }
-    }
-    if (slp) break;
-    std::this_thread::yield(); // more than four calls in flight on this device
-  }
-  DescSlot &sl = *slp;
-  struct Release {
-    DescRing *r;
-    DescSlot *s;
-    ~Release() {
-      std::lock_guard<std::mutex> lock(r->mu);
-      s->busy = false;
-    }
-  } release{ring, slp};
-  if (sl.read && hipEventQuery(sl.read) != hipSuccess) HIP_TRY(hipEventSynchronize(sl.read));
-  if (sl.cap < image_bytes) {
-    if (sl.buf) HIP_TRY(hipHostFree(sl.buf));
-    sl.buf = nullptr;
-    sl.buf_dev = nullptr;
-    sl.cap = 0;
-    const size_t cap = std::max<size_t>(image_bytes, 1 << 16);
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sl.buf), cap, hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&sl.buf_dev), sl.buf, 0));
-    sl.cap = cap;
-  }
-  if (!sl.read) HIP_TRY(hipEventCreateWithFlags(&sl.read, hipEventDisableTiming));
+  // the descriptor image goes through a slot of this entry's pinned ring (StageRings, fcp_host.h)
+  static StageRings rings;
+  StageRings::Lease sl;
+  if ((rc = rings.acquire(device, image_bytes, &sl))) return rc;
   const int ea = elem_bytes(out_kind_a), eb = elem_bytes(out_kind_b);
   CmpColumn *h = reinterpret_cast<CmpColumn *>(sl.buf);
   for (int32_t k = 0; k < n_columns; ++k) {
@@ -467,7 +387,7 @@ extern "C" int fcp_outputs_compare(const void *const *ptrs_a, const int64_t *row
   __atomic_thread_fence(__ATOMIC_SEQ_CST); // the image is in memory before the launch that reads it is queued
   const int e = fcp_launch_upload(sl.buf_dev, d_cols, image_bytes, stream);
   if (e) return hip_fail("fcp_outputs_compare: descriptor upload launch", (hipError_t)e);
-  HIP_TRY(hipEventRecord(sl.read, stream)); // the slot is free once the upload has run
+  if ((rc = sl.record(stream))) return rc; // the slot is free once the upload has run
   launch_compare(out_kind_a, out_kind_b, dim3((unsigned)((int64_t)n_columns * T)), stream, d_cols, (int32_t)T, d_partials);
   hipLaunchKernelGGL(fcp_outputs_compare_fold_kernel, dim3((unsigned)((n_columns + 63) / 64)), dim3(64), 0, stream, d_cols, d_partials,
                      n_columns, (int32_t)T, out);

@@ -39,13 +39,13 @@
 #pragma clang fp contract(off)
 
 #include "fcp_table_walk.h" // (behind the pragma: its code rounds every operation once, too)
+#include "fcp_block_fold.h" // wave_fold, block_fold, kNoSuchRow: the fold of a lane's record into the block's, in one fixed order
 
 static_assert(FCP_TAB_BF16 == 1 && FCP_TAB_F16 == 2 && FCP_TAB_Q8 == 3, "the audit's kind index k is FCP_TAB_* - 1");
 
 namespace {
 
 constexpr int kAuditBlocks = 2048;   // the fixed grid: 8 blocks of 256 threads on each of 256 CUs; also the records of the workspace
-constexpr uint32_t kNoSuchRow = 0xFFFFFFFFu; // rows < 2^32 - 3: a row index fits 32 bits, and this is none
 
 // What a lane, a wave, a block and the whole call have seen; k = FCP_TAB_* - 1.  96 bytes, 8-byte aligned.
 struct AuditPartial {
@@ -147,25 +147,6 @@ __device__ __forceinline__ AuditPartial nothing_seen() {
   return p;
 }
 
-// the 64 lanes of a wave into every lane: one fixed order
-__device__ __forceinline__ void wave_fold(AuditPartial &p) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    AuditPartial o;
-    o.sum_sq = __shfl_xor(p.sum_sq, m, 64);
-    o.nonfinite = __shfl_xor(p.nonfinite, m, 64);
-    o.first_nonfinite = __shfl_xor(p.first_nonfinite, m, 64);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      o.sse[k] = __shfl_xor(p.sse[k], m, 64);
-      o.bad[k] = __shfl_xor(p.bad[k], m, 64);
-      o.first_bad[k] = __shfl_xor(p.first_bad[k], m, 64);
-      o.max_err[k] = __shfl_xor(p.max_err[k], m, 64);
-    }
-    fold(p, o);
-  }
-}
-
 // src: the table's base; rows: all of them (< 2^32 - 3).  Block = 256 / G rows per step of the stride loop; a group never
 // straddles a wave, and it is live or not as a whole — lanes of rows beyond the end take part in the butterflies and touch no
 // memory.  Every thread of a block takes the same number of steps.
@@ -234,14 +215,7 @@ __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
     p.max_err[k] = __uint_as_float(a.max_err[k]);
   }
   p.pad = 0;
-  wave_fold(p);
-  __shared__ AuditPartial s_wave[FCP_BLOCK_THREADS / 64];
-  if ((tid & 63) == 0) s_wave[tid / 64] = p;
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < FCP_BLOCK_THREADS / 64; ++w) fold(p, s_wave[w]);
-    partials[blockIdx.x] = p;
-  }
+  block_fold(p, partials);
 }
 
 // one wave; n: records of the workspace the first kernel wrote (0: it was not launched)

@@ -16,13 +16,12 @@
 //                     and compared unsigned against table_rows; an id outside touches nothing.  insert_global: walk from the
 //                     home cell, claim an empty cell's key with a compare-and-swap (a key never changes once claimed, so a
 //                     relaxed load that sees a stale EMPTY only costs the compare-and-swap that tells the truth), then
-//                     atomicMax(pos1, i + 1).  SLOTS > 0: the block first resolves its share in LDS — count_row's scheme
-//                     (fcp_table_traffic.hip) with max in place of add: SLOTS {row, pos1} cells, home row mod SLOTS,
-//                     kDeltaProbes probes, else straight to insert_global — and flushes one insert_global per occupied
-//                     cell: a row that every position names costs one global atomic per block, not one per position.
-//                     SLOTS == 0 (-DFCP_DELTA_SLOTS=0): one insert_global per position — built for the measurement only: it
-//                     is as fast on distinct ids and 7x (Zipf) to 260x (one row) slower on repeated ones
-//                     (profiles/table_delta.txt).
+//                     atomicMax(pos1, i + 1).  The block first resolves its share in LDS — the row table of
+//                     fcp_block_fold.h, SLOTS {row, pos1} cells, an LDS max on a claimed cell, a row without one straight
+//                     to insert_global — and flushes one insert_global per occupied cell: a row that every position names
+//                     costs one global atomic per block, not one per position.  (One insert_global per position, no LDS, a
+//                     build of the commit that introduced the kernel, is as fast on distinct ids and 7x (Zipf) to 260x
+//                     (one row) slower on repeated ones: profiles/table_delta.txt)
 //   fcp_delta_classify_kernel   kDeltaBlocks blocks at the most, block b owns the contiguous chunk [b * chunk, (b + 1) * chunk) of
 //                     positions, chunk a multiple of kDeltaTile.  Position i with an id inside the table looks its row up (the
 //                     row is there: the insert phase has run) and WINS when the cell's pos1 is i + 1.  One flag byte per
@@ -44,14 +43,7 @@
 #pragma clang fp contract(off) // (fcp_table_walk.h's rule; nothing here is floating point)
 
 #include "fcp_table_walk.h" // vec_of, group_of, with_vec, with_group: the rows' V and G, the host's dispatch
-
-// Cells of a block's LDS table in fcp_delta_insert_kernel (a power of two; 2 x 8 KiB of LDS at 2048, for a tile of 1024
-// positions, as fcp_plan_traffic_kernel is sized).  -DFCP_DELTA_SLOTS=0 builds the plain kernel instead — one global claim and
-// max per position, no LDS — which the choice was measured against (scripts/table_delta_cost.py --variant,
-// profiles/table_delta.txt); the library is built with the default.
-#ifndef FCP_DELTA_SLOTS
-#define FCP_DELTA_SLOTS 2048
-#endif
+#include "fcp_block_fold.h" // wave_fold, block_fold; the block's LDS row table, kEmptyCell
 
 namespace {
 
@@ -63,15 +55,10 @@ constexpr int kDeltaInsertIdsPerThread = 4;
 constexpr int kDeltaInsertTile = kDeltaThreads * kDeltaInsertIdsPerThread;
 constexpr int kDeltaInsertMaxBlocks = 65535;        // longer deltas: the stride loop
 constexpr int kDeltaClearBlocks = 4096;
-constexpr int kDeltaSlots = FCP_DELTA_SLOTS;
-constexpr int kDeltaProbes = 4;                     // LDS cells a row looks at, from its home slot on
+constexpr int kDeltaSlots = 2048;                   // cells of a block's LDS table: 2 x 8 KiB, for a tile of 1024 positions
 constexpr int64_t kDeltaMinCells = 64;
 constexpr uint64_t kDeltaHashMul = 0x9E3779B97F4A7C15ull;
-constexpr uint32_t kEmptyCell = 0xFFFFFFFFu;        // table_rows < 2^32 - 3: a row index fits 32 bits, and this is none
 static_assert(kDeltaThreads == 256, "four waves per block: the compact kernel's scan of wave counts");
-static_assert((kDeltaSlots & (kDeltaSlots - 1)) == 0 && kDeltaSlots % kDeltaThreads == 0, "slot masks and the flush loop");
-
-typedef __attribute__((address_space(3))) uint32_t LdsU32;
 
 // What a block of the classify phase counted, and, once the fold has run, where its winners go.  32 bytes.
 struct DeltaPartial {
@@ -79,6 +66,18 @@ struct DeltaPartial {
   int64_t offset; // winners of the blocks before this one (the totals record: unused)
 };
 static_assert(sizeof(DeltaPartial) == 32 && sizeof(fcp_table_delta_report_t) == 32, "records of 32 bytes");
+
+// What a lane, a wave and a block of the classify phase count (uint32_t: a chunk stays below 2^23 positions), and what the
+// lanes of the fold sum (int64_t)
+template <class T> struct DeltaCounts {
+  T winners, duplicates, skipped;
+  __device__ operator DeltaPartial() const { return DeltaPartial{(int64_t)winners, (int64_t)duplicates, (int64_t)skipped, 0}; }
+};
+template <class T> __device__ __forceinline__ void fold(DeltaCounts<T> &a, const DeltaCounts<T> &b) {
+  a.winners += b.winners;
+  a.duplicates += b.duplicates;
+  a.skipped += b.skipped;
+}
 
 struct DeltaTable {
   uint32_t *cells; // cell c: key at cells[2 c], pos1 at cells[2 c + 1]
@@ -129,41 +128,13 @@ __global__ void __launch_bounds__(kDeltaThreads) fcp_delta_clear_kernel(uint32_t
     *as_global(reinterpret_cast<uint64_t *>(cells) + i) = empty;
 }
 
-// one position of row r into the block's LDS table, or — no cell within the probes — into the global one
-template <int SLOTS>
-__device__ __forceinline__ void insert_row(const DeltaTable &T, LdsU32 *s_key, LdsU32 *s_pos, uint32_t r, uint32_t pos1) {
-  if constexpr (SLOTS > 0) {
-#pragma unroll
-    for (int p = 0; p < kDeltaProbes; ++p) {
-      const uint32_t slot = (r + p) & (SLOTS - 1);
-      uint32_t k = __hip_atomic_load(&s_key[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (k == kEmptyCell) {
-        uint32_t seen = kEmptyCell;
-        __hip_atomic_compare_exchange_strong(&s_key[slot], &seen, r, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        k = seen == kEmptyCell ? r : seen;
-      }
-      if (k == r) {
-        (void)__hip_atomic_fetch_max(&s_pos[slot], pos1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return;
-      }
-    }
-  }
-  insert_global(T, r, pos1);
-}
-
 template <int SLOTS>
 __global__ void __launch_bounds__(kDeltaThreads)
     fcp_delta_insert_kernel(DeltaTable T, const void *ids, int32_t is64, int64_t n, uint64_t table_rows) {
-  __shared__ uint32_t s_key[SLOTS > 0 ? SLOTS : 1];
-  __shared__ uint32_t s_pos[SLOTS > 0 ? SLOTS : 1];
+  __shared__ uint32_t s_key[SLOTS];
+  __shared__ uint32_t s_pos[SLOTS];
   const int tid = threadIdx.x;
-  if constexpr (SLOTS > 0) {
-    for (int i = tid; i < SLOTS; i += kDeltaThreads) {
-      s_key[i] = kEmptyCell;
-      s_pos[i] = 0;
-    }
-    __syncthreads();
-  }
+  lds_rows_clear<SLOTS, kDeltaThreads>(s_key, s_pos, tid);
   for (int64_t base = (int64_t)blockIdx.x * kDeltaInsertTile; base < n; base += (int64_t)gridDim.x * kDeltaInsertTile) {
     uint64_t id[kDeltaInsertIdsPerThread];
 #pragma unroll
@@ -173,17 +144,17 @@ __global__ void __launch_bounds__(kDeltaThreads)
     }
 #pragma unroll
     for (int k = 0; k < kDeltaInsertIdsPerThread; ++k) {
-      const int64_t i = base + k * kDeltaThreads + tid;
-      if (id[k] < table_rows) insert_row<SLOTS>(T, (LdsU32 *)s_key, (LdsU32 *)s_pos, (uint32_t)id[k], (uint32_t)(i + 1));
+      if (id[k] >= table_rows) continue;
+      // one position of row r: into the block's cell for r, or — no cell within the probes — into the global table
+      const uint32_t r = (uint32_t)id[k], pos1 = (uint32_t)(base + k * kDeltaThreads + tid + 1);
+      const int slot = lds_rows_claim<SLOTS>((LdsU32 *)s_key, r);
+      if (slot >= 0)
+        (void)__hip_atomic_fetch_max((LdsU32 *)s_pos + slot, pos1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      else
+        insert_global(T, r, pos1);
     }
   }
-  if constexpr (SLOTS > 0) {
-    __syncthreads();
-    for (int i = tid; i < SLOTS; i += kDeltaThreads) {
-      const uint32_t r = s_key[i];
-      if (r != kEmptyCell) insert_global(T, r, s_pos[i]); // (a claimed cell's pos1 is at least 1)
-    }
-  }
+  lds_rows_flush<SLOTS, kDeltaThreads>(s_key, s_pos, tid, [&](uint32_t r, uint32_t pos1) { insert_global(T, r, pos1); });
 }
 
 // chunk: positions of a block, a multiple of kDeltaTile; every thread of a block takes the same number of steps
@@ -193,7 +164,7 @@ __global__ void __launch_bounds__(kDeltaThreads)
   const int tid = threadIdx.x;
   const int64_t c0 = (int64_t)blockIdx.x * chunk;
   const int64_t c1 = c0 + chunk < n ? c0 + chunk : n;
-  uint32_t winners = 0, duplicates = 0, skipped = 0; // (a chunk stays below 2^23 positions)
+  DeltaCounts<uint32_t> c = {0, 0, 0};
   for (int64_t t0 = c0; t0 < c1; t0 += kDeltaTile) {
     const int64_t i = t0 + tid;
     if (i < c1) {
@@ -201,36 +172,15 @@ __global__ void __launch_bounds__(kDeltaThreads)
       bool win = false;
       if (id < table_rows) {
         win = lookup_global(T, (uint32_t)id) == (uint32_t)(i + 1);
-        winners += win;
-        duplicates += !win;
+        c.winners += win;
+        c.duplicates += !win;
       } else {
-        ++skipped;
+        ++c.skipped;
       }
       *as_global(flags + i) = win ? 1 : 0;
     }
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    winners += __shfl_xor(winners, m, 64);
-    duplicates += __shfl_xor(duplicates, m, 64);
-    skipped += __shfl_xor(skipped, m, 64);
-  }
-  __shared__ uint32_t s_wave[kDeltaThreads / 64][3];
-  if ((tid & 63) == 0) {
-    s_wave[tid / 64][0] = winners;
-    s_wave[tid / 64][1] = duplicates;
-    s_wave[tid / 64][2] = skipped;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    DeltaPartial p = {0, 0, 0, 0};
-    for (int w = 0; w < kDeltaThreads / 64; ++w) {
-      p.winners += s_wave[w][0];
-      p.duplicates += s_wave[w][1];
-      p.skipped += s_wave[w][2];
-    }
-    partials[blockIdx.x] = p;
-  }
+  block_fold(c, partials);
 }
 
 // one wave; lane l owns the records [l * per, (l + 1) * per) of the nblocks the classify phase wrote (0: it was not launched)
@@ -239,36 +189,31 @@ __global__ void __launch_bounds__(64)
   constexpr int per = kDeltaBlocks / 64;
   const int lane = threadIdx.x;
   const int b0 = lane * per, b1 = b0 + per < nblocks ? b0 + per : nblocks;
-  int64_t winners = 0, duplicates = 0, skipped = 0;
+  DeltaCounts<int64_t> c = {0, 0, 0};
   for (int b = b0; b < b1; ++b) {
-    winners += partials[b].winners;
-    duplicates += partials[b].duplicates;
-    skipped += partials[b].skipped;
+    c.winners += partials[b].winners;
+    c.duplicates += partials[b].duplicates;
+    c.skipped += partials[b].skipped;
   }
-  int64_t before = winners; // inclusive scan of the lanes' winners, then made exclusive
+  int64_t before = c.winners; // inclusive scan of the lanes' winners, then made exclusive
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
     const int64_t up = __shfl_up(before, d, 64);
     if (lane >= d) before += up;
   }
-  before -= winners;
+  before -= c.winners;
   for (int b = b0; b < b1; ++b) {
     partials[b].offset = before;
     before += partials[b].winners;
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    winners += __shfl_xor(winners, m, 64);
-    duplicates += __shfl_xor(duplicates, m, 64);
-    skipped += __shfl_xor(skipped, m, 64);
-  }
+  wave_fold(c);
   if (lane != 0) return;
-  partials[kDeltaBlocks] = DeltaPartial{winners, duplicates, skipped, 0};
+  partials[kDeltaBlocks] = c;
   fcp_table_delta_report_t r;
   r.n = n;
-  r.distinct = winners;
-  r.duplicates = duplicates;
-  r.skipped = skipped;
+  r.distinct = c.winners;
+  r.duplicates = c.duplicates;
+  r.skipped = c.skipped;
   *report = r;
 }
 

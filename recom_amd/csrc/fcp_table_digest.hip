@@ -35,6 +35,7 @@
 #pragma clang fp contract(off) // (the header's rule; nothing here is floating point)
 
 #include "fcp_table_walk.h" // with_group, with_one_of: the host's dispatch
+#include "fcp_block_fold.h" // wave_fold, block_fold: the fold of a lane's record into the block's
 
 namespace {
 
@@ -94,13 +95,10 @@ template <int A> __device__ __forceinline__ uint64_t ld_row_word(const char *row
   return w;
 }
 
-__device__ __forceinline__ void wave_fold(uint64_t &sum, int64_t &rows, int64_t &skipped) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    sum += __shfl_xor(sum, m, 64);
-    rows += __shfl_xor(rows, m, 64);
-    skipped += __shfl_xor(skipped, m, 64);
-  }
+__device__ __forceinline__ void fold(DigestPartial &a, const DigestPartial &b) {
+  a.sum += b.sum;
+  a.rows += b.rows;
+  a.skipped += b.skipped;
 }
 
 // base: the first row (BY_ID: the table's base); count: rows (BY_ID: ids), < 2^32 - 3; rb: bytes of a row.  Block =
@@ -160,37 +158,20 @@ __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
     }
   }
 
-  wave_fold(sum, nrows, nskipped);
-  __shared__ DigestPartial s_wave[FCP_BLOCK_THREADS / 64];
-  if ((tid & 63) == 0) s_wave[tid / 64] = DigestPartial{sum, nrows, nskipped, 0};
-  __syncthreads();
-  if (tid == 0) {
-    DigestPartial p = s_wave[0];
-    for (int k = 1; k < FCP_BLOCK_THREADS / 64; ++k) {
-      p.sum += s_wave[k].sum;
-      p.rows += s_wave[k].rows;
-      p.skipped += s_wave[k].skipped;
-    }
-    partials[blockIdx.x] = p;
-  }
+  block_fold(DigestPartial{sum, nrows, nskipped, 0}, partials);
 }
 
 // one wave; n: records of the workspace the first kernel wrote (0: it was not launched)
 __global__ void __launch_bounds__(64) fcp_table_digest_fold_kernel(const DigestPartial *partials, int32_t n, fcp_table_digest_t *out) {
   const int lane = threadIdx.x;
-  uint64_t sum = 0;
-  int64_t rows = 0, skipped = 0;
-  for (int i = lane; i < n; i += 64) {
-    sum += partials[i].sum;
-    rows += partials[i].rows;
-    skipped += partials[i].skipped;
-  }
-  wave_fold(sum, rows, skipped);
+  DigestPartial p = {0, 0, 0, 0};
+  for (int i = lane; i < n; i += 64) fold(p, partials[i]);
+  wave_fold(p);
   if (lane != 0) return;
   fcp_table_digest_t r;
-  r.sum = sum;
-  r.rows = rows;
-  r.skipped = skipped;
+  r.sum = p.sum;
+  r.rows = p.rows;
+  r.skipped = p.skipped;
   r.reserved = 0;
   *out = r;
 }

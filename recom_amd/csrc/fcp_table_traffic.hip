@@ -10,12 +10,9 @@
 //                     register, per block through one LDS cell, with ONE 64-bit atomic per block at the end.
 //                     One global atomic per id is the floor for ids spread over a large table and a cliff for the head of a
 //                     Zipf distribution (adders on one address serialise at the memory side).  So a block first counts in
-//                     LDS: an open-addressed table of kCountSlots {row, count} cells, home slot row mod kCountSlots, linear
-//                     probing over at most kCountProbes cells.  A cell is claimed by an LDS compare-and-swap on its key (the
-//                     key of a claimed cell never changes while the block runs, so a key that is read as another row's is
-//                     another row's for good) and bumped by an LDS add.  A row that finds no cell within the probes goes
-//                     straight to a global atomicAdd.  After its last tile the block flushes: one global atomicAdd per
-//                     occupied cell.  Every id thus reaches counts[] exactly once, alone or inside a cell's count; unsigned
+//                     LDS: the row table of fcp_block_fold.h, kCountSlots {row, count} cells, a claimed cell bumped by an LDS
+//                     add.  A row that finds no cell within the probes goes straight to a global atomicAdd.  After its
+//                     last tile the block flushes: one global atomicAdd per occupied cell.  Every id thus reaches counts[] exactly once, alone or inside a cell's count; unsigned
 //                     adds modulo 2^32 commute, in LDS as in memory, so the result is exact and independent of any order,
 //                     of the grid and of concurrent calls into the same array.
 //                     The table is as large as LDS allows — one block of 16 waves per CU, 128 KiB of cells — because what it
@@ -34,16 +31,17 @@
 //                     bodies call it: a row adds 1 to counts[row], kFiltered adds nothing, kBadRow touches no memory and
 //                     is counted per wave by ballot and popcount, one 64-bit atomic per wave that saw any.  The plan's own
 //                     bad-id counter is never passed.
-//                     SLOTS > 0: the block's reads go through count_row's LDS table first (a block serves one column,
-//                     hence one table: the same {row, count} cells, SLOTS of them) and are flushed at the end.  SLOTS = 0:
-//                     one global atomic per counted id — built for the measurement only (FCP_TRAFFIC_SLOTS below; the
-//                     figures behind the choice: DESIGN.md 3, profiles/plan_traffic.txt).
+//                     The block's reads go through count_row's LDS table first (a block serves one column, hence one
+//                     table: the same {row, count} cells, SLOTS of them) and are flushed at the end.  (One global atomic
+//                     per counted id, no LDS, a build of the commit that introduced the kernel: the figures behind the
+//                     choice are in DESIGN.md 3 and profiles/plan_traffic.txt.)
 // Every atomic's result is unused except the compare-and-swap's: the global ones are the no-return vector forms
 // (global_atomic_add / global_atomic_add_x2), nothing scalar.  No scratch; LDS: the two arrays and the skipped cell
 // (fcp_table_count_ids: 128 KiB + 8 bytes — a CU holds one block, and the block waits for a CU whose LDS other kernels have
 // left; fcp_plan_traffic_kernel: its two arrays, 16 KiB).
 #include "fcp_fused_bodies.h"
 #include "fcp_host.h"
+#include "fcp_block_fold.h" // the block's LDS row table: lds_rows_clear / _claim / _flush
 
 namespace {
 
@@ -52,34 +50,14 @@ constexpr int kCountBlocks = 256;           // the fixed grid: one block on each
 constexpr int kIdsPerThread = 4;
 constexpr int kTileIds = kCountThreads * kIdsPerThread; // ids of one step of a block's stride loop
 constexpr int kCountSlots = 16384;          // cells of a block's LDS table (128 KiB of the CU's 160); a power of two
-constexpr int kCountProbes = 4;             // cells a row looks at, from its home slot on
-constexpr uint32_t kEmptyCell = 0xFFFFFFFFu; // table_rows < 2^32 - 3: a row index fits 32 bits, and this is none
-static_assert((kCountSlots & (kCountSlots - 1)) == 0 && kCountSlots % kCountThreads == 0, "slot masks and the flush loop");
-
-// (explicit address spaces: with generic pointers the compiler merges the LDS add and the global add of the two exits into
-// ONE flat atomic on either address)
-typedef __attribute__((address_space(3))) uint32_t LdsU32;
 
 // one read of row r: into the block's cell for r, or — no cell within the probes — into counts[r] itself
-// (SLOTS: cells of the block's table, a power of two)
-template <int SLOTS = kCountSlots>
-__device__ __forceinline__ void count_row(uint32_t *counts, LdsU32 *s_key, LdsU32 *s_cnt, uint32_t r) {
-#pragma unroll
-  for (int p = 0; p < kCountProbes; ++p) {
-    const uint32_t slot = (r + p) & (SLOTS - 1);
-    uint32_t k = __hip_atomic_load(&s_key[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (k == kEmptyCell) {
-      // what the cell held: still empty = claimed for r
-      uint32_t seen = kEmptyCell;
-      __hip_atomic_compare_exchange_strong(&s_key[slot], &seen, r, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      k = seen == kEmptyCell ? r : seen;
-    }
-    if (k == r) {
-      (void)__hip_atomic_fetch_add(&s_cnt[slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      return;
-    }
-  }
-  (void)__hip_atomic_fetch_add(as_global(counts + r), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+template <int SLOTS> __device__ __forceinline__ void count_row(uint32_t *counts, uint32_t *s_key, uint32_t *s_cnt, uint32_t r) {
+  const int slot = lds_rows_claim<SLOTS>((LdsU32 *)s_key, r);
+  if (slot >= 0)
+    (void)__hip_atomic_fetch_add((LdsU32 *)s_cnt + slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  else
+    (void)__hip_atomic_fetch_add(as_global(counts + r), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ids: the call's n ids.  Every thread of a block takes the same number of steps, so whole waves reach the ballots.
@@ -90,12 +68,8 @@ __global__ void __launch_bounds__(kCountThreads)
   __shared__ uint32_t s_cnt[kCountSlots];
   __shared__ unsigned long long s_skipped;
   const int tid = threadIdx.x;
-  for (int i = tid; i < kCountSlots; i += kCountThreads) {
-    s_key[i] = kEmptyCell;
-    s_cnt[i] = 0;
-  }
   if (tid == 0) s_skipped = 0;
-  __syncthreads();
+  lds_rows_clear<kCountSlots, kCountThreads>(s_key, s_cnt, tid);
 
   unsigned long long outside = 0; // of this wave: the same value in every lane
   for (int64_t base = (int64_t)blockIdx.x * kTileIds; base < n; base += (int64_t)gridDim.x * kTileIds) {
@@ -111,16 +85,11 @@ __global__ void __launch_bounds__(kCountThreads)
     for (int k = 0; k < kIdsPerThread; ++k) {
       const bool live = have[k] && id[k] < table_rows;
       outside += (unsigned long long)__popcll(__ballot(have[k] && !live));
-      if (live) count_row(counts, (LdsU32 *)s_key, (LdsU32 *)s_cnt, (uint32_t)id[k]);
+      if (live) count_row<kCountSlots>(counts, s_key, s_cnt, (uint32_t)id[k]);
     }
   }
   if ((tid & 63) == 0 && outside != 0) atomicAdd(&s_skipped, outside);
-  __syncthreads();
-
-  for (int i = tid; i < kCountSlots; i += kCountThreads) {
-    const uint32_t c = s_cnt[i];
-    if (c != 0) atomicAdd(counts + s_key[i], c); // (c != 0: the cell was claimed, its key is a row < table_rows)
-  }
+  lds_rows_flush<kCountSlots, kCountThreads>(s_key, s_cnt, tid, [&](uint32_t r, uint32_t c) { atomicAdd(counts + r, c); });
   if (tid == 0 && skipped && s_skipped != 0) atomicAdd(skipped, s_skipped);
 }
 
@@ -130,12 +99,12 @@ constexpr int kTrafficThreads = 256;
 constexpr int kTrafficIdsPerThread = 4;
 constexpr int kTrafficTile = kTrafficThreads * kTrafficIdsPerThread; // positions of an id stream per block and step
 constexpr int kTrafficMaxTilesY = 65535;                             // the grid's y extent; longer streams: the stride loop
+constexpr int kTrafficSlots = 2048;                                  // cells of a block's table: 2 x 8 KiB of LDS for a tile of 1024 ids
 
 template <int SLOTS>
 __global__ void __launch_bounds__(kTrafficThreads) fcp_plan_traffic_kernel(FcpTrafficLaunch T) {
-  static_assert((SLOTS & (SLOTS - 1)) == 0 && SLOTS % kTrafficThreads == 0, "slot masks and the flush loop");
-  __shared__ uint32_t s_key[SLOTS > 0 ? SLOTS : 1];
-  __shared__ uint32_t s_cnt[SLOTS > 0 ? SLOTS : 1];
+  __shared__ uint32_t s_key[SLOTS];
+  __shared__ uint32_t s_cnt[SLOTS];
   const FcpTrafficCol tc = ld_rec(as_const(T.list) + blockIdx.x);
   const FcpColDyn d = ld_rec(as_const(T.dyn) + tc.pos);
   const int nnz = d.nnz;
@@ -150,13 +119,7 @@ __global__ void __launch_bounds__(kTrafficThreads) fcp_plan_traffic_kernel(FcpTr
   const FcpXform *xf = T.xforms + tc.pos; // (only dereferenced by a column with a transform: then the array exists)
   uint32_t *counts = tc.counts;
   const int tid = threadIdx.x;
-  if constexpr (SLOTS > 0) {
-    for (int i = tid; i < SLOTS; i += kTrafficThreads) {
-      s_key[i] = kEmptyCell;
-      s_cnt[i] = 0;
-    }
-    __syncthreads();
-  }
+  lds_rows_clear<SLOTS, kTrafficThreads>(s_key, s_cnt, tid);
 
   unsigned long long outside = 0; // of this wave: the same value in every lane
   for (int64_t base = (int64_t)blockIdx.y * kTrafficTile; base < nnz; base += (int64_t)gridDim.y * kTrafficTile) {
@@ -167,35 +130,17 @@ __global__ void __launch_bounds__(kTrafficThreads) fcp_plan_traffic_kernel(FcpTr
       uint32_t row = kFiltered;
       if (i < nnz) row = fetch_slot_offset<1, false>(c, xf, i, nullptr, 0, 1, bad);
       outside += (unsigned long long)__popcll(__ballot(row == kBadRow));
-      if (is_row(row)) {
-        if constexpr (SLOTS > 0)
-          count_row<SLOTS>(counts, (LdsU32 *)s_key, (LdsU32 *)s_cnt, row);
-        else
-          (void)__hip_atomic_fetch_add(as_global(counts + row), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      if (is_row(row)) count_row<SLOTS>(counts, s_key, s_cnt, row);
     }
   }
   if ((tid & 63) == 0 && outside != 0 && T.skipped)
     (void)__hip_atomic_fetch_add(as_global(T.skipped), outside, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if constexpr (SLOTS > 0) {
-    __syncthreads();
-    for (int i = tid; i < SLOTS; i += kTrafficThreads) {
-      const uint32_t n = s_cnt[i];
-      // (n != 0: the cell was claimed, its key is a row < vocab)
-      if (n != 0) (void)__hip_atomic_fetch_add(as_global(counts + s_key[i]), n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  lds_rows_flush<SLOTS, kTrafficThreads>(s_key, s_cnt, tid, [&](uint32_t r, uint32_t n) {
+    (void)__hip_atomic_fetch_add(as_global(counts + r), n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  });
 }
 
 } // namespace
-
-// Cells of a block's table in fcp_plan_traffic_kernel: 2048 (2 x 8 KiB of LDS) for a tile of 1024 ids.  -DFCP_TRAFFIC_SLOTS=0
-// builds the plainer kernel instead — one global atomic per counted id, no LDS — which the choice was measured against
-// (scripts/plan_traffic_cost.py --variant, profiles/plan_traffic.txt); the library is built with the default.
-#ifndef FCP_TRAFFIC_SLOTS
-#define FCP_TRAFFIC_SLOTS 2048
-#endif
-constexpr int kTrafficSlots = FCP_TRAFFIC_SLOTS;
 
 int fcp_launch_plan_traffic(const FcpTrafficLaunch &T, int n_list, int max_nnz, ihipStream_t *s) {
   if (n_list <= 0 || max_nnz <= 0) return 0;

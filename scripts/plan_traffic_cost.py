@@ -3,9 +3,9 @@
 Per workload — S2 at batch 512 (1000 columns, every 10th bucketized), RAGGED (BASELINE configs[3]: 512 multi-hot columns,
 SparseTensor indices, int64 ids) and RAGGED with bags of up to 300 Zipf-distributed ids — one resident request, and for it
   (a) fcp_plan_traffic_count: one launch — the library's kernel (a block counts in an LDS table first) and, for every
-      `--variant NAME=LIBRARY`, another build's, called on the same plan object (how the kernel's shape was chosen:
-      `make -C recom_amd/csrc OUT=<dir> FLAGS="<the Makefile's FLAGS> -DFCP_TRAFFIC_SLOTS=0"` builds the plainer kernel, one
-      global atomic per counted id and no LDS table);
+      `--variant NAME=LIBRARY`, another build's, called on the same plan object (how the kernel's shape was chosen: the
+      variant on file was a build of the commit that introduced the kernel with the plainer kernel in it, one global atomic
+      per counted id and no LDS table; `make -C recom_amd/csrc OUT=<dir>` at any commit gives such a library);
   (b) the composition it replaces: per lookup column the ids transformed in torch (torch.bucketize for the bucketized
       columns; the others carry row ids already) and one fcp_table_count_ids per column, called through ctypes with
       arguments built beforehand — its device code is the same in every build, so it is measured here, in the same run;

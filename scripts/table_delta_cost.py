@@ -4,8 +4,9 @@ One delta of 2^20 ids and float32 rows of dim 64 against a q8 table of 16 M rows
 the positions repeating another position's id, Zipf(1.05), all equal.  Per pattern, the median of warm HIP-event timings of
   distinct          fcp_table_delta_distinct (its five launches), outputs and workspace allocated once — once per library:
                     the one the package loads and every `--variant NAME=LIBRARY`, another build's (how the insert phase was
-                    chosen: `make -C recom_amd/csrc OUT=<dir> DELTA_SLOTS=0` builds the plain kernel, one global claim and
-                    max per position, `DELTA_SLOTS=<cells>` another size of the LDS stage);
+                    chosen: the variant on file was a build of the commit that introduced the kernel with the plain kernel
+                    in it, one global claim and max per position; `make -C recom_amd/csrc OUT=<dir>` at any commit gives
+                    such a library);
   distinct+update   the same followed by fcp_table_update_rows of the padded outputs into the q8 table;
   update            plain fcp_table_update_rows of the delta as it stands (what a distinct delta costs today; with repeated ids
                     its bytes are unspecified, its time is not);
@@ -32,7 +33,7 @@ HEAD = """fcp_table_delta_distinct: what it costs beside the update, a copy and 
 =========================================================================================
 Produced by scripts/table_delta_cost.py (one MI355X, one child process under its own timeout; medians of {reps} warm HIP-event
 timings per leg).  {ids} ids (int64) and float32 rows of dim {dim} against a q8 table of {rows} rows.  `shipped` is the library
-the package loads; the other names are builds of the same source with another FCP_DELTA_SLOTS.
+the package loads; the other names are other builds of the library (--variant).
 
     {cmdline}
 

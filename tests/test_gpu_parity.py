@@ -1742,6 +1742,24 @@ def test_concat_outputs_host_from_many_threads_and_without_an_allocator(torch_cu
 
 
 @pytest.mark.gpu
+def test_concat_outputs_host_regrows_its_staging_slots(torch_cuda):
+    """A payload above a staging slot's 64 KiB floor after one below it on the same device: 8 inputs of dim 8 with 4 rows
+    once per slot of the ring (four), then with 320 rows (80 KiB) once per slot — a slot that was at its floor is freed and
+    allocated again — then 4 rows again; every output equals the NumPy scatter."""
+    from recom_amd.ops import concat_outputs_host
+    torch = torch_cuda
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(7)
+    offs = [8 * k for k in range(8)]
+    for rows in (4, 4, 4, 4, 320, 320, 320, 320, 4):
+        host = [rng.standard_normal((rows, 8)).astype(np.float32) for _ in offs]
+        out = torch.full((rows, 64), -7.0, device=dev)
+        concat_outputs_host(host, offs, out)
+        torch.cuda.synchronize()
+        assert np.array_equal(out.cpu().numpy(), np.concatenate(host, axis=1)), rows
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("seed", range(16))
 def test_random_sparse_reshape_graphs_to_hip_path(torch_cuda, tmp_path, seed):
     """GraphDef -> plan -> HIP for random SparseReshapes (identity, constant and run-time segment-id maps, ops left to
