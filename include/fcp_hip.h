@@ -590,6 +590,66 @@ int64_t fcp_table_delta_workspace_bytes(int64_t n);
 int fcp_table_delta_distinct(const void *row_ids, int32_t id_bytes, const float *rows, int32_t dim, int64_t n, int64_t table_rows,
                              int64_t *ids_out, float *rows_out, int64_t *pos_out, fcp_table_delta_report_t *report, void *workspace,
                              int32_t device, void *stream);
+/* ---- a new master against a served table: the rows whose stored bytes would change ------------------------------------------ */
+/* Every entry above takes a delta somebody already has.  A trainer often ships a whole new float32 checkpoint instead, and a
+ * digest says THAT two replicas differ, not WHERE.  fcp_table_diff turns "new rows + served table" into the delta
+ * fcp_table_update_rows takes, in one pass over the new rows and the stored rows, without a temporary table, and with the
+ * library's own quantiser deciding: a float32 row whose change the format cannot see — low mantissa bits that round away in
+ * bf16 / fp16, a nudge far below half a code step in q8 — is not reported and need not be shipped or written.
+ *
+ * `table` is the BASE of a table [table_rows, dim] in format `kind` (any FCP_TAB_* value, float32 included); `src` points at the
+ * FIRST of `rows` rows in format src_kind, and row i of `src` is the candidate for table row row0 + i — row0 lets a checkpoint
+ * stream through a bounce buffer, as dst_row0 does for fcp_table_convert.  src_kind is FCP_TAB_F32 (the new master) or `kind`
+ * (a replica of the same format: ids only, `rows_out` must be NULL); for a float32 table the two coincide and `rows_out` is
+ * allowed.  Everything is on the device.
+ *
+ * Which rows are changed.  Table row row0 + i is CHANGED when the fcp_table_row_bytes(kind, dim) bytes fcp_table_convert
+ * (float32 -> kind) writes for row i of `src` — for a replica, and for float32 against float32: the bytes of row i themselves —
+ * differ in any byte from the bytes stored: a compare of BITS (-0.0 differs from +0.0, two NaNs with equal bits are
+ * unchanged).  A q8 row is quantised in registers by the arithmetic of fcp_table_convert's value model and compared with the
+ * stored codes and the stored scale and bias; a 16-bit row is fl16 of its elements.  Nothing is written to the table.  The answer
+ * for a q8 row that holds a NaN or an infinity, or whose range overflows float32, is UNSPECIFIED (but never a fault), as its
+ * bytes are in fcp_table_convert.  With the changed rows r_0 < r_1 < ... < r_(m-1) — ascending table row index —
+ *   ids_out[k]     = r_k for k < m, and -1 for m <= k < rows;                                    int64 [rows]
+ *   rows_out[k, :] = the dim 32-bit words of the `src` row of r_k for k < m, copied as BITS; rows k >= m of rows_out are not
+ *                    touched;                                                                    float32 [rows, dim]; may be NULL
+ *   *report        = {rows, m, r_0, r_(m-1)}, as declared below; -1 for both rows when m == 0.
+ *
+ * Chaining without the host.  The -1 tail lets (ids_out, rows_out, rows) go straight into fcp_table_update_rows and
+ * fcp_table_digest_rows on the same stream; no host read of m is needed (both skip -1 and count it in their `skipped`).  After
+ * that update the table's rows row0 .. row0 + rows - 1 equal, byte for byte, what fcp_table_convert of `src` at dst_row0 = row0
+ * would have written.
+ *
+ * Device to device on `device`, asynchronous on `stream` (a hipStream_t), no allocation, no synchronisation.  `workspace` holds
+ * fcp_table_diff_workspace_bytes of `rows` bytes; its content before and after the call means nothing.  Every output byte is a
+ * function of the arguments alone — the grid is fixed by `rows`, one partial record per block, a one-wave fold, no atomics:
+ * two calls leave the same bytes.  Inputs are only read; outputs must not overlap the inputs or each other (not checked).
+ * table_rows lies in [1, 2^32 - 3), 0 <= row0 and row0 + rows <= table_rows.  Alignment: `table` and `src` obey the plan's rule
+ * for their kinds (with V the largest of 4 | 2 | 1 that divides dim: float32 4 * V bytes, bf16 / fp16 2 * V bytes, q8 4 bytes),
+ * `rows_out` that of a float32 table of this dim, `ids_out`, `report` and `workspace` 8 bytes.
+ *
+ * The workspace size depends on `rows` only — one flag byte per row and the blocks' records: a multiple of 8, non-decreasing,
+ * at most rows + 2^17; -1 for rows < 0 or rows >= 2^32 - 3.
+ *
+ * Status, decided in this order (the first needs no device), as in fcp_table_delta_distinct:
+ *   FCP_ERR_INVALID_ARGUMENT  rows < 0 or beyond its limit; table_rows outside its range; row0 < 0 or row0 + rows beyond
+ *                             table_rows; dim <= 0; a kind that is no row format; a src_kind that is neither FCP_TAB_F32 nor
+ *                             kind; a rows_out with a compact src_kind; a null report or workspace; a null table, src or
+ *                             ids_out with rows > 0; a misaligned table, src, ids_out, rows_out, report or workspace (in this
+ *                             order); fcp_last_error names the argument between backquotes;
+ *   FCP_ERR_NO_DEVICE         no usable gfx950 device (rows == 0 included: `report` is written on the device);
+ *   FCP_ERR_HIP               a kernel launch failed.
+ * No combination of valid arguments is FCP_ERR_UNSUPPORTED. */
+typedef struct fcp_table_diff_report {
+  int64_t rows;          /* rows compared */
+  int64_t changed;       /* rows whose stored bytes would change: m */
+  int64_t first_changed; /* smallest changed table row index, -1 if none */
+  int64_t last_changed;  /* largest, -1 if none */
+} fcp_table_diff_report_t; /* 32 bytes */
+int64_t fcp_table_diff_workspace_bytes(int64_t rows);
+int fcp_table_diff(const void *table, int32_t kind, int64_t table_rows, int32_t dim, const void *src, int32_t src_kind,
+                   int64_t row0, int64_t rows, int64_t *ids_out, float *rows_out, fcp_table_diff_report_t *report,
+                   void *workspace, int32_t device, void *stream);
 /* ---- table audit: what each compact format would do to a float32 table, before anything is written --------------------------- */
 /* fcp_table_audit: judge `rows` float32 rows of width `dim` — a table before fcp_table_convert, or the rows of a delta before
  * fcp_table_update_rows — against FCP_TAB_BF16, FCP_TAB_F16 and FCP_TAB_Q8 at once, reading every source element once (the

@@ -146,6 +146,11 @@ class TableDeltaReport(C.Structure):
     _fields_ = [("n", C.c_int64), ("distinct", C.c_int64), ("duplicates", C.c_int64), ("skipped", C.c_int64)]
 
 
+class TableDiffReport(C.Structure):
+    """fcp_table_diff_report_t"""
+    _fields_ = [("rows", C.c_int64), ("changed", C.c_int64), ("first_changed", C.c_int64), ("last_changed", C.c_int64)]
+
+
 class OutputError(C.Structure):
     """fcp_output_error_t"""
     _fields_ = [("elems", C.c_int64), ("differ", C.c_int64), ("nonfinite", C.c_int64), ("first_differ_row", C.c_int64),
@@ -205,6 +210,7 @@ EXPORTS = [
     "fcp_plan_table_rows", "fcp_plan_traffic_bind", "fcp_plan_traffic_count",
     "fcp_table_digest_workspace_bytes", "fcp_table_digest", "fcp_table_digest_rows", "fcp_table_digest_host",
     "fcp_table_delta_workspace_bytes", "fcp_table_delta_distinct",
+    "fcp_table_diff_workspace_bytes", "fcp_table_diff",
     "fcp_outputs_compare_workspace_bytes", "fcp_outputs_compare",
 ]
 
@@ -393,6 +399,11 @@ def load() -> C.CDLL:
         L.fcp_table_delta_workspace_bytes.argtypes = [C.c_int64]
         L.fcp_table_delta_distinct.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    if hasattr(L, "fcp_table_diff"):
+        L.fcp_table_diff_workspace_bytes.restype = C.c_int64
+        L.fcp_table_diff_workspace_bytes.argtypes = [C.c_int64]
+        L.fcp_table_diff.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     if hasattr(L, "fcp_outputs_compare"):
         L.fcp_outputs_compare_workspace_bytes.restype = C.c_int64
         L.fcp_outputs_compare_workspace_bytes.argtypes = [C.c_int32]

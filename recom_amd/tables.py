@@ -11,7 +11,10 @@ and the digest of a table of any format — an order-free 64-bit sum of row hash
 deployment checks that a served table is, byte for byte, the table it should be, and keeps that check across ``update_rows``;
 and, for deltas that name a row more than once, the ids made distinct on the device with the last occurrence winning
 (``fcp_table_delta_distinct``, recom_amd/csrc/fcp_table_delta.hip), in front of ``update_rows`` and the digest bookkeeping, which
-both ask for distinct ids and do not check (``apply_delta``).
+both ask for distinct ids and do not check (``apply_delta``);
+and, for a trainer that ships a whole new float32 master instead of a delta, the rows of a served table whose stored bytes
+would change, found on the device in one pass without a temporary table (``fcp_table_diff``,
+recom_amd/csrc/fcp_table_diff.hip: ``diff``, ``diff_from_host``, ``sync_from_host``).
 
 Plans do not quantise; this does, once, at load time.  The value model is the header's (include/fcp_hip.h): float32 -> q8 is
 exactly the tensor ``quantized::embedding_bag_byte_prepack`` returns, q8 -> float32 is ``fma(code, scale, bias)`` rounded
@@ -649,3 +652,164 @@ def apply_delta(table, row_ids, rows, digest: Optional[int] = None, row0: int = 
         return report
     before, after = _digests_of(outs)
     return report, (int(digest) - int(before.sum) + int(after.sum)) % (1 << 64)
+
+
+# ---- a new master against a served table (fcp_table_diff) ----------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class DiffReport:
+    """fcp_table_diff_report_t on the host."""
+    rows: int            # rows compared
+    changed: int         # rows whose stored bytes would change
+    first_changed: int   # smallest changed table row index, -1 if none
+    last_changed: int    # largest, -1 if none
+
+
+def _diff_report_of(report_t) -> DiffReport:
+    return DiffReport(*(int(v) for v in report_t.cpu().tolist()))
+
+
+def diff_async(table, src, row0: int = 0, want_rows: bool = True, stream: Optional[int] = None):
+    """``fcp_table_diff`` enqueued on ``stream`` (torch's current stream of the device by default), nothing synchronised.
+    ``table``: a device tensor in one of the four table formats; ``src``: the candidates for its rows ``row0 ..
+    row0 + len(src) - 1`` — float32 ``[rows, dim]`` (a new master), or rows in the table's own format (a replica: ids only,
+    ``want_rows=False``).  Returns ``(ids, rows, report)`` at their full length: the changed rows' table indices in front, in
+    ascending order, ``-1`` behind them; the changed ``src`` rows behind one another, the rest uninitialised (``None`` without
+    ``want_rows``); ``report`` the int64 ``[4]`` device tensor ``(rows, changed, first_changed, last_changed)``.  The padded
+    ``(ids, rows)`` go straight into ``update_rows`` / ``digest_rows`` on the same stream, which skip ``-1``.  Outputs and
+    workspace are allocated as that stream's."""
+    import torch
+    name, dim = _kind_and_dim(table, "table")
+    src_name, src_dim = _kind_and_dim(src, "src")
+    if src_name not in ("f32", name):
+        raise ValueError(f"src is {src_name}; a {name} table is compared with a float32 master or a {name} replica")
+    if src_dim != dim:
+        raise ValueError(f"src has rows of dim {src_dim}; the table's are of dim {dim}")
+    if src.device != table.device:
+        raise ValueError(f"table is on {table.device}, src on {src.device}")
+    rows = int(src.shape[0])
+    if row0 < 0 or row0 + rows > table.shape[0]:
+        raise ValueError(f"rows [{row0}, {row0 + rows}) do not lie in a table of {table.shape[0]} rows")
+    if want_rows and src_name != "f32":
+        raise ValueError(f"a {src_name} replica gives ids only: want_rows=False")
+    L = _lib.load()
+    device = table.device
+    need = int(L.fcp_table_diff_workspace_bytes(rows))
+    if need < 0:
+        raise ValueError(f"src has {rows} rows; a call stays below 2^32 - 3")
+    if stream is None:
+        stream = torch.cuda.current_stream(device).cuda_stream
+    with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device)):
+        ids_out = torch.empty((rows,), dtype=torch.int64, device=device)
+        rows_out = torch.empty((rows, dim), dtype=torch.float32, device=device) if want_rows else None
+        report = torch.empty((C.sizeof(_lib.TableDiffReport) // 8,), dtype=torch.int64, device=device)
+        workspace = torch.empty((need // 8,), dtype=torch.int64, device=device)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+    status = L.fcp_table_diff(ptr(table), _lib.TABLE_KINDS[name], int(table.shape[0]), dim, ptr(src), _lib.TABLE_KINDS[src_name], int(row0),
+                              rows, ptr(ids_out), ptr(rows_out), ptr(report), ptr(workspace), device.index or 0, C.c_void_p(stream))
+    _lib.check(status, "fcp_table_diff")
+    return ids_out, rows_out, report
+
+
+def diff(table, src, row0: int = 0, want_rows: bool = True, stream: Optional[int] = None):
+    """``fcp_table_diff``: the rows of ``table`` whose stored bytes would change if ``src`` — a new float32 master, or a replica
+    in the table's format — were converted over its rows ``row0`` and below: a row counts when the bytes ``convert`` writes for
+    it differ from the bytes stored, so a float32 change the format cannot see is not reported.  Runs on ``stream`` (torch's
+    current stream of the device by default), synchronises it, and returns ``(ids[:m], rows[:m] or None, report)`` with
+    ``report`` a ``DiffReport`` — the delta ``update_rows`` takes."""
+    import torch
+    ids, rows, report_t = diff_async(table, src, row0=row0, want_rows=want_rows, stream=stream)
+    if stream is None:
+        stream = torch.cuda.current_stream(table.device).cuda_stream
+    torch.cuda.ExternalStream(stream, device=table.device).synchronize()
+    report = _diff_report_of(report_t)
+    m = report.changed
+    return ids[:m], rows[:m] if rows is not None else None, report
+
+
+def _host_master_of(torch, table, master_cpu, who: str, chunk_rows: int):
+    if master_cpu.dtype != torch.float32 or master_cpu.dim() != 2 or master_cpu.is_cuda:
+        raise ValueError(f"{who} takes a float32 [rows, dim] tensor on the host")
+    if chunk_rows <= 0:
+        raise ValueError("chunk_rows must be positive")
+    _name, dim = _kind_and_dim(table, "table")
+    if tuple(master_cpu.shape) != (int(table.shape[0]), dim):
+        raise ValueError(f"the master is {tuple(master_cpu.shape)}; the table has {table.shape[0]} rows of dim {dim}")
+    return int(table.shape[0]), dim
+
+
+def diff_from_host(table, master_cpu, chunk_rows: int = 1 << 16):
+    """``diff`` of the device ``table`` against a whole new master in HOST memory (torch CPU tensor, float32 ``[rows, dim]``,
+    as many rows as the table), streamed through ONE pinned bounce buffer and one device buffer of ``chunk_rows`` rows, as
+    ``convert_from_host`` streams a table: the device never holds the float32 master.  Synchronises torch's current stream once
+    per chunk and returns the concatenated delta ``(ids, rows, report)`` — ascending ids, ``report`` a ``DiffReport`` of the
+    whole table."""
+    import torch
+    rows, dim = _host_master_of(torch, table, master_cpu, "diff_from_host", chunk_rows)
+    device = table.device
+    chunk = min(chunk_rows, max(rows, 1))
+    bounce = torch.empty((chunk, dim), dtype=torch.float32, pin_memory=True)
+    staged = torch.empty((chunk, dim), dtype=torch.float32, device=device)
+    ids, deltas, first, last = [], [], -1, -1
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device)
+        for r0 in range(0, rows, chunk):
+            n = min(chunk, rows - r0)
+            bounce[:n].copy_(master_cpu[r0:r0 + n])
+            staged[:n].copy_(bounce[:n], non_blocking=True)
+            ids_d, rows_d, report_t = diff_async(table, staged[:n], row0=r0, stream=stream.cuda_stream)
+            stream.synchronize()                      # the bounce buffer's copy has left it; the chunk's m is known
+            r = _diff_report_of(report_t)
+            if r.changed:
+                ids.append(ids_d[:r.changed].clone())
+                deltas.append(rows_d[:r.changed].clone())
+                first, last = (r.first_changed if first < 0 else first), r.last_changed
+    m = sum(int(t.shape[0]) for t in ids)
+    all_ids = torch.cat(ids) if ids else torch.empty((0,), dtype=torch.int64, device=device)
+    all_rows = torch.cat(deltas) if deltas else torch.empty((0, dim), dtype=torch.float32, device=device)
+    return all_ids, all_rows, DiffReport(rows, m, first, last)
+
+
+def sync_from_host(table, master_cpu, digest: Optional[int] = None, chunk_rows: int = 1 << 16):
+    """Make the device ``table`` what ``convert`` writes from a whole new master in HOST memory, rewriting only the rows whose
+    stored bytes change: per chunk, on torch's current stream, copy -> ``diff_async`` -> ``update_rows`` of the padded outputs,
+    through one pinned bounce buffer and one device buffer of ``chunk_rows`` rows.  With ``digest`` (that of the whole table
+    before) the ``digest_rows`` bookkeeping of ``apply_delta`` runs around every update.  Returns the number of rows rewritten,
+    or ``(rows rewritten, new digest)`` when ``digest`` was given."""
+    import torch
+    rows, dim = _host_master_of(torch, table, master_cpu, "sync_from_host", chunk_rows)
+    name, _dim = _kind_and_dim(table, "table")
+    device = table.device
+    L = _lib.load()
+    chunk = min(chunk_rows, max(rows, 1))
+    n_chunks = (rows + chunk - 1) // chunk
+    bounce = torch.empty((chunk, dim), dtype=torch.float32, pin_memory=True)
+    staged = torch.empty((chunk, dim), dtype=torch.float32, device=device)
+    size = C.sizeof(_lib.TableDigest)
+    reports = []
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device)
+        s = stream.cuda_stream
+        if digest is not None:
+            outs, workspace = _digest_buffers(torch, L, device, s, n_out=2 * max(n_chunks, 1))
+        for k, r0 in enumerate(range(0, rows, chunk)):
+            n = min(chunk, rows - r0)
+            stream.synchronize()                      # the bounce buffer's last copy has left it
+            bounce[:n].copy_(master_cpu[r0:r0 + n])
+            staged[:n].copy_(bounce[:n], non_blocking=True)
+            ids_d, rows_d, report_t = diff_async(table, staged[:n], row0=r0, stream=s)
+            if digest is not None:
+                _enqueue_digest_rows(L, table, name, dim, ids_d, n, 0, 1, outs.data_ptr() + 2 * k * size, workspace, s)
+            update_rows(table, ids_d, rows_d, stream=s)
+            if digest is not None:
+                _enqueue_digest_rows(L, table, name, dim, ids_d, n, 0, 1, outs.data_ptr() + (2 * k + 1) * size, workspace, s)
+            reports.append(report_t)
+        stream.synchronize()
+    changed = sum(_diff_report_of(t).changed for t in reports)
+    if digest is None:
+        return changed
+    new = int(digest)
+    if n_chunks:
+        records = _digests_of(outs)
+        for k in range(n_chunks):
+            new = new - int(records[2 * k].sum) + int(records[2 * k + 1].sum)
+    return changed, new % (1 << 64)
