@@ -25,6 +25,8 @@
 
 #include "../../include/fcp_hip.h"
 #include "fcp_fused_bodies.h" // (--mix-probe: the product's table loads and its three output stores)
+#include "fcp_env.h"
+#include "fcp_plain_map.h"    // (--mix-probe: the product's block mapping)
 #include "numa_util.h"
 
 struct fcp_harness;
@@ -82,20 +84,11 @@ __global__ void fill_table(float *t, uint32_t seed, uint64_t vocab, uint32_t dim
 // the offsets per (row, column) instead — fewer bytes than the ids, but behind one dependent hop (slot -> column).
 __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
 mix_probe_kernel(const float *const *tptr, const uint32_t *roff, const int32_t *col_of, int roff_stride, float *out, int rows, int nslots,
-                 int nsp8, int nlist, int out_stride, int policy) {
+                 int nsp8, int nlist, int deal_tiles, int out_stride, int policy) {
   constexpr int V = 4, R = 4, RB = FCP_WAVES_PER_BLOCK * R;
   const int lane = threadIdx.x & (FCP_WAVE - 1), wave = threadIdx.x >> 6;
-  const int bid = blockIdx.x;
   int idx, tile;
-  if (nsp8 > 0) {
-    const int xcd = bid & 7, j8 = bid >> 3;
-    idx = (j8 % nsp8) * 8 + xcd;
-    tile = j8 / nsp8;
-  } else {
-    idx = bid % (-nsp8);
-    tile = bid / (-nsp8);
-  }
-  if (idx >= nlist) return;
+  if (!fcp_plain_locate(blockIdx.x, nsp8, nlist, deal_tiles, idx, tile)) return;
   const int q = idx * FCP_WAVE + lane, row0 = tile * RB + wave * R;
   if (q >= nslots || row0 >= rows) return;
   const float *tb = *as_global(tptr + q);
@@ -419,6 +412,8 @@ int main(int argc, char **argv) {
     const int nslots = width / 4, nspans = (nslots + FCP_WAVE - 1) / FCP_WAVE;
     const int nsp8 = nspans >= 8 ? (nspans + 7) / 8 : -nspans, ntiles = (batch + 15) / 16;
     const int grid = (nsp8 > 0 ? 8 * nsp8 : nspans) * ntiles;
+    // the product's block mapping, and its switch (FCP_DIAG=plain_even_deal=0|1)
+    const int deal_tiles = fcp::diag_ll("plain_even_deal", FCP_PLAIN_EVEN_DEAL_DEFAULT) != 0 ? ntiles : 0;
     std::vector<const float *> h_tptr(nslots);
     std::vector<int> col_of(nslots);
     for (int c = 0; c < columns; ++c)
@@ -467,7 +462,7 @@ int main(int argc, char **argv) {
     CHECK_HIP(hipEventCreate(&e1));
     if (verify) { // the probe writes what the plan writes
       hipLaunchKernelGGL(mix_probe_kernel, dim3(grid), dim3(FCP_BLOCK_THREADS), 0, st, d_tptr, d_roff[0], d_col_of, roff_stride, arenas[0], batch,
-                         nslots, nsp8, nspans, width, 0);
+                         nslots, nsp8, nspans, deal_tiles, width, 0);
       CHECK_HIP(hipStreamSynchronize(st));
       std::vector<float> out((size_t)batch * width);
       CHECK_HIP(hipMemcpy(out.data(), arenas[0], out_bytes, hipMemcpyDeviceToHost));
@@ -503,7 +498,7 @@ int main(int argc, char **argv) {
           auto run = [&](int n) {
             for (int i = 0; i < n; ++i)
               hipLaunchKernelGGL(mix_probe_kernel, dim3(grid), dim3(FCP_BLOCK_THREADS), 0, st, d_tptr, d_roff[i % requests],
-                                 d_col_of, roff_stride, arenas[i % nring], batch, nslots, nsp8, nspans, width, policies[k]);
+                                 d_col_of, roff_stride, arenas[i % nring], batch, nslots, nsp8, nspans, deal_tiles, width, policies[k]);
           };
           run(warmup > 0 ? warmup : 1);
           CHECK_HIP(hipEventRecord(e0, st));

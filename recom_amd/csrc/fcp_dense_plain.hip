@@ -10,7 +10,9 @@
 // source, bucketize tier, id transform, shard and 64-bit row path:
 //   * ONE coalesced read of the span's record of the per-span image (FcpPlainSpan + FcpPlainCol[], fcp_internal.h) into
 //     LDS instead of kernarg -> slot map -> static + dynamic column records;
-//   * the kernel arguments are 15 separate dwords (FcpPlainLaunch), preloaded into SGPRs where the loader supports it;
+//   * the kernel arguments are 16 separate dwords (FcpPlainLaunch), the first 14 preloaded into SGPRs where the loader
+//     supports it (the last two are bad_ids, wanted on a bad id only);
+//   * the partial last group of eight spans is dealt evenly over the XCDs (fcp_plain_map.h); the grid is unchanged;
 //   * the ids of the (column, row) pairs asked for BEFORE the record has arrived: all a pair thread needs first is its
 //     column's id fact (one dword: where the id stream starts, 4 or 8 bytes per id), and the four facts of a wave's
 //     columns are one 16-byte scalar load; the record goes to LDS, and the block meets its first barrier, behind the
@@ -20,6 +22,7 @@
 // Same bits out as the generic kernel, same bad-id counts (a column that straddles two spans is counted by the block that
 // holds its first slot).
 #include "fcp_fused_bodies.h"
+#include "fcp_plain_map.h"
 
 namespace {
 
@@ -43,27 +46,18 @@ typedef U2 __attribute__((aligned(4))) Id64;
 
 template <int R>
 __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
-fcp_dense_kernel_plain(const char *img, const char *blob, float *out, unsigned long long *bad_ids, int rows, int nslots,
-                       int nsp8, int nlist, int img_stride, int out_stride, int policy) {
+fcp_dense_kernel_plain(const char *img, const char *blob, float *out, int rows, int nslots, int nsp8, int nlist, int img_stride,
+                       int deal_tiles, int out_stride, int policy, unsigned long long *bad_ids) {
   constexpr int V = 4, RB = PlainLds<R>::RB, IDS = PlainLds<R>::IDS;
   __shared__ PlainLds<R> S;
   const int tid = threadIdx.x;
   const int lane = tid & (FCP_WAVE - 1);
   const int wave = tid >> 6;
 
-  // the block mapping of locate_block (one group, every span listed in order): blocks with equal (bid & 7) share an XCD
-  // and are given the same spans
-  const int bid = blockIdx.x;
+  // the block mapping (fcp_plain_map.h): locate_block's, but for the partial last group of eight spans, whose (span, row
+  // tile) pairs are dealt evenly over the eight XCDs when deal_tiles is the grid's number of row tiles (0: locate_block's)
   int idx, tile;
-  if (nsp8 > 0) {
-    const int xcd = bid & 7, j8 = bid >> 3;
-    idx = (j8 % nsp8) * 8 + xcd;
-    tile = j8 / nsp8;
-  } else {
-    idx = bid % (-nsp8);
-    tile = bid / (-nsp8);
-  }
-  if (idx >= nlist) return; // uniform: whole block leaves
+  if (!fcp_plain_locate(blockIdx.x, nsp8, nlist, deal_tiles, idx, tile)) return; // uniform: whole block leaves
   const int q0 = idx * FCP_WAVE, row_blk = tile * RB;
   if (q0 >= nslots || row_blk >= rows) return;
 
@@ -171,9 +165,9 @@ int fcp_launch_dense_plain(const FcpPlainLaunch &P, int grid_blocks, ihipStream_
   const dim3 grid(grid_blocks), block(FCP_BLOCK_THREADS);
   if (stop || flags)
     hipExtLaunchKernelGGL(fcp_dense_kernel_plain<4>, grid, block, 0, s, nullptr, static_cast<hipEvent_t>(stop), flags, P.img, P.blob,
-                          P.out, P.bad_ids, P.rows, P.nslots, P.nsp8, P.nlist, P.img_stride, P.out_stride, P.store_policy);
+                          P.out, P.rows, P.nslots, P.nsp8, P.nlist, P.img_stride, P.deal_tiles, P.out_stride, P.store_policy, P.bad_ids);
   else
-    hipLaunchKernelGGL(fcp_dense_kernel_plain<4>, grid, block, 0, s, P.img, P.blob, P.out, P.bad_ids, P.rows, P.nslots, P.nsp8,
-                       P.nlist, P.img_stride, P.out_stride, P.store_policy);
+    hipLaunchKernelGGL(fcp_dense_kernel_plain<4>, grid, block, 0, s, P.img, P.blob, P.out, P.rows, P.nslots, P.nsp8, P.nlist,
+                       P.img_stride, P.deal_tiles, P.out_stride, P.store_policy, P.bad_ids);
   return (int)hipGetLastError();
 }

@@ -283,6 +283,9 @@ struct fcp_plan {
   // with everything that does not depend on the request or the bound tables; plain_entries names, per FcpPlainCol of the
   // image, its byte offset there and the column (concat position) it describes.
   bool plain_dense = false;
+  // The plain kernel's block mapping (fcp_plain_map.h): the partial last group of eight spans dealt evenly over the XCDs,
+  // or the generic kernel's.  FCP_DIAG=plain_even_deal=0|1 at plan creation; the default is FCP_PLAIN_EVEN_DEAL_DEFAULT.
+  bool plain_even_deal = false;
   int32_t plain_stride = 0, plain_spans = 0, plain_cols_off = 0; // (plain_cols_off: FcpPlainSpan::cols_off of every record)
   std::vector<char> plain_tmpl;
   std::vector<std::pair<uint32_t, int32_t>> plain_entries;

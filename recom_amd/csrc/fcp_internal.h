@@ -159,14 +159,17 @@ struct FcpPlainSpan {      // 80 bytes
   int32_t pad_[2];
   uint8_t lane_col[FCP_WAVE]; // slot of the span -> index of its column among the span's FcpPlainCol
 };
-// kernel arguments: 15 dwords, passed one by one so that they can be preloaded into SGPRs
+// kernel arguments: 16 dwords, passed one by one so that 14 can be preloaded into SGPRs (the kernel takes bad_ids last: it
+// is wanted on a bad id only)
 struct FcpPlainLaunch {
   const char *img;         // the span records
   const char *blob;
   float *out;              // element (0, 0) of the concat group in the arena
   unsigned long long *bad_ids; // nullable
-  int32_t rows, nslots, nsp8, nlist; // as FcpGroupLaunch (the grid and the block mapping are the generic dense kernel's)
+  int32_t rows, nslots, nsp8, nlist; // as FcpGroupLaunch (the grid is the generic dense kernel's)
   int32_t img_stride;      // bytes per span record (a multiple of 16)
+  int32_t deal_tiles;      // the grid's row tiles: the partial last group of eight spans is dealt evenly to the XCDs
+                           // (fcp_plain_map.h); 0: the generic kernel's block mapping
   int32_t out_stride;      // row stride of the output in elements
   int32_t store_policy;    // FcpLaunch::store_through bits 0 and 2
 };

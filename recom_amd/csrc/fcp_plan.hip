@@ -20,6 +20,7 @@
 //   * 64-bit byte offsets and row offsets (the reference's int arithmetic
 //     overflows beyond 2^31).
 #include "fcp_host.h"
+#include "fcp_plain_map.h"
 
 namespace fcph {
 
@@ -455,6 +456,8 @@ void build_plain_template(fcp_plan *p) {
   p->plain_dense = false;
   // FCP_DIAG=dense_generic: a qualifying plan stays on the generic kernel (the tests' seam)
   if (fcp::diag_ll("dense_generic", 0) != 0) return;
+  // FCP_DIAG=plain_even_deal=0|1: the block mapping of the plain kernel's partial last group (the A/B's seam)
+  p->plain_even_deal = fcp::diag_ll("plain_even_deal", FCP_PLAIN_EVEN_DEAL_DEFAULT) != 0;
   const fcp_plan_desc_t &d = p->desc;
   if (p->out_elem != 4 || p->tab_elem != 4 || d.layout != FCP_LAYOUT_CONCAT || d.n_groups != 1 || d.shard_world > 1 || p->vec != 4 || p->wide_rows ||
       p->weighted_kernel || !p->dense_only || p->cols.empty())

@@ -448,6 +448,7 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
     P.nsp8 = G.nsp8;
     P.nlist = G.nlist;
     P.img_stride = p->plain_stride;
+    P.deal_tiles = p->plain_even_deal ? (int32_t)(((int64_t)G.rows + FCP_WAVES_PER_BLOCK * 4 - 1) / (FCP_WAVES_PER_BLOCK * 4)) : 0; // (m.plain: R = 4)
     P.out_stride = p->group_width[0];
     P.store_policy = store_policy;
     const int e = fcp_launch_dense_plain(P, dense_blocks, stream);
