@@ -536,6 +536,60 @@ int fcp_table_update_rows(void *table, int32_t kind, int64_t table_rows, int32_t
  * status order are those of fcp_table_update_rows. */
 int fcp_table_read_rows(float *rows, const void *table, int32_t kind, int64_t table_rows, int32_t dim, const int64_t *row_ids,
                         int64_t n, int32_t device, void *stream);
+/* ---- rows by id, many tables in one call: a model's delta ------------------------------------------------------------------- */
+/* A model has hundreds to thousands of tables and a trainer's delta names rows in most of them; one call of the two entries
+ * above per table is one device guard, one round of argument checks and one small launch per table.  fcp_tables_update_rows
+ * and fcp_tables_read_rows take the whole delta: one fcp_table_rows_t per table (an ENTRY), any mix of formats and dims, and a
+ * number of launches that does not grow with the number of entries.
+ *
+ * `entries` is a HOST array of n_tables records; it is read before the call returns and may then be freed.  Everything an entry
+ * points at is on the device.  The contract is that of the single-table entries, entry by entry: after
+ * fcp_tables_update_rows every byte of every table is what one fcp_table_update_rows call per entry would have left, and
+ * skipped[k] (`skipped`: device int64 [n_tables], or NULL) has grown by what entry k's own call would have added to its
+ * counter; fcp_tables_read_rows leaves in every entry's `rows` the bits fcp_table_read_rows leaves, a row of +0.0 for an id
+ * outside the table.  Alignment, the row limit, asynchrony on `stream`, "no allocation, no synchronisation" and what is
+ * unspecified (duplicate ids, overlap, a concurrent reader on another stream) are inherited unchanged.  Two entries may name
+ * the same table if their ids are pairwise distinct together.
+ *
+ * Limits: n_tables lies in [0, 65536], and the entries of one call name at most 2^40 elements together (n * dim summed: 4 TiB
+ * of float32 rows).  `workspace`: fcp_tables_rows_workspace_bytes bytes on the device, 8-byte aligned, the call's own until
+ * its kernels have run (calls on one stream may share one); the size depends on n_tables alone, is a multiple of 8, does not
+ * decrease with n_tables, and is -1 outside the range.
+ *
+ * Launches.  The entries with n > 0 are sorted into CLASSES: a q8 update by (V, G) — V the largest of 4 | 2 | 1 that divides
+ * dim, G the lanes that share a row: 21 classes; every other update, and every read, by V alone: 3 classes (the format is
+ * read from the entry's record, a wave-uniform branch).  A call enqueues one small launch that installs the entries' records
+ * in the workspace and ONE launch per class present; a block finds its entry by a search over its class's first-block table.
+ * A class of more than 2^30 threads is split as the single-table entries split their launches.  fcp_tables_rows_launches
+ * (host only, no device is touched) returns the number of launches fcp_tables_update_rows enqueues for these entries, the
+ * installing one included — 0 when no entry has rows, at most 25 whatever n_tables is while no class is split — computed by
+ * the function the two entries build their launch list with; fcp_tables_read_rows enqueues what it returns for the same
+ * entries with no q8 table among them, never more.  Invalid arguments: the negative of the status.
+ *
+ * Status, decided in this order (the first two need no device):
+ *   FCP_ERR_INVALID_ARGUMENT  n_tables outside its range; a null `entries` with n_tables > 0; then, over the entries in
+ *                             ascending order, the checks of fcp_table_update_rows in its own order and a non-zero `reserved`
+ *                             (fcp_last_error reads "<entry point>: entry k: " and names the argument between backquotes);
+ *                             more than 2^40 elements; a null `workspace` with n_tables > 0 or a misaligned one; a misaligned
+ *                             `skipped`;
+ *   FCP_OK                    n_tables == 0, or every n == 0: nothing is launched and no device is touched;
+ *   FCP_ERR_NO_DEVICE         no usable gfx950 device;
+ *   FCP_ERR_UNSUPPORTED       `stream` is capturing and there is work to do: the records are installed from the host by every
+ *                             call, which a replay would not repeat (the only such case);
+ *   FCP_ERR_HIP               a kernel launch failed. */
+typedef struct fcp_table_rows {
+  void *table;             /* base of a table [table_rows, dim] in format `kind` (any FCP_TAB_*) */
+  const int64_t *row_ids;  /* device int64 [n] */
+  float *rows;             /* device float32 [n, dim]: the source of an update, the destination of a read */
+  int64_t table_rows, n;
+  int32_t kind, dim;
+  int64_t reserved[2];     /* 0 */
+} fcp_table_rows_t;        /* 64 bytes */
+int64_t fcp_tables_rows_workspace_bytes(int32_t n_tables);
+int32_t fcp_tables_rows_launches(const fcp_table_rows_t *entries, int32_t n_tables);   /* host only */
+int fcp_tables_update_rows(const fcp_table_rows_t *entries, int32_t n_tables, int64_t *skipped /* device [n_tables] or NULL */,
+                           void *workspace, int32_t device, void *stream);
+int fcp_tables_read_rows(const fcp_table_rows_t *entries, int32_t n_tables, void *workspace, int32_t device, void *stream);
 /* ---- a delta's ids made distinct: the last occurrence of an id wins ---------------------------------------------------------- */
 /* fcp_table_update_rows and fcp_table_digest_rows ask that the ids of one call be pairwise distinct and do not check.  Deltas
  * do repeat ids: two incremental checkpoints concatenated before they are applied, a parameter stream replayed after a

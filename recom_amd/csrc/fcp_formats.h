@@ -27,6 +27,18 @@ inline bool known_tab_kind(int kind) { return kind >= 0 && kind < kTabKinds; } /
 inline int64_t row_bytes(int kind, int dim) { return (int64_t)dim * kTab[kind].elem + kTab[kind].row_tail; }
 // the base alignment a plan asks of a table of `kind` whose rows are read `vec` elements at a time (q8: its tail's floats)
 inline int base_alignment(int kind, int vec) { return kTab[kind].row_tail ? 4 : kTab[kind].elem * vec; }
+// How the table kernels walk a float32 row (fcp_table_walk.h): V elements per lane and access, G lanes per row of a q8 row.
+// V: the largest of 4 | 2 | 1 that divides dim
+inline int vec_of(int32_t dim) { return dim % 4 == 0 ? 4 : dim % 2 == 0 ? 2 : 1; }
+// G, the lanes that share a row: 1 for dims <= 4, else the power of two that holds the row's dim / V slots, at most 64
+inline int group_of(int dim, int vec) {
+  int g = 1;
+  if (dim > 4)
+    while (g < dim / vec && g < 64) g <<= 1;
+  return g;
+}
+// a kind in a refusal's text
+inline const char *kind_name(int32_t k) { return k == FCP_TAB_F32 ? "float32" : k == FCP_TAB_BF16 ? "bf16" : k == FCP_TAB_F16 ? "fp16" : "q8"; }
 
 // the kind the plan-wide flag bits name: float32 without a bit, -1 for two bits at once
 inline int kind_of_flags(const Format *t, int n, uint32_t bits) {

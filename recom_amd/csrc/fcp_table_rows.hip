@@ -28,80 +28,33 @@
 #pragma clang fp contract(off)
 
 #include "fcp_table_walk.h" // (behind the pragma: its code rounds every operation once, too)
+#include "fcp_table_rows_bodies.h" // the three bodies and count_skipped: one text with fcp_tables_rows.hip
+#include "fcp_tables_rows_plan.h"  // fcpr::check_row_args: the argument checks, shared with the grouped entries
 
 static_assert(FCP_TAB_BF16 == FCP_OUT_BF16 && FCP_TAB_F16 == FCP_OUT_F16, "st_out_narrow takes the table kind as its output kind");
 
 namespace {
 
-// One vector atomicAdd per wave at most: `mine` is set in the one lane that speaks for a skipped row.  Every lane of the wave
-// gets here (no lane has returned yet), so the wave's first lane is there to issue it.
-__device__ __forceinline__ void count_skipped(unsigned long long *skipped, bool mine) {
-  if (!skipped) return;
-  const unsigned long long m = __ballot(mine);
-  if (m != 0 && (threadIdx.x & 63) == 0) atomicAdd(skipped, (unsigned long long)__popcll(m));
-}
-
-// table: the table's base; ids / src: the first row of this launch; rows: of this launch (< 2^30).  Block = 256 / G rows; a
-// group never straddles a wave, and it is live or not as a whole.
+// The bodies are those of fcp_table_rows_bodies.h with the block index of the launch.
 template <int V, int G>
 __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
     fcp_update_q8_kernel(char *table, const int64_t *ids, const float *src, int32_t rows, int32_t dim, uint64_t table_rows,
                          unsigned long long *skipped) {
-  const int tid = threadIdx.x;
-  const int lane = tid & (G - 1);
-  const int64_t row = (int64_t)blockIdx.x * (FCP_BLOCK_THREADS / G) + tid / G;
-  const bool have = row < rows;
-  const uint64_t id = have ? (uint64_t)*as_global(ids + row) : ~0ull; // the whole group: one address
-  const bool live = have && id < table_rows;
-  count_skipped(skipped, have && !live && lane == 0);
-  quantize_row<V, G>(table + (live ? id : 0) * ((uint64_t)dim + 8), src + row * dim, dim, lane, live);
+  update_q8_body<V, G>(table, ids, src, rows, dim, table_rows, skipped, blockIdx.x);
 }
 
-// n: slots of this launch (<= 2^30, one row of more: < 2^31); ids / src: the first row of this launch; spr: slots per row,
-// dim / V; kind: FCP_TAB_F32 | _BF16 | _F16, the same for every wave
 template <int V>
 __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
     fcp_update_rows_kernel(char *table, const int64_t *ids, const float *src, uint32_t n, uint32_t spr, int32_t dim, int32_t kind,
                            uint64_t table_rows, unsigned long long *skipped) {
-  const uint32_t i = blockIdx.x * FCP_BLOCK_THREADS + threadIdx.x;
-  const bool have = i < n;
-  const uint32_t r = have ? i / spr : 0;
-  const uint32_t e = (i - r * spr) * V;
-  const uint64_t id = have ? (uint64_t)*as_global(ids + r) : ~0ull;
-  const bool live = have && id < table_rows;
-  count_skipped(skipped, have && !live && e == 0);
-  if (!live) return;
-  const VF<V> x = ld_f32<V>(src + (uint64_t)i * V);
-  if (kind == FCP_TAB_F32)
-    st_f32<V>(reinterpret_cast<float *>(table) + (id * (uint64_t)dim + e), x);
-  else
-    st_out_narrow<V>(table + 2 * (id * (uint64_t)dim + e), x, FCP_ST_PLAIN, kind);
+  update_rows_body<V>(table, ids, src, n, spr, dim, kind, table_rows, skipped, blockIdx.x);
 }
 
-// dst / ids: the first row of this launch; kind: any FCP_TAB_* value, the same for every wave
 template <int V>
 __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
     fcp_read_rows_kernel(float *dst, const char *table, const int64_t *ids, uint32_t n, uint32_t spr, int32_t dim, int32_t kind,
                          uint64_t table_rows) {
-  const uint32_t i = blockIdx.x * FCP_BLOCK_THREADS + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t r = i / spr;
-  const uint32_t e = (i - r * spr) * V;
-  const uint64_t id = (uint64_t)*as_global(ids + r);
-  VF<V> x = vzero<V>();
-  if (id < table_rows) {
-    if (kind == FCP_TAB_F32) {
-      x = ld_f32<V>(reinterpret_cast<const float *>(table) + (id * (uint64_t)dim + e));
-    } else if (kind == FCP_TAB_Q8) {
-      const char *row = table + id * ((uint64_t)dim + 8);
-      x = ld_q8<V>(row + e, row + dim);
-    } else {
-      typedef typename NarrowType<V>::T T;
-      const T t = *as_global(reinterpret_cast<const T *>(table + 2 * (id * (uint64_t)dim + e)));
-      x = widen16<V>(t, kind);
-    }
-  }
-  st_f32<V>(dst + (uint64_t)i * V, x);
+  read_rows_body<V>(dst, table, ids, n, spr, dim, kind, table_rows, blockIdx.x);
 }
 
 // G: 1 for dims <= 4, else the power of two that holds the row's slots, at most 64 (group_of)
@@ -144,28 +97,14 @@ void read(float *dst, const void *table, int kind, const int64_t *ids, int64_t n
   }
 }
 
-// The argument checks both entries share, in the stated order; `who` is the entry's name.  The argument is named between
-// backquotes: `rows` is also part of two other arguments' names.
+// The argument checks both entries share, in the stated order (fcpr::check_row_args, fcp_tables_rows_plan.cc: the grouped
+// entries run the same text per entry); `who` is the entry's name.
 int check_args(const char *who, const void *table, int32_t kind, int64_t table_rows, int32_t dim, const void *row_ids, const void *rows,
                int64_t n, const void *skipped) {
-  const std::string w = std::string(who) + ": ";
-  if (n < 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`n` is negative");
-  if (n >= fcpf::kRowLimit) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`n` must stay below 2^32 - 3");
-  if (table_rows < 1 || table_rows >= fcpf::kRowLimit)
-    return fail(FCP_ERR_INVALID_ARGUMENT, w + "`table_rows` must lie in [1, 2^32 - 3), a plan's row limit");
-  if (dim <= 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`dim` must be positive");
-  if (!fcpf::known_tab_kind(kind)) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`kind` is no FCP_TAB_* value");
-  if (n > 0 && !table) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`table` is null");
-  if (n > 0 && !row_ids) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`row_ids` is null");
-  if (n > 0 && !rows) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`rows` is null");
-  const int vec = vec_of(dim);
-  if ((uintptr_t)table % fcpf::base_alignment(kind, vec))
-    return fail(FCP_ERR_INVALID_ARGUMENT, w + "`table` is not " + std::to_string(fcpf::base_alignment(kind, vec)) + "-byte aligned (a " +
-                                              kind_name(kind) + " table of this dim)");
-  if ((uintptr_t)rows % (4 * vec))
-    return fail(FCP_ERR_INVALID_ARGUMENT, w + "`rows` is not " + std::to_string(4 * vec) + "-byte aligned (float32 rows of this dim)");
-  if ((uintptr_t)row_ids % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`row_ids` is not 8-byte aligned");
-  if ((uintptr_t)skipped % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`skipped` is not 8-byte aligned");
+  std::string why;
+  const int rc = fcpr::check_row_args(std::string(who) + ": ", table, kind, table_rows, dim, row_ids, rows, n, &why);
+  if (rc) return fail(rc, why);
+  if ((uintptr_t)skipped % 8) return fail(FCP_ERR_INVALID_ARGUMENT, std::string(who) + ": `skipped` is not 8-byte aligned");
   return FCP_OK;
 }
 

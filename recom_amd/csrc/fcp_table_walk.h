@@ -122,15 +122,9 @@ template <int V, int G> __device__ __forceinline__ void quantize_row(char *drow,
 
 inline dim3 blocks_for(int64_t threads) { return dim3((uint32_t)((threads + FCP_BLOCK_THREADS - 1) / FCP_BLOCK_THREADS)); }
 
-// V: the largest of 4 | 2 | 1 that divides dim
-inline int vec_of(int32_t dim) { return dim % 4 == 0 ? 4 : dim % 2 == 0 ? 2 : 1; }
-// G, the lanes that share a row: 1 for dims <= 4, else the power of two that holds the row's dim / V slots, at most 64
-inline int group_of(int dim, int vec) {
-  int g = 1;
-  if (dim > 4)
-    while (g < dim / vec && g < 64) g <<= 1;
-  return g;
-}
+// V and G of a dim: fcp_formats.h has the two rules (the host-only units read them too)
+using fcpf::group_of;
+using fcpf::vec_of;
 
 // The host's dispatch on a template argument: f(std::integral_constant<int, N>{}) for the N of Ns... that n equals — the caller
 // writes [&](auto N) { ... decltype(N)::value ... }.  n is one of them by construction (group_of, vec_of).
@@ -138,6 +132,6 @@ template <int... Ns, class F> void with_one_of(int n, F f) { (void)((n == Ns && 
 template <class F> void with_group(int g, F f) { with_one_of<1, 2, 4, 8, 16, 32, 64>(g, f); }
 template <class F> void with_vec(int vec, F f) { with_one_of<4, 2, 1>(vec, f); }
 
-inline const char *kind_name(int32_t k) { return k == FCP_TAB_F32 ? "float32" : k == FCP_TAB_BF16 ? "bf16" : k == FCP_TAB_F16 ? "fp16" : "q8"; }
+using fcpf::kind_name;
 
 } // namespace

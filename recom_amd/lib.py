@@ -158,6 +158,12 @@ class OutputError(C.Structure):
                 ("reserved", C.c_int64)]
 
 
+class TableRows(C.Structure):
+    """fcp_table_rows_t: one entry of fcp_tables_update_rows / fcp_tables_read_rows"""
+    _fields_ = [("table", C.c_void_p), ("row_ids", C.c_void_p), ("rows", C.c_void_p), ("table_rows", C.c_int64), ("n", C.c_int64),
+                ("kind", C.c_int32), ("dim", C.c_int32), ("reserved", C.c_int64 * 2)]
+
+
 class PrivateStreamsStats(C.Structure):
     """fcp_private_streams_stats_t"""
     _fields_ = [("supervised_stream", C.c_void_p), ("requests", C.c_int64), ("lane_requests", C.c_int64), ("evaluations", C.c_int64),
@@ -212,6 +218,7 @@ EXPORTS = [
     "fcp_table_delta_workspace_bytes", "fcp_table_delta_distinct",
     "fcp_table_diff_workspace_bytes", "fcp_table_diff",
     "fcp_outputs_compare_workspace_bytes", "fcp_outputs_compare",
+    "fcp_tables_rows_workspace_bytes", "fcp_tables_rows_launches", "fcp_tables_update_rows", "fcp_tables_read_rows",
 ]
 
 _lib = None
@@ -409,6 +416,13 @@ def load() -> C.CDLL:
         L.fcp_outputs_compare_workspace_bytes.argtypes = [C.c_int32]
         L.fcp_outputs_compare.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    if hasattr(L, "fcp_tables_update_rows"):
+        L.fcp_tables_rows_workspace_bytes.restype = C.c_int64
+        L.fcp_tables_rows_workspace_bytes.argtypes = [C.c_int32]
+        L.fcp_tables_rows_launches.restype = C.c_int32
+        L.fcp_tables_rows_launches.argtypes = [C.POINTER(TableRows), C.c_int32]
+        L.fcp_tables_update_rows.argtypes = [C.POINTER(TableRows), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.fcp_tables_read_rows.argtypes = [C.POINTER(TableRows), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     if L.fcp_abi_version() != FCP_ABI_VERSION:
         raise ImportError("libfcp_hip.so ABI version mismatch; rebuild")
     _lib = L

@@ -192,6 +192,92 @@ def read_rows(table, row_ids, out=None, stream: Optional[int] = None):
     return out
 
 
+# ---- rows by id, many tables in one call (fcp_tables_update_rows / fcp_tables_read_rows) --------------------------------------
+def _grouped_entries(torch, tables_, row_ids, rows, what: str):
+    """The ``fcp_table_rows_t`` array of equally long sequences, each entry validated as ``update_rows`` / ``read_rows``
+    validate theirs, and the one device all of it lives on (``None`` for no entries)."""
+    if len(row_ids) != len(tables_) or len(rows) != len(tables_):
+        raise ValueError(f"tables names {len(tables_)} entries, row_ids {len(row_ids)}, {what} {len(rows)}")
+    entries = (_lib.TableRows * max(len(tables_), 1))()
+    device = None
+    for k, (t, ids, r) in enumerate(zip(tables_, row_ids, rows)):
+        try:
+            name, dim = _kind_and_dim(t, "table")
+            n = _ids_of(torch, t, ids)
+            _rows_of(torch, t, dim, n, r, what)
+        except ValueError as e:
+            raise ValueError(f"entry {k}: {e}") from None
+        if device is None:
+            device = t.device
+        elif t.device != device:
+            raise ValueError(f"entry {k}: table is on {t.device}, entry 0's on {device}")
+        entries[k] = _lib.TableRows(t.data_ptr(), ids.data_ptr(), r.data_ptr(), int(t.shape[0]), n, _lib.TABLE_KINDS[name], dim)
+    return entries, device
+
+
+def _grouped_workspace(torch, L, device, stream: int, n_tables: int):
+    """the call's workspace, allocated as that stream's (``_digest_buffers`` says why)"""
+    with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device)):
+        return torch.empty((int(L.fcp_tables_rows_workspace_bytes(n_tables)) // 8,), dtype=torch.int64, device=device)
+
+
+def update_rows_grouped(tables, row_ids, rows, skipped=None, stream: Optional[int] = None):
+    """``fcp_tables_update_rows``: ``update_rows`` for a whole model's delta in ONE call — ``tables``, ``row_ids`` and ``rows``
+    are equally long sequences, entry k what ``update_rows(tables[k], row_ids[k], rows[k])`` takes, in any mix of formats and
+    dims on one device; the number of launches does not grow with their length.  Every table ends up, byte for byte, as
+    after one ``update_rows`` per entry.  ``skipped``: one int64 ``[len(tables)]`` device tensor; element k is increased by
+    entry k's ids outside its table (the caller zeroes it).  Two entries may name one table if their ids are distinct
+    together.  Asynchronous on ``stream`` (torch's current stream of the device by default).  Returns ``tables``."""
+    import torch
+    entries, device = _grouped_entries(torch, tables, row_ids, rows, "rows")
+    n_tables = len(tables)
+    if skipped is not None:
+        if skipped.dtype != torch.int64 or skipped.dim() != 1 or skipped.shape[0] != n_tables or not skipped.is_contiguous() or \
+                (device is not None and skipped.device != device):
+            raise ValueError("skipped is a contiguous int64 [len(tables)] tensor on the tables' device")
+    if device is None:
+        return tables
+    L = _lib.load()
+    if stream is None:
+        stream = torch.cuda.current_stream(device).cuda_stream
+    workspace = _grouped_workspace(torch, L, device, stream, n_tables)
+    status = L.fcp_tables_update_rows(entries, n_tables, C.c_void_p(skipped.data_ptr()) if skipped is not None else None,
+                                      C.c_void_p(workspace.data_ptr()), device.index or 0, C.c_void_p(stream))
+    _lib.check(status, "fcp_tables_update_rows")
+    return tables
+
+
+def read_rows_grouped(tables, row_ids, out=None, stream: Optional[int] = None) -> list:
+    """``fcp_tables_read_rows``: ``read_rows`` of many tables in ONE call — entry k gives what
+    ``read_rows(tables[k], row_ids[k])`` gives, bit for bit, a row of +0.0 for an id outside the table.  ``out``: a sequence
+    of float32 ``[n_k, dim_k]`` tensors on the tables' device, allocated when not given.  Asynchronous on ``stream`` (torch's
+    current stream of the device by default).  Returns the list of outputs."""
+    import torch
+    if len(row_ids) != len(tables):
+        raise ValueError(f"tables names {len(tables)} entries, row_ids {len(row_ids)}")
+    if stream is None and len(tables) and getattr(tables[0], "is_cuda", False):
+        stream = torch.cuda.current_stream(tables[0].device).cuda_stream
+    if out is None:
+        out = []
+        for k, (t, ids) in enumerate(zip(tables, row_ids)):
+            try:
+                _name, dim = _kind_and_dim(t, "table")
+                n = _ids_of(torch, t, ids)
+            except ValueError as e:
+                raise ValueError(f"entry {k}: {e}") from None
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=t.device)):
+                out.append(torch.empty((n, dim), dtype=torch.float32, device=t.device))
+    out = list(out)
+    entries, device = _grouped_entries(torch, tables, row_ids, out, "out")
+    if device is None:
+        return out
+    L = _lib.load()
+    workspace = _grouped_workspace(torch, L, device, stream, len(tables))
+    status = L.fcp_tables_read_rows(entries, len(tables), C.c_void_p(workspace.data_ptr()), device.index or 0, C.c_void_p(stream))
+    _lib.check(status, "fcp_tables_read_rows")
+    return out
+
+
 def update_from_host(table, ids_cpu, rows_cpu, chunk_rows: int = 1 << 16):
     """A host delta — ``ids_cpu`` int64 ``[n]`` and ``rows_cpu`` float32 ``[n, dim]``, torch CPU tensors — into the device
     ``table``, streamed through ONE pinned bounce buffer and one device buffer of ``chunk_rows`` rows (and as many ids), as
