@@ -4,6 +4,7 @@
 #pragma once
 #include <cstdint>
 #include <cstring>
+#include <string>
 
 #include "../../include/fcp_hip.h"
 
@@ -39,6 +40,18 @@ inline int group_of(int dim, int vec) {
 }
 // a kind in a refusal's text
 inline const char *kind_name(int32_t k) { return k == FCP_TAB_F32 ? "float32" : k == FCP_TAB_BF16 ? "bf16" : k == FCP_TAB_F16 ? "fp16" : "q8"; }
+
+// Refusals the table entries share, to go behind the entry's "name: " (the host tests assert the sentences).
+// `name` lies at an address that is no multiple of align; what: " (...)" or nothing
+inline std::string not_aligned(const char *name, int align, const std::string &what = std::string()) {
+  return std::string("`") + name + "` is not " + std::to_string(align) + "-byte aligned" + what;
+}
+// a call's count `name` (n: ids or rows) and the table's rows against kRowLimit; empty when both pass
+inline std::string row_limit_refusal(const char *name, int64_t n, int64_t table_rows) {
+  if (n >= kRowLimit) return std::string("`") + name + "` must stay below 2^32 - 3";
+  if (table_rows < 1 || table_rows >= kRowLimit) return "`table_rows` must lie in [1, 2^32 - 3), a plan's row limit";
+  return std::string();
+}
 
 // the kind the plan-wide flag bits name: float32 without a bit, -1 for two bits at once
 inline int kind_of_flags(const Format *t, int n, uint32_t bits) {

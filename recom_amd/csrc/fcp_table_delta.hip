@@ -3,9 +3,10 @@
 // (fcp_table_digest.hip) see it — both ask for distinct ids and neither checks.  No sort and no lock: the winner of a row is the
 // MAXIMUM of the positions that name it, and a maximum commutes.  The reference has no counterpart.
 //
-// The workspace holds, in this order: kDeltaBlocks + 1 records of 32 bytes (one per block of the fixed grid, and the totals),
-// an open-addressed hash table of `cells` {uint32 row, uint32 pos1} cells — cells a power of two, at least 2 n and at least
-// kDeltaMinCells, so the load stays at or below 0.5 and an empty cell always exists — and one flag byte per position.  A row's
+// The winners are selected by the classify / fold / compact pipeline of fcp_select_compact.h.  The workspace holds, in this
+// order: kDeltaBlocks + 1 of its records (one per block of the fixed grid, and the totals), an open-addressed hash table of
+// `cells` {uint32 row, uint32 pos1} cells — cells a power of two, at least 2 n and at least kDeltaMinCells, so the load
+// stays at or below 0.5 and an empty cell always exists — and one flag byte per position.  A row's
 // home cell is the top bits of row * kDeltaHashMul (64-bit, Fibonacci hashing: ids that share low bits, as the ids of one
 // shard do, still spread); probing is linear.  The phases are separate launches; launch boundaries order them, no block ever
 // waits for another, and every probe loop is bounded by the number of cells.
@@ -22,16 +23,13 @@
 //                     costs one global atomic per block, not one per position.  (One insert_global per position, no LDS, a
 //                     build of the commit that introduced the kernel, is as fast on distinct ids and 7x (Zipf) to 260x
 //                     (one row) slower on repeated ones: profiles/table_delta.txt)
-//   fcp_delta_classify_kernel   kDeltaBlocks blocks at the most, block b owns the contiguous chunk [b * chunk, (b + 1) * chunk) of
-//                     positions, chunk a multiple of kDeltaTile.  Position i with an id inside the table looks its row up (the
-//                     row is there: the insert phase has run) and WINS when the cell's pos1 is i + 1.  One flag byte per
-//                     position (1: wins), and ONE partial record per block: winners, duplicates, skipped.
-//   fcp_delta_fold_kernel       one wave: exclusive offsets of the blocks' winners into their records, the totals record, the report.
-//   fcp_delta_compact_kernel<V, G>   the classify grid again.  Per tile of kDeltaTile positions: winners are ranked by ballot and
-//                     popcount inside a wave and a scan of the four wave counts, so winner number k of the call — in ascending
-//                     position: stable — writes ids_out[k] and pos_out[k]; positions i >= m write the -1 tails.  V > 0: the
-//                     tile's winners' rows are then copied by power-of-two groups of G lanes, V 32-bit words per load and
-//                     store (integer vectors: bits, not floats), rows[p_k] -> rows_out[k].  V == 0: ids only.
+//   fcp_delta_classify_kernel   the selection grid, kDeltaBlocks blocks at the most.  Position i with an id inside the table looks
+//                     its row up (the row is there: the insert phase has run) and WINS when the cell's pos1 is i + 1.  One
+//                     flag byte per position (1: wins), and ONE partial record per block: winners, duplicates, skipped.
+//   fcp_delta_fold_kernel       one wave: the records' offsets (select_offsets), the totals record, the report.
+//   fcp_delta_compact_kernel<V, G>   select_compact: winner number k of the call, in ascending position, writes ids_out[k] — its
+//                     id, loaded before the ballot — and pos_out[k]; positions i >= m write the -1 tails.  V > 0: the
+//                     winners' rows as bits, rows[p_k] -> rows_out[k].  V == 0: ids only.
 // Every output byte is a function of the arguments alone: the hash, the grid and the order of the atomics decide only WHERE a
 // row's cell lies and WHEN its maximum is reached.  Nothing is dereferenced by an id's value but the cell it maps to.
 // All global atomics are vector forms at agent scope, results unused except the compare-and-swap's; nothing scalar.
@@ -44,11 +42,12 @@
 
 #include "fcp_table_walk.h" // vec_of, group_of, with_vec, with_group: the rows' V and G, the host's dispatch
 #include "fcp_block_fold.h" // wave_fold, block_fold; the block's LDS row table, kEmptyCell
+#include "fcp_select_compact.h" // select_grid, select_offsets, select_compact, with_compact_shape: the selection's shared tail
 
 namespace {
 
 constexpr int kDeltaThreads = FCP_BLOCK_THREADS;
-constexpr int kDeltaTile = kDeltaThreads;           // positions of one step of a classify / compact block
+constexpr int kDeltaTile = kSelectTile;             // positions of one step of a classify / compact block
 constexpr int kDeltaBlocks = 1024;                  // the fixed grid of classify / compact; also the partial records
 constexpr int kDeltaMinChunkTiles = 4;              // a block's chunk is at least this many tiles
 constexpr int kDeltaInsertIdsPerThread = 4;
@@ -58,7 +57,6 @@ constexpr int kDeltaClearBlocks = 4096;
 constexpr int kDeltaSlots = 2048;                   // cells of a block's LDS table: 2 x 8 KiB, for a tile of 1024 positions
 constexpr int64_t kDeltaMinCells = 64;
 constexpr uint64_t kDeltaHashMul = 0x9E3779B97F4A7C15ull;
-static_assert(kDeltaThreads == 256, "four waves per block: the compact kernel's scan of wave counts");
 
 // What a block of the classify phase counted, and, once the fold has run, where its winners go.  32 bytes.
 struct DeltaPartial {
@@ -190,22 +188,8 @@ __global__ void __launch_bounds__(64)
   const int lane = threadIdx.x;
   const int b0 = lane * per, b1 = b0 + per < nblocks ? b0 + per : nblocks;
   DeltaCounts<int64_t> c = {0, 0, 0};
-  for (int b = b0; b < b1; ++b) {
-    c.winners += partials[b].winners;
-    c.duplicates += partials[b].duplicates;
-    c.skipped += partials[b].skipped;
-  }
-  int64_t before = c.winners; // inclusive scan of the lanes' winners, then made exclusive
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int64_t up = __shfl_up(before, d, 64);
-    if (lane >= d) before += up;
-  }
-  before -= c.winners;
-  for (int b = b0; b < b1; ++b) {
-    partials[b].offset = before;
-    before += partials[b].winners;
-  }
+  for (int b = b0; b < b1; ++b) fold(c, DeltaCounts<int64_t>{partials[b].winners, partials[b].duplicates, partials[b].skipped});
+  select_offsets<kDeltaBlocks>(partials, nblocks, c.winners);
   wave_fold(c);
   if (lane != 0) return;
   partials[kDeltaBlocks] = c;
@@ -216,12 +200,6 @@ __global__ void __launch_bounds__(64)
   r.skipped = c.skipped;
   *report = r;
 }
-
-// V 32-bit words as one load / store at the rows' alignment 4 * V
-template <int V> struct DeltaWords;
-template <> struct DeltaWords<4> { typedef uint32_t __attribute__((ext_vector_type(4))) T; };
-template <> struct DeltaWords<2> { typedef uint32_t __attribute__((ext_vector_type(2))) T; };
-template <> struct DeltaWords<1> { typedef uint32_t T; };
 
 struct DeltaCompact {
   const void *ids;
@@ -234,55 +212,23 @@ struct DeltaCompact {
   int32_t is64, dim;
 };
 
+// what select_compact asks of the unit: a position's id (loaded before the ballot), a winner's outputs, the -1 tails
+struct DeltaEmit {
+  const DeltaCompact &A;
+  __device__ __forceinline__ uint64_t prepare(int64_t i, bool have) const { return have ? ld_id(A.ids, i, A.is64 != 0) : 0; }
+  __device__ __forceinline__ void emit(int64_t k, int64_t i, uint64_t id) const {
+    *as_global(A.ids_out + k) = (int64_t)id;
+    if (A.pos_out) *as_global(A.pos_out + k) = i;
+  }
+  __device__ __forceinline__ void tail(int64_t i) const {
+    *as_global(A.ids_out + i) = -1;
+    if (A.pos_out) *as_global(A.pos_out + i) = -1;
+  }
+};
+
 // V == 0: ids only (rows and rows_out are null and never read); else G lanes copy a winner's row, V words at a time
 template <int V, int G> __global__ void __launch_bounds__(kDeltaThreads) fcp_delta_compact_kernel(const DeltaCompact A) {
-  __shared__ uint32_t s_list[kDeltaTile]; // the tile's winners, by rank: their thread
-  __shared__ uint32_t s_count[kDeltaThreads / 64];
-  const int tid = threadIdx.x;
-  const int wave = tid / 64;
-  const int64_t c0 = (int64_t)blockIdx.x * A.chunk;
-  const int64_t c1 = c0 + A.chunk < A.n ? c0 + A.chunk : A.n;
-  const int64_t m = A.partials[kDeltaBlocks].winners;
-  int64_t k0 = A.partials[blockIdx.x].offset; // the output index of the tile's first winner
-  for (int64_t t0 = c0; t0 < c1; t0 += kDeltaTile) {
-    const int64_t i = t0 + tid;
-    const bool have = i < c1;
-    const bool win = have && *as_global(A.flags + i) != 0;
-    const uint64_t id = have ? ld_id(A.ids, i, A.is64 != 0) : 0;
-    const unsigned long long ballot = __ballot(win);
-    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
-    if ((tid & 63) == 0) s_count[wave] = (uint32_t)__popcll(ballot);
-    __syncthreads();
-    uint32_t rank = below, total = 0;
-#pragma unroll
-    for (int w = 0; w < kDeltaThreads / 64; ++w) {
-      const uint32_t c = s_count[w];
-      if (w < wave) rank += c;
-      total += c;
-    }
-    if (win) {
-      *as_global(A.ids_out + (k0 + rank)) = (int64_t)id;
-      if (A.pos_out) *as_global(A.pos_out + (k0 + rank)) = i;
-      if constexpr (V > 0) s_list[rank] = (uint32_t)tid;
-    }
-    if (have && i >= m) { // the tails: indices no winner has
-      *as_global(A.ids_out + i) = -1;
-      if (A.pos_out) *as_global(A.pos_out + i) = -1;
-    }
-    __syncthreads(); // s_list is whole; s_count may be written again
-    if constexpr (V > 0) {
-      typedef typename DeltaWords<V>::T W;
-      const int lane = tid & (G - 1);
-      const int nslots = A.dim / V;
-      for (uint32_t j = (uint32_t)(tid / G); j < total; j += kDeltaThreads / G) {
-        const FCP_GLOBAL W *src = as_global(reinterpret_cast<const W *>(A.rows + (t0 + (int64_t)s_list[j]) * A.dim));
-        FCP_GLOBAL W *dst = as_global(reinterpret_cast<W *>(A.rows_out + (k0 + (int64_t)j) * A.dim));
-        for (int slot = lane; slot < nslots; slot += G) dst[slot] = src[slot];
-      }
-      __syncthreads(); // the copies have read s_list
-    }
-    k0 += total;
-  }
+  select_compact<V, G, kDeltaBlocks>(A.flags, A.partials, A.n, A.chunk, A.rows, A.rows_out, A.dim, DeltaEmit{A});
 }
 
 int64_t cells_for(int64_t n) {
@@ -304,9 +250,7 @@ extern "C" int fcp_table_delta_distinct(const void *row_ids, int32_t id_bytes, c
                                         void *workspace, int32_t device, void *stream) {
   const std::string w = "fcp_table_delta_distinct: ";
   if (n < 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`n` is negative");
-  if (n >= fcpf::kRowLimit) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`n` must stay below 2^32 - 3");
-  if (table_rows < 1 || table_rows >= fcpf::kRowLimit)
-    return fail(FCP_ERR_INVALID_ARGUMENT, w + "`table_rows` must lie in [1, 2^32 - 3), a plan's row limit");
+  if (const std::string why = fcpf::row_limit_refusal("n", n, table_rows); !why.empty()) return fail(FCP_ERR_INVALID_ARGUMENT, w + why);
   if (id_bytes != 4 && id_bytes != 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`id_bytes` is 4 (int32 ids) or 8 (int64 ids)");
   if (rows && dim <= 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`dim` must be positive");
   if (rows_out && !rows) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`rows_out` without `rows`: ids only takes both null");
@@ -316,16 +260,13 @@ extern "C" int fcp_table_delta_distinct(const void *row_ids, int32_t id_bytes, c
   if (n > 0 && !row_ids) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`row_ids` is null");
   if (n > 0 && !ids_out) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`ids_out` is null");
   const int vec = rows ? vec_of(dim) : 1;
-  const auto misaligned = [&](const char *name, const void *p, int align, const char *what) {
-    return fail(FCP_ERR_INVALID_ARGUMENT, w + "`" + name + "` is not " + std::to_string(align) + "-byte aligned" + what);
-  };
-  if ((uintptr_t)row_ids % (uintptr_t)id_bytes) return misaligned("row_ids", row_ids, id_bytes, "");
-  if ((uintptr_t)rows % (4 * vec)) return misaligned("rows", rows, 4 * vec, " (float32 rows of this dim)");
-  if ((uintptr_t)ids_out % 8) return misaligned("ids_out", ids_out, 8, "");
-  if ((uintptr_t)rows_out % (4 * vec)) return misaligned("rows_out", rows_out, 4 * vec, " (float32 rows of this dim)");
-  if ((uintptr_t)pos_out % 8) return misaligned("pos_out", pos_out, 8, "");
-  if ((uintptr_t)report % 8) return misaligned("report", report, 8, "");
-  if ((uintptr_t)workspace % 8) return misaligned("workspace", workspace, 8, "");
+  if ((uintptr_t)row_ids % (uintptr_t)id_bytes) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("row_ids", id_bytes));
+  if ((uintptr_t)rows % (4 * vec)) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("rows", 4 * vec, " (float32 rows of this dim)"));
+  if ((uintptr_t)ids_out % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("ids_out", 8));
+  if ((uintptr_t)rows_out % (4 * vec)) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("rows_out", 4 * vec, " (float32 rows of this dim)"));
+  if ((uintptr_t)pos_out % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("pos_out", 8));
+  if ((uintptr_t)report % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("report", 8));
+  if ((uintptr_t)workspace % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("workspace", 8));
 
   DeltaPartial *partials = static_cast<DeltaPartial *>(workspace);
   const int64_t cells = cells_for(n);
@@ -334,10 +275,7 @@ extern "C" int fcp_table_delta_distinct(const void *row_ids, int32_t id_bytes, c
   T.mask = (uint64_t)cells - 1;
   T.shift = 64 - __builtin_ctzll((unsigned long long)cells);
   uint8_t *flags = reinterpret_cast<uint8_t *>(T.cells) + cells * 8;
-  // the classify / compact grid: chunks of whole tiles, at least kDeltaMinChunkTiles of them, at most kDeltaBlocks chunks
-  const int64_t tiles = (n + kDeltaTile - 1) / kDeltaTile;
-  const int64_t chunk = std::max<int64_t>(kDeltaMinChunkTiles, (tiles + kDeltaBlocks - 1) / kDeltaBlocks) * kDeltaTile;
-  const int nblocks = (int)((n + chunk - 1) / chunk);
+  const auto grid = select_grid(n, kDeltaBlocks, kDeltaMinChunkTiles); // of classify and compact
   const int64_t insert_tiles = (n + kDeltaInsertTile - 1) / kDeltaInsertTile;
   DeltaCompact A;
   A.ids = row_ids;
@@ -348,7 +286,7 @@ extern "C" int fcp_table_delta_distinct(const void *row_ids, int32_t id_bytes, c
   A.pos_out = pos_out;
   A.rows_out = rows_out;
   A.n = n;
-  A.chunk = chunk;
+  A.chunk = grid.chunk;
   A.is64 = id_bytes == 8;
   A.dim = dim;
   return on_device("fcp_table_delta_distinct", device, stream, [&](hipStream_t s) {
@@ -358,19 +296,13 @@ extern "C" int fcp_table_delta_distinct(const void *row_ids, int32_t id_bytes, c
       hipLaunchKernelGGL(fcp_delta_clear_kernel, dim3(clear_blocks), threads, 0, s, T.cells, (uint64_t)cells);
       hipLaunchKernelGGL(fcp_delta_insert_kernel<kDeltaSlots>, dim3((unsigned)std::min<int64_t>(insert_tiles, kDeltaInsertMaxBlocks)), threads,
                          0, s, T, row_ids, A.is64, n, (uint64_t)table_rows);
-      hipLaunchKernelGGL(fcp_delta_classify_kernel, dim3(nblocks), threads, 0, s, T, row_ids, A.is64, n, chunk, (uint64_t)table_rows, flags,
+      hipLaunchKernelGGL(fcp_delta_classify_kernel, dim3(grid.nblocks), threads, 0, s, T, row_ids, A.is64, n, grid.chunk, (uint64_t)table_rows, flags,
                          partials);
     }
-    hipLaunchKernelGGL(fcp_delta_fold_kernel, dim3(1), dim3(64), 0, s, partials, (int32_t)nblocks, n, report);
+    hipLaunchKernelGGL(fcp_delta_fold_kernel, dim3(1), dim3(64), 0, s, partials, (int32_t)grid.nblocks, n, report);
     if (n == 0) return;
-    if (!rows) {
-      hipLaunchKernelGGL((fcp_delta_compact_kernel<0, 1>), dim3(nblocks), threads, 0, s, A);
-      return;
-    }
-    with_vec(vec, [&](auto v) {
-      with_group(group_of(dim, vec), [&](auto g) {
-        hipLaunchKernelGGL((fcp_delta_compact_kernel<decltype(v)::value, decltype(g)::value>), dim3(nblocks), threads, 0, s, A);
-      });
+    with_compact_shape(rows != nullptr, dim, vec, [&](auto v, auto g) {
+      hipLaunchKernelGGL((fcp_delta_compact_kernel<decltype(v)::value, decltype(g)::value>), dim3(grid.nblocks), threads, 0, s, A);
     });
   });
 }

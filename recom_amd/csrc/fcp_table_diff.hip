@@ -7,11 +7,11 @@
 // is made of — RowSlots, minmax and q8_code of fcp_table_walk.h, narrow_bf16 / narrow_f16 of fcp_fused_bodies.h — and nothing is
 // written to the table.  The reference reads float32 tables only and has no counterpart.
 //
-// The workspace holds, in this order: kDiffBlocks + 1 records of 32 bytes (one per block of the fixed grid, and the totals) and
-// one flag byte per row.  The phases are separate launches; launch boundaries order them and no block ever waits for another.
+// The changed rows are selected by the classify / fold / compact pipeline of fcp_select_compact.h.  The workspace holds, in
+// this order: kDiffBlocks + 1 of its records (one per block of the fixed grid, and the totals) and one flag byte per row.
 //
-//   fcp_diff_classify_kernel<F, V, G>   kDiffBlocks blocks at the most, block b owns the contiguous chunk [b * chunk, (b + 1) * chunk)
-//                     of rows, chunk a multiple of kDiffTile.  A row is handled by the power-of-two group of G lanes the
+//   fcp_diff_classify_kernel<F, V, G>   the selection grid, kDiffBlocks blocks at the most; a position is a row of the call.
+//                     A row is handled by the power-of-two group of G lanes the
 //                     quantiser gives it (group_of), every lane owning V-element slots; a block takes 256 / G rows at a time,
 //                     kDiffUnroll (G == 64: 2) of such steps at once — their loads are issued before the first compare.  F is
 //                     what lies between the source and the stored bytes:
@@ -26,12 +26,10 @@
 //                     The lanes' differences are ORed over the group by __shfl_xor butterflies.  One flag byte per row
 //                     (1: changed) from the group's first lane, and ONE partial record per block: changed, first, last.
 //                     Lanes of rows beyond the chunk take part in the exchanges and touch no memory.
-//   fcp_diff_fold_kernel        one wave: exclusive offsets of the blocks' changed rows into their records, the totals record, the report.
-//   fcp_diff_compact_kernel<V, G>   the classify grid again, a thread per row.  Per tile of kDiffTile rows: changed rows are ranked
-//                     by ballot and popcount inside a wave and a scan of the four wave counts, so changed row number k of the
-//                     call — in ascending row index — writes ids_out[k] = row0 + its position; positions i >= m write the -1
-//                     tail.  V > 0: the tile's changed source rows are then copied by groups of G lanes, V 32-bit words per
-//                     load and store (integer vectors: bits, not floats), src[p_k] -> rows_out[k].  V == 0: ids only.
+//   fcp_diff_fold_kernel        one wave: the records' offsets (select_offsets), the totals record, the report.
+//   fcp_diff_compact_kernel<V, G>   select_compact, a thread per row: changed row number k of the call, in ascending row index,
+//                     writes ids_out[k] = row0 + its position; positions i >= m write the -1 tail.  V > 0: the changed
+//                     source rows as bits, src[p_k] -> rows_out[k].  V == 0: ids only.
 // Every output byte is a function of the arguments alone: the grid is fixed by `rows`, integer sums, minima and maxima are
 // exact in any order, and there is no atomic.  Vector loads and stores only.
 // No scratch (-Rpass-analysis=kernel-resource-usage: ScratchSize 0 for every kernel); LDS: the classify kernel's fold (4 wave
@@ -43,16 +41,16 @@
 
 #include "fcp_table_walk.h" // RowSlots, minmax, q8_code, vec_of, group_of, with_vec, with_group: the rows' walk and the host's dispatch
 #include "fcp_block_fold.h" // wave_fold, block_fold
+#include "fcp_select_compact.h" // select_grid, select_offsets, select_compact, with_compact_shape: the selection's shared tail
 
 namespace {
 
 constexpr int kDiffThreads = FCP_BLOCK_THREADS;
-constexpr int kDiffTile = kDiffThreads;   // rows of one step of a compact block; a chunk is whole tiles
+constexpr int kDiffTile = kSelectTile;    // rows of one step of a compact block; a chunk is whole tiles
 constexpr int kDiffBlocks = 2048;         // the fixed grid of classify / compact: 8 blocks on each of 256 CUs; also the partial records
 constexpr int kDiffMinChunkTiles = 4;     // a block's chunk is at least this many tiles
 constexpr int kDiffUnroll = 4;            // steps of 256 / G rows a classify block has in flight (G == 64: half of it)
-static_assert(kDiffThreads == 256, "four waves per block: the compact kernel's scan of wave counts");
-static_assert(kDiffBlocks % 64 == 0, "the fold's lanes own equal runs of records");
+static_assert(kDiffTile == kDiffThreads, "select_compact takes a thread per row of a tile");
 
 // What a block of the classify phase found, and, once the fold has run, where its changed rows go.  32 bytes.
 struct DiffPartial {
@@ -78,9 +76,7 @@ enum { kDiffBits32 = 0, kDiffBits16 = 1, kDiffBits8 = 2, kDiffN16 = 3, kDiffQ8 =
 
 // V elements of E bytes as one load: what a slot of a stored row is
 template <int E, int V> struct DiffSlot;
-template <> struct DiffSlot<4, 4> { typedef uint32_t __attribute__((ext_vector_type(4))) T; };
-template <> struct DiffSlot<4, 2> { typedef uint32_t __attribute__((ext_vector_type(2))) T; };
-template <> struct DiffSlot<4, 1> { typedef uint32_t T; };
+template <int V> struct DiffSlot<4, V> : Words<V> {};
 template <int V> struct DiffSlot<2, V> { typedef typename NarrowType<V>::T T; };
 template <int V> struct DiffSlot<1, V> { typedef typename Q8Codes<V>::T T; };
 
@@ -277,17 +273,7 @@ __global__ void __launch_bounds__(64)
   const int b0 = lane * per, b1 = b0 + per < nblocks ? b0 + per : nblocks;
   DiffCounts c = {0, kNoFirst, -1};
   for (int b = b0; b < b1; ++b) fold(c, DiffCounts{partials[b].changed, partials[b].first, partials[b].last});
-  int64_t before = c.changed; // inclusive scan of the lanes' changed rows, then made exclusive
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int64_t up = __shfl_up(before, d, 64);
-    if (lane >= d) before += up;
-  }
-  before -= c.changed;
-  for (int b = b0; b < b1; ++b) {
-    partials[b].offset = before;
-    before += partials[b].changed;
-  }
+  select_offsets<kDiffBlocks>(partials, nblocks, c.changed);
   wave_fold(c);
   if (lane != 0) return;
   partials[kDiffBlocks] = c;
@@ -309,50 +295,17 @@ struct DiffCompact {
   int32_t dim;
 };
 
+// what select_compact asks of the unit: nothing to bring along, a changed row's table index, the -1 tail
+struct DiffEmit {
+  const DiffCompact &A;
+  __device__ __forceinline__ int prepare(int64_t, bool) const { return 0; }
+  __device__ __forceinline__ void emit(int64_t k, int64_t i, int) const { *as_global(A.ids_out + k) = A.row0 + i; }
+  __device__ __forceinline__ void tail(int64_t i) const { *as_global(A.ids_out + i) = -1; }
+};
+
 // V == 0: ids only (rows_out is null and src is never read); else G lanes copy a changed row, V words at a time
 template <int V, int G> __global__ void __launch_bounds__(kDiffThreads) fcp_diff_compact_kernel(const DiffCompact A) {
-  __shared__ uint32_t s_list[kDiffTile]; // the tile's changed rows, by rank: their thread
-  __shared__ uint32_t s_count[kDiffThreads / 64];
-  const int tid = threadIdx.x;
-  const int wave = tid / 64;
-  const int64_t c0 = (int64_t)blockIdx.x * A.chunk;
-  const int64_t c1 = c0 + A.chunk < A.rows ? c0 + A.chunk : A.rows;
-  const int64_t m = A.partials[kDiffBlocks].changed;
-  int64_t k0 = A.partials[blockIdx.x].offset; // the output index of the tile's first changed row
-  for (int64_t t0 = c0; t0 < c1; t0 += kDiffTile) {
-    const int64_t i = t0 + tid;
-    const bool have = i < c1;
-    const bool hit = have && *as_global(A.flags + i) != 0;
-    const unsigned long long ballot = __ballot(hit);
-    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
-    if ((tid & 63) == 0) s_count[wave] = (uint32_t)__popcll(ballot);
-    __syncthreads();
-    uint32_t rank = below, total = 0;
-#pragma unroll
-    for (int w = 0; w < kDiffThreads / 64; ++w) {
-      const uint32_t n = s_count[w];
-      if (w < wave) rank += n;
-      total += n;
-    }
-    if (hit) {
-      *as_global(A.ids_out + (k0 + rank)) = A.row0 + i;
-      if constexpr (V > 0) s_list[rank] = (uint32_t)tid;
-    }
-    if (have && i >= m) *as_global(A.ids_out + i) = -1; // the tail: indices no changed row has
-    __syncthreads();                                     // s_list is whole; s_count may be written again
-    if constexpr (V > 0) {
-      typedef typename DiffSlot<4, V>::T W;
-      const int lane = tid & (G - 1);
-      const int nslots = A.dim / V;
-      for (uint32_t j = (uint32_t)(tid / G); j < total; j += kDiffThreads / G) {
-        const FCP_GLOBAL W *src = as_global(reinterpret_cast<const W *>(A.src + (t0 + (int64_t)s_list[j]) * A.dim));
-        FCP_GLOBAL W *dst = as_global(reinterpret_cast<W *>(A.rows_out + (k0 + (int64_t)j) * A.dim));
-        for (int slot = lane; slot < nslots; slot += G) dst[slot] = src[slot];
-      }
-      __syncthreads(); // the copies have read s_list
-    }
-    k0 += total;
-  }
+  select_compact<V, G, kDiffBlocks>(A.flags, A.partials, A.rows, A.chunk, A.src, A.rows_out, A.dim, DiffEmit{A});
 }
 
 int64_t partial_bytes() { return (int64_t)(kDiffBlocks + 1) * (int64_t)sizeof(DiffPartial); }
@@ -377,9 +330,7 @@ extern "C" int fcp_table_diff(const void *table, int32_t kind, int64_t table_row
                               void *workspace, int32_t device, void *stream) {
   const std::string w = "fcp_table_diff: ";
   if (rows < 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`rows` is negative");
-  if (rows >= fcpf::kRowLimit) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`rows` must stay below 2^32 - 3");
-  if (table_rows < 1 || table_rows >= fcpf::kRowLimit)
-    return fail(FCP_ERR_INVALID_ARGUMENT, w + "`table_rows` must lie in [1, 2^32 - 3), a plan's row limit");
+  if (const std::string why = fcpf::row_limit_refusal("rows", rows, table_rows); !why.empty()) return fail(FCP_ERR_INVALID_ARGUMENT, w + why);
   if (row0 < 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`row0` is negative");
   if (row0 > table_rows - rows) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`row0` + rows must not exceed table_rows");
   if (dim <= 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`dim` must be positive");
@@ -394,30 +345,26 @@ extern "C" int fcp_table_diff(const void *table, int32_t kind, int64_t table_row
   if (rows > 0 && !src) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`src` is null");
   if (rows > 0 && !ids_out) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`ids_out` is null");
   const int vec = vec_of(dim);
-  const auto misaligned = [&](const char *name, int align, const std::string &what) {
-    return fail(FCP_ERR_INVALID_ARGUMENT, w + "`" + name + "` is not " + std::to_string(align) + "-byte aligned" + what);
-  };
   if ((uintptr_t)table % fcpf::base_alignment(kind, vec))
-    return misaligned("table", fcpf::base_alignment(kind, vec), std::string(" (a ") + kind_name(kind) + " table of this dim)");
+    return fail(FCP_ERR_INVALID_ARGUMENT,
+                w + fcpf::not_aligned("table", fcpf::base_alignment(kind, vec), std::string(" (a ") + kind_name(kind) + " table of this dim)"));
   if ((uintptr_t)src % fcpf::base_alignment(src_kind, vec))
-    return misaligned("src", fcpf::base_alignment(src_kind, vec), std::string(" (") + kind_name(src_kind) + " rows of this dim)");
-  if ((uintptr_t)ids_out % 8) return misaligned("ids_out", 8, "");
-  if ((uintptr_t)rows_out % (4 * vec)) return misaligned("rows_out", 4 * vec, " (float32 rows of this dim)");
-  if ((uintptr_t)report % 8) return misaligned("report", 8, "");
-  if ((uintptr_t)workspace % 8) return misaligned("workspace", 8, "");
+    return fail(FCP_ERR_INVALID_ARGUMENT,
+                w + fcpf::not_aligned("src", fcpf::base_alignment(src_kind, vec), std::string(" (") + kind_name(src_kind) + " rows of this dim)"));
+  if ((uintptr_t)ids_out % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("ids_out", 8));
+  if ((uintptr_t)rows_out % (4 * vec)) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("rows_out", 4 * vec, " (float32 rows of this dim)"));
+  if ((uintptr_t)report % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("report", 8));
+  if ((uintptr_t)workspace % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("workspace", 8));
 
   DiffPartial *partials = static_cast<DiffPartial *>(workspace);
   uint8_t *flags = static_cast<uint8_t *>(workspace) + partial_bytes();
-  // the classify / compact grid: chunks of whole tiles, at least kDiffMinChunkTiles of them, at most kDiffBlocks chunks
-  const int64_t tiles = (rows + kDiffTile - 1) / kDiffTile;
-  const int64_t chunk = std::max<int64_t>(kDiffMinChunkTiles, (tiles + kDiffBlocks - 1) / kDiffBlocks) * kDiffTile;
-  const int nblocks = (int)((rows + chunk - 1) / chunk);
+  const auto grid = select_grid(rows, kDiffBlocks, kDiffMinChunkTiles); // of classify and compact
   DiffClassify A;
   A.table = static_cast<const char *>(table);
   A.src = static_cast<const char *>(src);
   A.row0 = row0;
   A.rows = rows;
-  A.chunk = chunk;
+  A.chunk = grid.chunk;
   A.trb = fcpf::row_bytes(kind, dim);
   A.srb = fcpf::row_bytes(src_kind, dim);
   A.dim = dim;
@@ -432,26 +379,20 @@ extern "C" int fcp_table_diff(const void *table, int32_t kind, int64_t table_row
   B.rows_out = rows_out;
   B.row0 = row0;
   B.rows = rows;
-  B.chunk = chunk;
+  B.chunk = grid.chunk;
   B.dim = dim;
   return on_device("fcp_table_diff", device, stream, [&](hipStream_t s) {
     if (rows > 0) {
       if (src_kind == kind)
-        kind == FCP_TAB_F32 ? launch_classify<kDiffBits32>(A, vec, nblocks, s)
-                            : kind == FCP_TAB_Q8 ? launch_classify<kDiffBits8>(A, vec, nblocks, s) : launch_classify<kDiffBits16>(A, vec, nblocks, s);
+        kind == FCP_TAB_F32 ? launch_classify<kDiffBits32>(A, vec, grid.nblocks, s)
+                            : kind == FCP_TAB_Q8 ? launch_classify<kDiffBits8>(A, vec, grid.nblocks, s) : launch_classify<kDiffBits16>(A, vec, grid.nblocks, s);
       else
-        kind == FCP_TAB_Q8 ? launch_classify<kDiffQ8>(A, vec, nblocks, s) : launch_classify<kDiffN16>(A, vec, nblocks, s);
+        kind == FCP_TAB_Q8 ? launch_classify<kDiffQ8>(A, vec, grid.nblocks, s) : launch_classify<kDiffN16>(A, vec, grid.nblocks, s);
     }
-    hipLaunchKernelGGL(fcp_diff_fold_kernel, dim3(1), dim3(64), 0, s, partials, (int32_t)nblocks, row0, rows, report);
+    hipLaunchKernelGGL(fcp_diff_fold_kernel, dim3(1), dim3(64), 0, s, partials, (int32_t)grid.nblocks, row0, rows, report);
     if (rows == 0) return;
-    if (!rows_out) {
-      hipLaunchKernelGGL((fcp_diff_compact_kernel<0, 1>), dim3(nblocks), dim3(kDiffThreads), 0, s, B);
-      return;
-    }
-    with_vec(vec, [&](auto v) {
-      with_group(group_of(dim, vec), [&](auto g) {
-        hipLaunchKernelGGL((fcp_diff_compact_kernel<decltype(v)::value, decltype(g)::value>), dim3(nblocks), dim3(kDiffThreads), 0, s, B);
-      });
+    with_compact_shape(rows_out != nullptr, dim, vec, [&](auto v, auto g) {
+      hipLaunchKernelGGL((fcp_diff_compact_kernel<decltype(v)::value, decltype(g)::value>), dim3(grid.nblocks), dim3(kDiffThreads), 0, s, B);
     });
   });
 }

@@ -33,7 +33,7 @@ int check_common(const std::string &w, int32_t kind, int32_t dim, int64_t row0, 
 
 int check_aligned(const std::string &w, const char *name, const void *p, int align, const char *what, std::string *why) {
   if ((uintptr_t)p % (uintptr_t)align)
-    return refuse(why, w + "`" + name + "` is not " + std::to_string(align) + "-byte aligned" + what);
+    return refuse(why, w + fcpf::not_aligned(name, align, what));
   return FCP_OK;
 }
 

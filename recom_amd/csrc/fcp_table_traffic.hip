@@ -159,10 +159,9 @@ extern "C" int fcp_table_count_ids(uint32_t *counts, int64_t table_rows, const v
   if (id_bytes != 4 && id_bytes != 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`id_bytes` is 4 (int32 ids) or 8 (int64 ids)");
   if (n > 0 && !counts) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`counts` is null");
   if (n > 0 && !ids) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`ids` is null");
-  if ((uintptr_t)counts % 4) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`counts` is not 4-byte aligned");
-  if ((uintptr_t)ids % (uintptr_t)id_bytes)
-    return fail(FCP_ERR_INVALID_ARGUMENT, w + "`ids` is not " + std::to_string(id_bytes) + "-byte aligned");
-  if ((uintptr_t)skipped % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`skipped` is not 8-byte aligned");
+  if ((uintptr_t)counts % 4) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("counts", 4));
+  if ((uintptr_t)ids % (uintptr_t)id_bytes) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("ids", id_bytes));
+  if ((uintptr_t)skipped % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("skipped", 8));
   if (n == 0) return FCP_OK;
   unsigned long long *sk = reinterpret_cast<unsigned long long *>(skipped);
   const int blocks = (int)std::min<int64_t>(kCountBlocks, n / kTileIds + (n % kTileIds != 0));

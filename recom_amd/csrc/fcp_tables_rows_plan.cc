@@ -33,8 +33,7 @@ int64_t rows_per_piece(int group, int64_t spr) {
 int check_row_args(const std::string &w, const void *table, int32_t kind, int64_t table_rows, int32_t dim, const void *row_ids,
                    const void *rows, int64_t n, std::string *why) {
   if (n < 0) return refuse(why, w + "`n` is negative");
-  if (n >= fcpf::kRowLimit) return refuse(why, w + "`n` must stay below 2^32 - 3");
-  if (table_rows < 1 || table_rows >= fcpf::kRowLimit) return refuse(why, w + "`table_rows` must lie in [1, 2^32 - 3), a plan's row limit");
+  if (const std::string limit = fcpf::row_limit_refusal("n", n, table_rows); !limit.empty()) return refuse(why, w + limit);
   if (dim <= 0) return refuse(why, w + "`dim` must be positive");
   if (!fcpf::known_tab_kind(kind)) return refuse(why, w + "`kind` is no FCP_TAB_* value");
   if (n > 0 && !table) return refuse(why, w + "`table` is null");
@@ -42,10 +41,9 @@ int check_row_args(const std::string &w, const void *table, int32_t kind, int64_
   if (n > 0 && !rows) return refuse(why, w + "`rows` is null");
   const int vec = fcpf::vec_of(dim);
   if ((uintptr_t)table % fcpf::base_alignment(kind, vec))
-    return refuse(why, w + "`table` is not " + std::to_string(fcpf::base_alignment(kind, vec)) + "-byte aligned (a " + fcpf::kind_name(kind) +
-                           " table of this dim)");
-  if ((uintptr_t)rows % (4 * vec)) return refuse(why, w + "`rows` is not " + std::to_string(4 * vec) + "-byte aligned (float32 rows of this dim)");
-  if ((uintptr_t)row_ids % 8) return refuse(why, w + "`row_ids` is not 8-byte aligned");
+    return refuse(why, w + fcpf::not_aligned("table", fcpf::base_alignment(kind, vec), std::string(" (a ") + fcpf::kind_name(kind) + " table of this dim)"));
+  if ((uintptr_t)rows % (4 * vec)) return refuse(why, w + fcpf::not_aligned("rows", 4 * vec, " (float32 rows of this dim)"));
+  if ((uintptr_t)row_ids % 8) return refuse(why, w + fcpf::not_aligned("row_ids", 8));
   return FCP_OK;
 }
 
@@ -73,8 +71,8 @@ int check_call(const char *who, const fcp_table_rows_t *entries, int32_t n_table
   if (rc) return rc;
   const std::string w = std::string(who) + ": ";
   if (n_tables > 0 && !workspace) return refuse(why, w + "`workspace` is null");
-  if ((uintptr_t)workspace % 8) return refuse(why, w + "`workspace` is not 8-byte aligned");
-  if ((uintptr_t)skipped % 8) return refuse(why, w + "`skipped` is not 8-byte aligned");
+  if ((uintptr_t)workspace % 8) return refuse(why, w + fcpf::not_aligned("workspace", 8));
+  if ((uintptr_t)skipped % 8) return refuse(why, w + fcpf::not_aligned("skipped", 8));
   return FCP_OK;
 }
 

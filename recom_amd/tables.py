@@ -631,8 +631,27 @@ class DeltaReport:
     skipped: int       # ids outside [0, table_rows)
 
 
-def _report_of(report_t) -> DeltaReport:
-    return DeltaReport(*(int(v) for v in report_t.cpu().tolist()))
+def _report_of(cls, report_t):          # cls: DeltaReport | DiffReport, the dataclass of the int64 device tensor report_t
+    return cls(*(int(v) for v in report_t.cpu().tolist()))
+
+
+def _stream_of(torch, device, stream: Optional[int]) -> int:
+    return torch.cuda.current_stream(device).cuda_stream if stream is None else stream
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _selection_outputs(torch, device, stream: int, n: int, dim: Optional[int], pos: bool, report_t, need: int):
+    """``(ids, pos, rows, report, workspace)`` of a selecting entry as that stream's; ``pos`` / ``rows`` ``None`` unless asked for"""
+    with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device)):
+        ids_out = torch.empty((n,), dtype=torch.int64, device=device)
+        pos_out = torch.empty((n,), dtype=torch.int64, device=device) if pos else None
+        rows_out = torch.empty((n, dim), dtype=torch.float32, device=device) if dim is not None else None
+        report = torch.empty((C.sizeof(report_t) // 8,), dtype=torch.int64, device=device)
+        workspace = torch.empty((need // 8,), dtype=torch.int64, device=device)
+    return ids_out, pos_out, rows_out, report, workspace
 
 
 def _delta_ids_of(torch, row_ids) -> int:
@@ -667,17 +686,11 @@ def delta_distinct_async(row_ids, rows=None, table_rows: Optional[int] = None, p
     need = int(L.fcp_table_delta_workspace_bytes(n))
     if need < 0:
         raise ValueError(f"row_ids names {n} ids; a delta stays below 2^32 - 3")
-    if stream is None:
-        stream = torch.cuda.current_stream(device).cuda_stream
-    with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device)):
-        ids_out = torch.empty((n,), dtype=torch.int64, device=device)
-        pos_out = torch.empty((n,), dtype=torch.int64, device=device) if pos else None
-        rows_out = torch.empty_like(rows) if rows is not None else None
-        report = torch.empty((C.sizeof(_lib.TableDeltaReport) // 8,), dtype=torch.int64, device=device)
-        workspace = torch.empty((need // 8,), dtype=torch.int64, device=device)
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
-    status = L.fcp_table_delta_distinct(ptr(row_ids), int(row_ids.element_size()), ptr(rows), dim, n, int(table_rows), ptr(ids_out),
-                                        ptr(rows_out), ptr(pos_out), ptr(report), ptr(workspace), device.index or 0, C.c_void_p(stream))
+    stream = _stream_of(torch, device, stream)
+    ids_out, pos_out, rows_out, report, workspace = _selection_outputs(torch, device, stream, n, dim if rows is not None else None, pos,
+                                                                       _lib.TableDeltaReport, need)
+    status = L.fcp_table_delta_distinct(_ptr(row_ids), int(row_ids.element_size()), _ptr(rows), dim, n, int(table_rows), _ptr(ids_out),
+                                        _ptr(rows_out), _ptr(pos_out), _ptr(report), _ptr(workspace), device.index or 0, C.c_void_p(stream))
     _lib.check(status, "fcp_table_delta_distinct")
     return (ids_out, rows_out, report, pos_out) if pos else (ids_out, rows_out, report)
 
@@ -691,10 +704,8 @@ def delta_distinct(row_ids, rows=None, table_rows: Optional[int] = None, pos: bo
     inside the table as it stood: it comes back byte for byte."""
     import torch
     out = delta_distinct_async(row_ids, rows, table_rows=table_rows, pos=pos, stream=stream)
-    if stream is None:
-        stream = torch.cuda.current_stream(row_ids.device).cuda_stream
-    torch.cuda.ExternalStream(stream, device=row_ids.device).synchronize()
-    report = _report_of(out[2])
+    torch.cuda.ExternalStream(_stream_of(torch, row_ids.device, stream), device=row_ids.device).synchronize()
+    report = _report_of(DeltaReport, out[2])
     m = report.distinct
     head = (out[0][:m], out[1][:m] if out[1] is not None else None, report)
     return head + (out[3][:m],) if pos else head
@@ -718,8 +729,7 @@ def apply_delta(table, row_ids, rows, digest: Optional[int] = None, row0: int = 
         if skipped.dtype != torch.int64 or skipped.numel() != 1 or skipped.device != table.device:
             raise ValueError("skipped is an int64 tensor of one element on the table's device")
     L = _lib.load()
-    if stream is None:
-        stream = torch.cuda.current_stream(table.device).cuda_stream
+    stream = _stream_of(torch, table.device, stream)
     ids_d, rows_d, report_t = delta_distinct_async(row_ids, rows, table_rows=int(table.shape[0]), stream=stream)
     if digest is not None:
         outs, workspace = _digest_buffers(torch, L, table.device, stream, n_out=2)
@@ -733,7 +743,7 @@ def apply_delta(table, row_ids, rows, digest: Optional[int] = None, row0: int = 
         with torch.cuda.stream(ext):
             skipped.view(-1).add_(report_t[3:4])
     ext.synchronize()
-    report = _report_of(report_t)
+    report = _report_of(DeltaReport, report_t)
     if digest is None:
         return report
     before, after = _digests_of(outs)
@@ -748,10 +758,6 @@ class DiffReport:
     changed: int         # rows whose stored bytes would change
     first_changed: int   # smallest changed table row index, -1 if none
     last_changed: int    # largest, -1 if none
-
-
-def _diff_report_of(report_t) -> DiffReport:
-    return DiffReport(*(int(v) for v in report_t.cpu().tolist()))
 
 
 def diff_async(table, src, row0: int = 0, want_rows: bool = True, stream: Optional[int] = None):
@@ -782,16 +788,11 @@ def diff_async(table, src, row0: int = 0, want_rows: bool = True, stream: Option
     need = int(L.fcp_table_diff_workspace_bytes(rows))
     if need < 0:
         raise ValueError(f"src has {rows} rows; a call stays below 2^32 - 3")
-    if stream is None:
-        stream = torch.cuda.current_stream(device).cuda_stream
-    with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device)):
-        ids_out = torch.empty((rows,), dtype=torch.int64, device=device)
-        rows_out = torch.empty((rows, dim), dtype=torch.float32, device=device) if want_rows else None
-        report = torch.empty((C.sizeof(_lib.TableDiffReport) // 8,), dtype=torch.int64, device=device)
-        workspace = torch.empty((need // 8,), dtype=torch.int64, device=device)
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
-    status = L.fcp_table_diff(ptr(table), _lib.TABLE_KINDS[name], int(table.shape[0]), dim, ptr(src), _lib.TABLE_KINDS[src_name], int(row0),
-                              rows, ptr(ids_out), ptr(rows_out), ptr(report), ptr(workspace), device.index or 0, C.c_void_p(stream))
+    stream = _stream_of(torch, device, stream)
+    ids_out, _pos, rows_out, report, workspace = _selection_outputs(torch, device, stream, rows, dim if want_rows else None, False,
+                                                                    _lib.TableDiffReport, need)
+    status = L.fcp_table_diff(_ptr(table), _lib.TABLE_KINDS[name], int(table.shape[0]), dim, _ptr(src), _lib.TABLE_KINDS[src_name], int(row0),
+                              rows, _ptr(ids_out), _ptr(rows_out), _ptr(report), _ptr(workspace), device.index or 0, C.c_void_p(stream))
     _lib.check(status, "fcp_table_diff")
     return ids_out, rows_out, report
 
@@ -804,10 +805,8 @@ def diff(table, src, row0: int = 0, want_rows: bool = True, stream: Optional[int
     ``report`` a ``DiffReport`` — the delta ``update_rows`` takes."""
     import torch
     ids, rows, report_t = diff_async(table, src, row0=row0, want_rows=want_rows, stream=stream)
-    if stream is None:
-        stream = torch.cuda.current_stream(table.device).cuda_stream
-    torch.cuda.ExternalStream(stream, device=table.device).synchronize()
-    report = _diff_report_of(report_t)
+    torch.cuda.ExternalStream(_stream_of(torch, table.device, stream), device=table.device).synchronize()
+    report = _report_of(DiffReport, report_t)
     m = report.changed
     return ids[:m], rows[:m] if rows is not None else None, report
 
@@ -844,7 +843,7 @@ def diff_from_host(table, master_cpu, chunk_rows: int = 1 << 16):
             staged[:n].copy_(bounce[:n], non_blocking=True)
             ids_d, rows_d, report_t = diff_async(table, staged[:n], row0=r0, stream=stream.cuda_stream)
             stream.synchronize()                      # the bounce buffer's copy has left it; the chunk's m is known
-            r = _diff_report_of(report_t)
+            r = _report_of(DiffReport, report_t)
             if r.changed:
                 ids.append(ids_d[:r.changed].clone())
                 deltas.append(rows_d[:r.changed].clone())
@@ -890,7 +889,7 @@ def sync_from_host(table, master_cpu, digest: Optional[int] = None, chunk_rows: 
                 _enqueue_digest_rows(L, table, name, dim, ids_d, n, 0, 1, outs.data_ptr() + (2 * k + 1) * size, workspace, s)
             reports.append(report_t)
         stream.synchronize()
-    changed = sum(_diff_report_of(t).changed for t in reports)
+    changed = sum(_report_of(DiffReport, t).changed for t in reports)
     if digest is None:
         return changed
     new = int(digest)

@@ -156,7 +156,18 @@ def mask_of(pattern: str, rows: int) -> np.ndarray:
         return (i % TILE == TILE - 1) | ((i % TILE == 0) & (i > 0))
     if pattern == "last_element":
         return i % 2 == 0
+    if pattern == "wave_edges":          # the last row of every wave and the first row of the next one: every tile's edges too
+        return (i % WAVE == WAVE - 1) | ((i % WAVE == 0) & (i > 0))
     raise ValueError(pattern)
+
+
+# The selection's own edges (fcp_select_compact.h serves the delta too): nothing, everything, and rows on both sides of every
+# wave and tile boundary — at float32 against float32, the cheapest classify, with rows_out at V 4 / G 1 and at V 2 / G 4 —
+# over the delta's size list: ROW_COUNTS, and BIG_ROWS at the V 4 dim alone.
+WAVE = 64
+EDGE_PATTERNS = ("none", "all", "wave_edges")
+EDGE_DIMS = (4, 6)
+EDGE_ROW_COUNTS = ROW_COUNTS + (BIG_ROWS,)
 
 
 class Variants:

@@ -9,6 +9,7 @@ nothing.
 
 (The references on themselves, and every pattern shown to contain what it is for: tests/test_table_diff_host.py.)"""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -147,6 +148,40 @@ def test_one_full_pass_of_the_grid_and_one_row(torch_cuda, kind, dim):
     out = _run(torch, _table_of(torch, base, kind, dev), kind, dim, torch.from_numpy(new).to(dev))
     report = _check(out, want, new, {"kind": kind, "dim": dim, "rows": rows})
     assert report["last_changed"] == rows - 1 and report["first_changed"] == 1
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_rows(dim):
+    """(base, loud(base)) float32 at the largest row count an edge cell of `dim` takes, read-only: a prefix serves every count"""
+    rows = D.BIG_ROWS if dim == 4 else D.MAX_ROWS
+    base = D.base_rows(rows, dim, seed=11)
+    changed = D.loud(base)
+    base.setflags(write=False)
+    changed.setflags(write=False)
+    return base, changed
+
+
+@pytest.mark.parametrize("pattern", D.EDGE_PATTERNS)
+def test_the_selection_s_edges(torch_cuda, pattern):
+    """What fcp_table_delta_distinct's size sweep holds the shared compact body to, held to it through this entry: nothing
+    changed, every row changed, and changed rows on both sides of every wave and tile boundary, at one row, two, a wave -+ 1, a
+    tile -+ 1, a chunk -+ 1 and one full pass of the fixed grid + 1; float32 against float32, rows_out by V 4 / G 1 (dim 4)
+    and by V 2 / G 4 (dim 6; not at the full pass)."""
+    torch = torch_cuda
+    dev = torch.device("cuda", 0)
+    for dim in D.EDGE_DIMS:
+        base, changed = _edge_rows(dim)
+        for rows in D.EDGE_ROW_COUNTS:
+            if rows > len(base):
+                continue
+            mask = D.mask_of(pattern, rows)
+            new = np.where(mask[:, None], changed[:rows], base[:rows])
+            want = D.diff_ref(D.ref_bytes(new, "f32"), D.ref_bytes(base[:rows], "f32"))
+            assert want[0].tolist() == np.flatnonzero(mask).tolist()
+            out = _run(torch, _table_of(torch, base[:rows], "f32", dev), "f32", dim, torch.from_numpy(new).to(dev))
+            report = _check(out, want, new, {"dim": dim, "rows": rows, "pattern": pattern})
+            assert report["changed"] == {"none": 0, "all": rows, "wave_edges": rows // D.WAVE + (rows - 1) // D.WAVE}[pattern]
+    assert D.BIG_ROWS in D.EDGE_ROW_COUNTS and D.chunk_for(D.BIG_ROWS) > D.chunk_for(D.BIG_ROWS - 1)
 
 
 @pytest.mark.parametrize("kind", tuple(D.KINDS))

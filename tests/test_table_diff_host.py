@@ -194,6 +194,21 @@ def test_the_geometry_and_the_sizes():
     assert set(D.quiet_dims("q8")) == set(D.dims_of("q8")) - {1, 2} and D.quiet_dims("f16") == D.dims_of("f16")
 
 
+def test_the_selection_s_edge_cells_stand_on_the_delta_s_sizes():
+    """the edge cells of tests/test_gpu_table_diff.py: the size list of tests/table_delta_cases.py in this grid's terms, and a
+    mixed pattern with a changed row on both sides of every wave boundary — every tile boundary is one"""
+    assert set(D.EDGE_ROW_COUNTS) == {1, 2, 63, 64, 65, D.TILE - 1, D.TILE, D.TILE + 1, D.MIN_CHUNK - 1, D.MIN_CHUNK, D.MIN_CHUNK + 1,
+                                      D.FULL_PASS + 1}
+    assert D.EDGE_PATTERNS == ("none", "all", "wave_edges") and D.TILE % D.WAVE == 0
+    for rows in D.ROW_COUNTS:
+        mask = D.mask_of("wave_edges", rows)
+        for edge in range(D.WAVE, rows, D.WAVE):
+            assert mask[edge - 1] and mask[edge]
+        assert mask.sum() == rows // D.WAVE + (rows - 1) // D.WAVE and not mask[0] and (rows < 3 or not mask[1:D.WAVE - 1].any())
+        assert (D.mask_of("tile_edges", rows) <= mask).all()
+    assert D.EDGE_DIMS == (4, 6)        # float32 rows copied by V 4 / G 1 and by V 2 / G 4, as the delta's sweep copies them
+
+
 @pytest.mark.parametrize("kind", tuple(D.KINDS))
 def test_every_pattern_contains_what_it_is_for(kind):
     """From the reference alone: the rows a pattern means to change are the rows whose bytes change in every format, nothing
