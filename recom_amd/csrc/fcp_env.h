@@ -6,7 +6,7 @@
 //     (fcp_stager_create*) or the RCCL binding is created — and the values live in that object: nothing on the request path
 //     reads the environment.
 //   * Everything else — diagnostics and test hooks — is ONE variable,
-//       FCP_DIAG="key[=value],key[=value],..."      e.g.  FCP_DIAG="lane_fault_us=120,dyn_general"
+//       FCP_DIAG="key[=value],key[=value],..."      e.g.  FCP_DIAG="lane_fault_us=120,wide_rows"
 //     looked up with fcp::diag("key") at the (rare or cached) place that wants it.  A bare key has the value "1".  The
 //     keys are listed in INTEGRATION.md section 8; a deployment never sets FCP_DIAG.
 //

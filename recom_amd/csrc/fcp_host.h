@@ -1,14 +1,16 @@
 // fcp_host.h — what the host-side translation units of libfcp_hip.so share: the plan object, the per-request descriptor
 // cache, the private-stream (lane) state and the helpers that cross files.  Internal: nothing here is part of the ABI
 // (include/fcp_hip.h).  Round 6 carved the single 3 700-line fcp_api.hip into
-//   fcp_plan.hip     building the plan object, geometry (compute_dyn), const buffers and device resources, accessors
+//   fcp_plan.hip     the device half of the plan object: const buffers, static records and device resources; accessors
 //   fcp_process.hip  the request path: descriptor slots, launch records, fcp_internal_process, fcp_process_feature_columns
 //   fcp_lanes.hip    plan-owned private streams (EXPERIMENTAL): lanes, verification, supervisor, result registry
 //   fcp_concat.hip   Addons>ConcatOutputs entry points and fcp_shard_finalize
 //   fcp_stager.hip   Addons>ConcatInputs packers, the request stager, the pack pool
-// and the descriptor level, which needs no GPU header, became a unit of ordinary C++:
-//   fcp_plan_desc.cc validation, the formats' refusals, plan files, the placement gate, fcp_last_error (fcp_plan_desc.h)
-//   fcp_formats.h    the one table of the storage formats' facts (names, flag bits, element and row sizes)
+// and the levels that need no GPU header became units of ordinary C++:
+//   fcp_plan_desc.cc  validation, the formats' refusals, plan files, the placement gate, fcp_last_error (fcp_plan_desc.h)
+//   fcp_plan_shape.cc the host half of the plan (HostPlan, build_host_plan) and shape evaluation (evaluate_shapes): per-column
+//                     records, arena layout and launch geometry from a request's shapes (fcp_plan_shape.h)
+//   fcp_formats.h     the one table of the storage formats' facts (names, flag bits, element and row sizes)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -34,6 +36,7 @@
 #include "fcp_env.h"
 #include "fcp_formats.h"
 #include "fcp_plan_desc.h"
+#include "fcp_plan_shape.h"
 
 namespace fcph {
 
@@ -45,48 +48,10 @@ int hip_fail(const char *what, hipError_t e); // (fail: fcp_plan_desc.h)
     if (e_ != hipSuccess) return hip_fail(#expr, e_);   \
   } while (0)
 
-inline int64_t align128(int64_t x) { return (x + 127) / 128 * 128; } // alignmem, cuda_emitter.cc:967-969
-
 constexpr int kSlots = 32; // descriptor slots per plan: distinct (shapes, stream) pairs resident at once (8 until round 4: 16 rotating shapes reinstalled on every request)
-constexpr uint32_t kFlagHostOnly = FCP_FLAG_HOST_ONLY; // plan without device resources (layout queries)
-
-struct HostColumn {
-  fcp_column_desc_t d;
-  fcp_column_ext_t ext = {}; // extensions (segment-id map); all zeros = none
-  std::vector<float> boundaries;
-  int32_t weights_input = -1; // host input of the per-id weights (fcp_column_ext_t::weights_input1 - 1), or -1
-  std::vector<int64_t> xf_lo, xf_hi; // id transform intervals (closed)
-  int64_t xf_const_off = -1;         // byte offset in the const buffer of intervals 1.. as (lo, hi) pairs
-  int32_t out_off = 0;
-  int64_t const_off = -1; // byte offset of the boundaries in the const buffer
-};
 
 constexpr int kAllSlotsBusy = -2; // find_or_reserve: every slot is pinned by a concurrent request
 constexpr int kNeedsInstall = -3; // find_or_reserve during stream capture: these shapes are not resident
-
-struct DynMeta {
-  std::vector<int32_t> group_rows;
-  std::vector<int64_t> group_base;
-  int64_t arena_bytes = 0;
-  int64_t csr_arena_off = 0;
-  int32_t max_seg_nnz = 0;
-  int32_t max_lookup_nnz = 0; // longest id stream of a lookup column (GATHER, SEGMENT_REDUCE, GATHER_SCATTER): fcp_plan_traffic_count's grid
-  int64_t seg_pairs = 0;   // sum of rows over the segment-id columns: cost of the in-block search
-  bool seg_search = false; // this request: blocks search the segment ids (no pre-pass launch)
-  bool plain = false;      // plain dense plan and at least 64 rows: the request takes fcp_dense_kernel_plain (its span image is built)
-  int64_t work_bytes = 0;  // table rows gathered + output written: what decides whether a private lane pays (fcp_plan_set_private_streams)
-  // regular CSR (FcpLaunch::csr_reg): 0 = none, 1 = the arena scratch laid out by column position, 2 = CSR inputs that lie
-  // one stride apart in the blob; byte offset of position 0's array in the arena / the blob; stride in int32 elements
-  int32_t csr_reg_mode = 0, csr_reg_stride = 0;
-  int64_t csr_reg_base = 0;
-  // launch geometry per kernel kind: [0] dense kernel (spans whose columns all have exactly
-  // one source row per output row), [1] ragged kernel (spans with pooled / scatter / reduction columns)
-  struct Geo {
-    int32_t grid_blocks = 0;
-    int32_t rows_per_wave = 1;
-    FcpGroupLaunch groups[FCP_MAX_GROUPS];
-  } geo[2];
-};
 
 struct DynSlot {
   bool valid = false;
@@ -224,58 +189,13 @@ int wait_for_inputs(const void *const *inputs, int32_t n, void *stream);
 } // namespace fcph
 using namespace fcph; // (an internal header: every includer is one of the five files above)
 
-struct fcp_plan {
-  fcp::Env env; // the shipping environment switches as they were when the plan was created (fcp_env.h)
-  fcp_plan_desc_t desc;
-  std::vector<HostColumn> cols;
-  std::vector<int32_t> ranks, elem_sizes, shape_off;
-  std::vector<int32_t> group_width, group_nslots, group_map_off;
-  std::vector<int32_t> seg_cols;
-  int32_t n_seg_plain = 0;  // seg_cols[0 .. n_seg_plain): pooled columns; the rest: any-order ScatterNd columns (inverse maps)
-  bool seg_search = false;  // blocks search the segment ids themselves; no segment-offset pre-pass
-  bool has_inverse = false; // some ScatterNd column brings its row ids as delivered (any order): inverse map in the pre-pass
-  // (r6) the CSR scratch of segment-id columns is laid out by column POSITION (one row of round32(rows + 1) entries per
-  // column of the plan, pooled or not) instead of packed: the ragged body then knows where a range is before it has the
-  // column's record (FcpLaunch::csr_reg).  One concat group, no any-order ScatterNd column (their inverse maps are the
-  // scratch's tail, cleared per request), and pooled columns at least half of the plan (the unused rows cost arena bytes,
-  // never traffic: RAGGED 512 of 512 columns; the reference's models E / F, 10-20 of ~1000, keep the packed scratch).
-  bool csr_by_pos = false;
-  // device arrays are kept in concat order (group-major, ascending concat offset)
-  // so that the columns of one output span are contiguous: order[pos] = column,
-  // pos_of[column] = pos.
-  std::vector<int32_t> order, pos_of;
-  // compact per-column facts in concat (pos) order + one representative column per group:
-  // what compute_dyn_fast walks on the request path
-  struct FastCol {
-    int32_t ids_input, seg_input, rows_arg, dim, seg_stride;
-    int64_t out_off_bytes;
-    uint8_t form, rows_source, seg_kind, group;
-  };
-  std::vector<FastCol> fast_cols;
-  std::vector<int32_t> group_rep;
-  int vec = 1;
-  bool dense_only = true;   // no span needs the ragged kernel
-  // hybrid dispatch: per group, the spans served by the dense kernel and by the ragged kernel
-  std::vector<uint32_t> span_list;                 // host copy of d_span_list
-  std::vector<int32_t> list_off[2], list_n[2];     // [kind][group]
-  uint32_t *d_span_list = nullptr;
-  bool host_only = false;
-  int32_t rank_sum = 0;
-
+// The plan: its host half (fcp_plan_shape.h: everything decided without a device) and, here, what needs HIP or a device.
+struct fcp_plan : fcph::HostPlan {
+  uint32_t *d_span_list = nullptr; // device copy of span_list
   uint32_t *d_slot_map = nullptr;
   FcpColStatic *d_cols = nullptr;
   FcpXform *d_xforms = nullptr; // per column, only for plans with id transforms
   FcpSegMap *d_segmaps = nullptr; // per column, only for plans with segment-id maps
-  bool has_seg_map = false;
-  // Per-id weights / the sqrtn combiner (fcp_weighted.hip).  has_weights: some pooled column has weights — every descriptor
-  // slot then carries, behind its FcpColDyn records, one int64 per column (concat order): the byte offset of the column's
-  // weights in the request's blob, or -1 (shape-dependent like the records, installed and uploaded with them; plans
-  // without weighted columns have no such array).  weighted_kernel: has_weights, or some column's combiner is SQRTN — all
-  // spans of the plan run the weighted ragged kernel.
-  bool has_weights = false, weighted_kernel = false;
-  // Which unit's fused kernels serve the plan (fcp_internal.h): decided once, when the plan is created, by check_desc
-  // (fcp_plan_desc.h); the request path dispatches on it and on nothing else.
-  FcpVariant variant = FCP_VAR_F32;
   // Plain dense plan (fcp_dense_plain.hip): float32 concat output, one group, unsharded, V 4, no wide rows, no id transform,
   // every column a gather by int32 / int64 ids or by float32 values bucketized with reproducible boundaries.  Decided at
   // plan creation (FCP_DIAG=dense_generic keeps such a plan on the generic kernel).  Every descriptor slot then carries,
@@ -290,27 +210,6 @@ struct fcp_plan {
   std::vector<char> plain_tmpl;
   std::vector<std::pair<uint32_t, int32_t>> plain_entries;
   std::atomic<int32_t> last_dense_front{0}; // fcp_plan_last_dense_front: FCP_DENSE_FRONT_* of the last request
-  bool wide_rows = false; // some table shard has >= 2^32 - 3 slots: FcpLaunch::store_through bit 1
-  // narrow output (FCP_FLAG_OUT_BF16 / FCP_FLAG_OUT_F16): the element type (FCP_OUT_*) and its size in bytes — every byte
-  // quantity of the output region (group sizes, column bases, the position of the CSR scratch) is formed with out_elem
-  int out_kind = FCP_OUT_F32, out_elem = 4;
-  // 16-bit tables (FCP_FLAG_TABLES_BF16 / FCP_FLAG_TABLES_F16): the element type (FCP_TAB_*) of every table and its size in
-  // bytes.  Geometry, slot offsets and wide_rows are in elements and do not depend on it; fcp_plan_table_bytes does
-  int tab_kind = FCP_TAB_F32, tab_elem = 4;
-  // 8-bit row-quantised tables (FCP_FLAG_TABLES_Q8): tab_kind FCP_TAB_Q8, tab_elem 1, and 8 bytes of scale and bias behind
-  // every row.  Geometry stays in elements; the row STRIDE in slots, (dim + 8) / vec, is what scales a row index and what
-  // wide_rows is decided from
-  int tab_row_tail = 0;
-  // Per-input table formats (FCP_FLAG_TABLES_PER_INPUT) whose tables really differ: tab_kind FCP_TAB_MIXED, tab_elem 0, and the
-  // kind of every column's table (FCP_TAB_*, by plan column; FCP_TAB_F32 for columns without one) — it rides in bits 16..17
-  // of the column record's flags.  Plans whose tables all have one kind are the plan-wide plan of that kind: col_kind empty.
-  std::vector<int8_t> col_kind;
-  bool tab_mixed() const { return !col_kind.empty(); }
-  int col_tab_kind(size_t k) const { return col_kind.empty() ? tab_kind : col_kind[k]; }
-  // bytes of one row of the table column k reads
-  int64_t col_row_bytes(size_t k, int dim) const {
-    return fcpf::row_bytes(col_tab_kind(k), dim);
-  }
   std::vector<FcpColStatic> h_cols;
   char *d_const = nullptr;
   int32_t *d_seg_cols = nullptr;
@@ -485,10 +384,6 @@ struct StageRings {
 
 // ---- functions that cross translation units -----------------------------------------------------------------------
 // fcp_plan.hip
-int compute_dyn(const fcp_plan *p, const int32_t *offsets, const int32_t *shapes, const int32_t *symbols, int64_t blob_bytes,
-                FcpColDyn *dyn, DynMeta *m);
-// plans with weighted columns: the weights' byte offsets (per column, concat order; -1 = unweighted) for these shapes
-int compute_weights(const fcp_plan *p, const int32_t *offsets, const int32_t *shapes, int64_t *wts);
 // bytes of one descriptor slot: the FcpColDyn records and, in plans with weighted columns, the weights' offsets behind them
 inline size_t slot_dyn_bytes(const fcp_plan *p) {
   return p->cols.size() * sizeof(FcpColDyn) + (p->has_weights ? p->cols.size() * sizeof(int64_t) : 0) +

@@ -177,12 +177,10 @@ int install_slot(fcp_plan *p, const fcp_process_args_t *a, DynSlot &s) {
     }
     if (!p->host_writes_dyn && hipEventQuery(s.uploaded) != hipSuccess) HIP_TRY(hipEventSynchronize(s.uploaded));
   }
-  int rc = compute_dyn(p, a->concated_offsets, a->concated_shapes, a->symbols, a->concated_bytes, s.h_dyn, &s.meta);
+  // (the weights' blob offsets ride behind the records: one install, one upload)
+  int rc = evaluate_shapes(*p, a->concated_offsets, a->concated_shapes, a->symbols, a->concated_bytes, s.h_dyn,
+                           p->has_weights ? reinterpret_cast<int64_t *>(s.h_dyn + p->cols.size()) : nullptr, &s.meta);
   if (rc) return rc;
-  if (p->has_weights) { // the weights' blob offsets ride behind the records: one install, one upload
-    rc = compute_weights(p, a->concated_offsets, a->concated_shapes, reinterpret_cast<int64_t *>(s.h_dyn + p->cols.size()));
-    if (rc) return rc;
-  }
   p->last_work_bytes.store(s.meta.work_bytes, std::memory_order_relaxed);
   // Plain dense plans: requests of at least 64 rows (R = 4) take fcp_dense_kernel_plain and need the slot's span image.  It
   // holds table addresses, so it is built and handed to the device under the plan's mutex: a re-bind of the tables
@@ -550,7 +548,7 @@ int fcp_plan_traffic_bind(fcp_plan_t *p, uint32_t *const *counts, int32_t n_coun
   return FCP_OK;
 }
 
-// The request's descriptors come from the slot cache exactly as a request's do (same key, compute_dyn, upload, `done`
+// The request's descriptors come from the slot cache exactly as a request's do (same key, evaluate_shapes, upload, `done`
 // protocol): a count of resident shapes installs nothing, a count of new shapes installs what the request itself would.
 // Tables are neither bound nor read, no allocator is called.  (A plain dense plan's span image is built with the table
 // addresses the plan holds, null before the first bind; bind_tables rewrites the images of all slots.)

@@ -413,23 +413,19 @@ def test_tf_shim_parses_against_a_mock_of_the_tf_api():
     assert r.returncode == 0, r.stderr[-3000:]
 
 
-def test_fast_and_general_shape_evaluation_agree(monkeypatch):
-    """compute_dyn_fast (one pass, concat-layout plans) and the general routine give the same
-    arena size for every synthetic model, and the same error for an inconsistent request."""
-    from recom_amd import lib, synth
+def test_fast_and_general_shape_evaluation_agree():
+    """The arena size the built library gives (fcp_plan_arena_bytes -> evaluate_shapes) is the restated one
+    (plan_shape_cases.py) for every synthetic model, and an inconsistent request is a shape mismatch."""
+    import plan_shape_cases as S
+    from recom_amd import lib
     from recom_amd.ops import Plan, concat_inputs
-    models = [synth.model_mixed(batch=21, vocab=97, n_groups=2), synth.model_s1(), synth.model_ragged(columns=40, batch=17),
-              synth.model_ragged(columns=9, batch=5, seg="indices"), synth.model_dlrm(batch=33), synth.model_ae("E", batch=19)]
-    for m in models:
+    for _, m in S.agreement_models():
         p = Plan(m.spec, host_only=True)
         for seed in range(3):
             req = m.make_request(seed)
             _, _, shapes = concat_inputs(req.inputs)
-            monkeypatch.delenv("FCP_DIAG", raising=False)
-            fast = p.arena_bytes(shapes, req.symbols)
-            monkeypatch.setenv("FCP_DIAG", "dyn_general")
-            assert p.arena_bytes(shapes, req.symbols) == fast > 0
-        monkeypatch.delenv("FCP_DIAG", raising=False)
+            restated = S.evaluate(m.spec, S.plan_facts(m.spec), [0] * m.spec.n_host_inputs, shapes, req.symbols)["arena_bytes"][0]
+            assert p.arena_bytes(shapes, req.symbols) == restated > 0
         gather = [c for c in m.spec.columns if c.form == 1]
         if gather:                                    # a one-hot column one element longer: row counts disagree
             bad = np.array(shapes, np.int32)
@@ -439,9 +435,9 @@ def test_fast_and_general_shape_evaluation_agree(monkeypatch):
             assert e.value.status == lib.FCP_ERR_SHAPE_MISMATCH
 
 
-def test_external_slots_host_side(monkeypatch):
+def test_external_slots_host_side():
     """FCP_FORM_EXTERNAL (Addons>ConcatOutputs host inputs): reserved in the concat layout, not an output
-    of FeatureColumnProcess, rows from the group; both shape-evaluation routines agree; bad plans refused."""
+    of FeatureColumnProcess, rows from the group; the arena size is the restated one; bad plans refused."""
     import ctypes as C
     import dataclasses
     from recom_amd import lib, synth
@@ -462,11 +458,9 @@ def test_external_slots_host_side(monkeypatch):
     req = m.make_request(0)
     _, _, shapes = concat_inputs(req.inputs)
     base = Plan(m.spec, host_only=True).arena_bytes(shapes, req.symbols)
-    monkeypatch.delenv("FCP_DIAG", raising=False)
-    fast = p.arena_bytes(shapes, req.symbols)
-    monkeypatch.setenv("FCP_DIAG", "dyn_general")
-    assert p.arena_bytes(shapes, req.symbols) == fast > base
-    monkeypatch.delenv("FCP_DIAG", raising=False)
+    import plan_shape_cases as S
+    restated = S.evaluate(spec, S.plan_facts(spec), [0] * spec.n_host_inputs, shapes, req.symbols)["arena_bytes"][0]
+    assert p.arena_bytes(shapes, req.symbols) == restated > base
     for bad in (dataclasses.replace(ext, rows_source=ROWS_FROM_IDS),):
         with pytest.raises(ValueError):
             dataclasses.replace(m.spec, columns=m.spec.columns + [bad]).validate()
