@@ -932,6 +932,60 @@ int fcp_table_digest_rows(const void *table, int32_t kind, int64_t table_rows, i
  * it never touches a device.  Rows may start at any byte.  Returns 0 for invalid arguments (those of fcp_table_digest without
  * out and workspace), which is also the digest of no rows. */
 uint64_t fcp_table_digest_host(const void *first_row, int32_t kind, int64_t rows, int32_t dim, int64_t row0, int64_t row_step);
+/* ---- grouped digest: a model's tables, or a delta's rows in all of them, in one call ------------------------------------------ */
+/* fcp_tables_digest is fcp_table_digest and fcp_table_digest_rows for MANY tables: one fcp_table_digest_entry_t per table (an
+ * ENTRY), any mix of formats, dims and of the two modes, and a number of launches that does not grow with n_tables.  Once the
+ * stream has run, out[k] holds exactly the 32 bytes ONE call would have left for entry k — fcp_table_digest when its row_ids is
+ * NULL, fcp_table_digest_rows otherwise — `rows`, `skipped` and `reserved == 0` included; an entry with nothing to sum leaves
+ * zeros.  The value model is the one above.  Everything the single entries promise is inherited: no atomics, two calls leave the
+ * same bytes, no load touches a byte outside an entry's rows, q8 rows start at any byte, the alignment rules per kind, the row
+ * limits; asynchronous on `stream`, no allocation, no synchronisation.  Entries may alias (chunks of one table, the same table
+ * twice); tables are only read.
+ *
+ * `entries` is a HOST array of n_tables entries, n_tables in [0, 65536], read before the call returns.  `out` (n_tables records)
+ * and `workspace` (fcp_tables_digest_workspace_bytes of n_tables bytes; its content before and after the call means nothing,
+ * and it is the call's own until the stream has passed the call) are on the device, 8-byte aligned.  The workspace size
+ * depends on n_tables alone: a multiple of 8, non-decreasing, -1 outside the range.
+ *
+ * Launches.  An entry with rows belongs to the class (A, G, by-id) of the digest kernel it would run alone: A the largest
+ * power of two up to 8 that divides the entry's address and its row bytes, G the lanes that share a row (the largest power
+ * of two not above the row's 64-bit words, at most 64), by-id whether row_ids is set — 56 classes, none folded.  A call enqueues
+ * one upload, one launch per class PRESENT (a fixed order; entries inside a class in ascending order) and one fold: at most 58
+ * launches whatever n_tables is.  fcp_tables_digest_launches returns that number for the same arguments — 0 for n_tables ==
+ * 0, the negative status for invalid ones — from the function fcp_tables_digest builds its launch list with; host only.
+ * Alone, an entry of `count` rows (ids) takes B = min(2048, ceil(count / (256 / G))) blocks.  Grouped it takes at most that, at
+ * least 1 when it has rows: exactly B while the Bs of a call sum to 8192 or less, else max(1, floor(B * 8192 / sum)) — so
+ * the blocks of a call sum to at most 8192 + n_tables, and a single-entry call takes the single-table grid.  `blocks`, if
+ * not NULL, receives every entry's share (0 without rows).  The deal plays no part in the result: the sums are integers.
+ *
+ * Stream capture: a call with n_tables > 0 installs its records from the host (a pinned ring and an upload kernel, as
+ * fcp_tables_update_rows does), which a replay would not repeat: FCP_ERR_UNSUPPORTED while `stream` is capturing.
+ *
+ * Status, decided in this order (the first needs no device and dereferences no device pointer):
+ *   FCP_ERR_INVALID_ARGUMENT  n_tables outside [0, 65536]; a null `entries` with n_tables > 0; then, over the entries in
+ *                             ascending order, what the matching single-table entry refuses for the entry's fields, in its
+ *                             order (`table` is its first_row / table, `rows` its rows / table_rows), then a non-zero
+ *                             `reserved`, then n != 0 with a null row_ids; then a null (n_tables > 0) or misaligned `out`;
+ *                             then a null (n_tables > 0) or misaligned `workspace`.  fcp_last_error names the argument
+ *                             between backquotes, behind "fcp_tables_digest: entry k: " for an entry's;
+ *   FCP_OK                    n_tables == 0: no device is touched;
+ *   FCP_ERR_NO_DEVICE         no usable gfx950 device;
+ *   FCP_ERR_UNSUPPORTED       `stream` is capturing — the only case;
+ *   FCP_ERR_HIP               a runtime call or a kernel launch failed. */
+typedef struct fcp_table_digest_entry {
+  const void *table;        /* row_ids == NULL: the first of `rows` rows lying back to back (fcp_table_digest's first_row);
+                               else the table's BASE (fcp_table_digest_rows' table) */
+  const int64_t *row_ids;   /* device int64 [n], or NULL */
+  int64_t rows;             /* row_ids == NULL: rows to digest; else table_rows */
+  int64_t n;                /* ids; 0 when row_ids == NULL */
+  int64_t row0, row_step;
+  int32_t kind, dim;
+  int64_t reserved;         /* 0 */
+} fcp_table_digest_entry_t; /* 64 bytes */
+int64_t fcp_tables_digest_workspace_bytes(int32_t n_tables);
+int32_t fcp_tables_digest_launches(const fcp_table_digest_entry_t *entries, int32_t n_tables, int32_t *blocks /* host [n_tables] or NULL */);  /* host only */
+int fcp_tables_digest(const fcp_table_digest_entry_t *entries, int32_t n_tables, fcp_table_digest_t *out /* device [n_tables] */,
+                      void *workspace, int32_t device, void *stream);
 /* ---- outputs compare: what two requests' outputs differ by, per column ------------------------------------------------------- */
 /* The audits predict what a table ROW loses in a format.  fcp_outputs_compare measures what a request's OUTPUT lost: two plans —
  * float32 tables and the formats fcp_table_formats_choose picked, a plan before and after a delta, two kernel variants — serve

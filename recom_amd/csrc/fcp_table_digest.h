@@ -49,5 +49,11 @@ int check_digest(const void *first_row, int32_t kind, int64_t rows, int32_t dim,
                  const void *workspace, std::string *why);
 int check_digest_rows(const void *table, int32_t kind, int64_t table_rows, int32_t dim, int64_t row0, int64_t row_step, const void *row_ids,
                       int64_t n, const void *out, const void *workspace, std::string *why);
+// The same checks behind another text: `w` goes in front of the message in place of "fcp_table_digest: " /
+// "fcp_table_digest_rows: " (the grouped entry, fcp_tables_digest_plan.cc: "fcp_tables_digest: entry k: ").
+int check_digest(const std::string &w, const void *first_row, int32_t kind, int64_t rows, int32_t dim, int64_t row0, int64_t row_step,
+                 const void *out, const void *workspace, std::string *why);
+int check_digest_rows(const std::string &w, const void *table, int32_t kind, int64_t table_rows, int32_t dim, int64_t row0, int64_t row_step,
+                      const void *row_ids, int64_t n, const void *out, const void *workspace, std::string *why);
 
 } // namespace fcpd

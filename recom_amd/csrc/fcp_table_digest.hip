@@ -5,7 +5,8 @@
 // little-endian 64-bit words, the last one zero-padded; H(r) = mix(salt + (r + 1) * G + sum_j mix(w[j] ^ (j + 1) * G)); the
 // digest is the sum of H over the rows, modulo 2^64.  The reference reads float32 tables only and has no counterpart.
 //
-//   fcp_table_digest_kernel<A, G, BY_ID>   the grid of fcp_table_audit_kernel: kDigestBlocks blocks of FCP_BLOCK_THREADS, fewer
+//   fcp_table_digest_kernel<A, G, BY_ID>   (its body, digest_body, lives in fcp_table_digest_bodies.h: fcp_tables_digest.hip runs
+//                     the same text for many tables per call, with the block index and the grid local to an entry)  the grid of fcp_table_audit_kernel: kDigestBlocks blocks of FCP_BLOCK_THREADS, fewer
 //                     when the rows do not fill it, a 64-bit grid-stride walk, a power-of-two group of G <= 64 lanes per row —
 //                     G the largest power of two not above the row's words, so lane l of a group loads words l and l + G (fewer
 //                     than 2 G words unless G is 64: words l + 128, l + 192, ... in a loop) and a wave's loads of its rows are
@@ -34,131 +35,21 @@
 
 #pragma clang fp contract(off) // (the header's rule; nothing here is floating point)
 
-#include "fcp_table_walk.h" // with_group, with_one_of: the host's dispatch
-#include "fcp_block_fold.h" // wave_fold, block_fold: the fold of a lane's record into the block's
+#include "fcp_table_walk.h"          // with_group, with_one_of: the host's dispatch
+#include "fcp_table_digest_bodies.h" // digest_body, DigestPartial: shared with fcp_tables_digest.hip
+#include "fcp_block_fold.h"          // wave_fold, block_fold: the fold of a lane's record into the block's
+#include "fcp_tables_digest_plan.h"  // group_of_words, align_of, lone_blocks: the rules the grouped entry classes by
 
 namespace {
 
-using fcpd::row_hash;
-using fcpd::word_term;
+constexpr int kDigestBlocks = fcpg::kLoneBlocks; // the fixed grid: 8 blocks of 256 threads on each of 256 CUs; also the records of the workspace
 
-constexpr int kDigestBlocks = 2048; // the fixed grid: 8 blocks of 256 threads on each of 256 CUs; also the records of the workspace
-constexpr int kUnroll = 4;          // rows of a group per step of the walk
-
-// What a lane, a wave, a block and the whole call have summed.  32 bytes, 8-byte aligned.
-struct DigestPartial {
-  uint64_t sum;
-  int64_t rows, skipped, pad;
-};
-static_assert(sizeof(DigestPartial) == 32, "the workspace is kDigestBlocks records of 32 bytes");
-static_assert(sizeof(fcp_table_digest_t) == 32, "fcp_table_digest_t is 32 bytes");
-
-// loads of 8, 4 and 2 bytes from an address that is A-byte aligned (A-aligned for the narrower ones as far as they need it)
-template <int A> struct Loads;
-template <> struct Loads<8> {
-  typedef uint64_t U64;
-  typedef uint32_t U32;
-  typedef uint16_t U16;
-};
-template <> struct Loads<4> {
-  typedef uint64_t U64 __attribute__((aligned(4)));
-  typedef uint32_t U32;
-  typedef uint16_t U16;
-};
-template <> struct Loads<2> {
-  typedef uint64_t U64 __attribute__((aligned(2)));
-  typedef uint32_t U32 __attribute__((aligned(2)));
-  typedef uint16_t U16;
-};
-template <> struct Loads<1> {
-  typedef uint64_t U64 __attribute__((aligned(1)));
-  typedef uint32_t U32 __attribute__((aligned(1)));
-  typedef uint16_t U16 __attribute__((aligned(1)));
-};
-
-// word j of the row at `row`: a whole word for j < full, else the row's last rem = 1 .. 7 bytes, zero-padded.  The tail
-// starts 8 * full bytes into the row, as aligned as the row; its pieces lie at offsets 0, 4 and 6 at the most.
-template <int A> __device__ __forceinline__ uint64_t ld_row_word(const char *row, int j, int full, int rem) {
-  const char *p = row + 8 * (int64_t)j;
-  if (j < full) return *(const FCP_GLOBAL typename Loads<A>::U64 *)(p);
-  uint64_t w = 0;
-  int at = 0;
-  if (rem & 4) {
-    w = *(const FCP_GLOBAL typename Loads<A>::U32 *)(p);
-    at = 4;
-  }
-  if (rem & 2) {
-    w |= (uint64_t) * (const FCP_GLOBAL typename Loads<A>::U16 *)(p + at) << (8 * at);
-    at += 2;
-  }
-  if (rem & 1) w |= (uint64_t) * (const FCP_GLOBAL uint8_t *)(p + at) << (8 * at);
-  return w;
-}
-
-__device__ __forceinline__ void fold(DigestPartial &a, const DigestPartial &b) {
-  a.sum += b.sum;
-  a.rows += b.rows;
-  a.skipped += b.skipped;
-}
-
-// base: the first row (BY_ID: the table's base); count: rows (BY_ID: ids), < 2^32 - 3; rb: bytes of a row.  Block =
-// 256 / G rows per step; a group never straddles a wave, and it is live or not as a whole.  Every thread of a block takes
-// the same number of steps.  The instantiations without BY_ID never read row_ids or table_rows.
+// digest_body with the block's own index and the grid: see fcp_table_digest_bodies.h
 template <int A, int G, bool BY_ID>
 __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
     fcp_table_digest_kernel(const char *base, int64_t count, int32_t rb, uint64_t salt, uint64_t row0, uint64_t row_step,
                             const int64_t *row_ids, uint64_t table_rows, DigestPartial *partials) {
-  constexpr int kRowsPerBlock = FCP_BLOCK_THREADS / G;
-  const int tid = threadIdx.x;
-  const int lane = tid & (G - 1);
-  const int full = rb >> 3, rem = rb & 7;
-  const int nw = full + (rem != 0);
-  const int64_t stride = (int64_t)gridDim.x * kRowsPerBlock;
-  uint64_t sum = 0;
-  int64_t nrows = 0, nskipped = 0;
-  for (int64_t first = (int64_t)blockIdx.x * kRowsPerBlock; first < count; first += stride * kUnroll) {
-    uint64_t id[kUnroll], w[kUnroll], w2[kUnroll];
-    bool have[kUnroll], live[kUnroll];
-#pragma unroll
-    for (int u = 0; u < kUnroll; ++u) {
-      const int64_t i = first + u * stride + tid / G;
-      have[u] = i < count;
-      if constexpr (BY_ID) {
-        id[u] = have[u] ? (uint64_t) * as_global(row_ids + i) : ~0ull; // the whole group: one address
-        live[u] = have[u] && id[u] < table_rows;
-      } else {
-        id[u] = (uint64_t)i;
-        live[u] = have[u];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < kUnroll; ++u) {
-      w[u] = w2[u] = 0;
-      if (live[u] && lane < nw) w[u] = ld_row_word<A>(base + id[u] * (uint64_t)rb, lane, full, rem);
-      if (live[u] && lane + G < nw) w2[u] = ld_row_word<A>(base + id[u] * (uint64_t)rb, lane + G, full, rem);
-    }
-#pragma unroll
-    for (int u = 0; u < kUnroll; ++u) {
-      uint64_t t = (live[u] && lane < nw) ? word_term(w[u], (uint64_t)lane) : 0;
-      if (live[u] && lane + G < nw) t += word_term(w2[u], (uint64_t)(lane + G));
-      if constexpr (G == 64) {
-        if (live[u])
-          for (int j = lane + 128; j < nw; j += 64) t += word_term(ld_row_word<A>(base + id[u] * (uint64_t)rb, j, full, rem), (uint64_t)j);
-      }
-#pragma unroll
-      for (int m = G / 2; m >= 1; m >>= 1) t += __shfl_xor(t, m, 64);
-      if (lane == 0) {
-        if (live[u]) {
-          sum += row_hash(salt, row0 + id[u] * row_step, t);
-          ++nrows;
-        } else if (have[u]) {
-          ++nskipped;
-        }
-      }
-    }
-  }
-
-  block_fold(DigestPartial{sum, nrows, nskipped, 0}, partials);
+  block_fold(digest_body<A, G, BY_ID>(base, count, rb, salt, row0, row_step, row_ids, table_rows, blockIdx.x, gridDim.x), partials);
 }
 
 // one wave; n: records of the workspace the first kernel wrote (0: it was not launched)
@@ -167,13 +58,7 @@ __global__ void __launch_bounds__(64) fcp_table_digest_fold_kernel(const DigestP
   DigestPartial p = {0, 0, 0, 0};
   for (int i = lane; i < n; i += 64) fold(p, partials[i]);
   wave_fold(p);
-  if (lane != 0) return;
-  fcp_table_digest_t r;
-  r.sum = p.sum;
-  r.rows = p.rows;
-  r.skipped = p.skipped;
-  r.reserved = 0;
-  *out = r;
+  if (lane == 0) write_digest(out, p);
 }
 
 struct DigestLaunch {
@@ -196,14 +81,6 @@ template <int A, int G> void launch_ag(const DigestLaunch &L, hipStream_t s) {
                        L.row0, L.row_step, L.row_ids, L.table_rows, L.partials);
 }
 
-// G, the lanes that share a row: the largest power of two that is not above the row's words, at most 64 — a row of 9 words
-// (q8, dim 64) takes 8 lanes and two words in its first lane, not 16 lanes of which 7 idle
-int group_of_words(int64_t nw) {
-  int g = 1;
-  while (2 * g <= nw && g < 64) g <<= 1;
-  return g;
-}
-
 // Both entries behind their argument checks.  by_id: row_ids names `count` rows of the table at `base`; else `count` rows
 // lie back to back from `base`.
 int digest_entry(const char *who, const void *base, int32_t kind, int32_t dim, int64_t count, int64_t row0, int64_t row_step,
@@ -219,13 +96,9 @@ int digest_entry(const char *who, const void *base, int32_t kind, int32_t dim, i
   L.row_ids = row_ids;
   L.table_rows = (uint64_t)table_rows;
   L.partials = static_cast<DigestPartial *>(workspace);
-  const int g = group_of_words((rb + 7) / 8);
-  const int64_t rows_per_block = FCP_BLOCK_THREADS / g;
-  L.blocks = (int)std::min<int64_t>(kDigestBlocks, (count + rows_per_block - 1) / rows_per_block);
-  // what is known of every row's address: the base's low bits and the row bytes' (a q8 table of dim % 8 == 0 at an
-  // allocation's start takes the aligned loads)
-  const uintptr_t bits = (uintptr_t)base | (uintptr_t)rb | 8u;
-  const int a = (int)(bits & (~bits + 1));
+  const int g = fcpg::group_of_words((rb + 7) / 8);
+  L.blocks = (int)fcpg::lone_blocks(count, g);
+  const int a = fcpg::align_of(base, rb); // what is known of every row's address
   return on_device(who, device, stream, [&](hipStream_t s) {
     if (L.blocks > 0)
       with_one_of<8, 4, 2, 1>(a, [&](auto al) {

@@ -39,9 +39,8 @@ int check_aligned(const std::string &w, const char *name, const void *p, int ali
 
 } // namespace
 
-int check_digest(const void *first_row, int32_t kind, int64_t rows, int32_t dim, int64_t row0, int64_t row_step, const void *out,
-                 const void *workspace, std::string *why) {
-  const std::string w = "fcp_table_digest: ";
+int check_digest(const std::string &w, const void *first_row, int32_t kind, int64_t rows, int32_t dim, int64_t row0, int64_t row_step,
+                 const void *out, const void *workspace, std::string *why) {
   if (rows < 0) return refuse(why, w + "`rows` is negative");
   if (rows >= kRowLimit) return refuse(why, w + "`rows` must stay below 2^32 - 3, a plan's row limit");
   int rc = check_common(w, kind, dim, row0, row_step, rows, why);
@@ -54,9 +53,8 @@ int check_digest(const void *first_row, int32_t kind, int64_t rows, int32_t dim,
   return check_aligned(w, "workspace", workspace, 8, "", why);
 }
 
-int check_digest_rows(const void *table, int32_t kind, int64_t table_rows, int32_t dim, int64_t row0, int64_t row_step, const void *row_ids,
-                      int64_t n, const void *out, const void *workspace, std::string *why) {
-  const std::string w = "fcp_table_digest_rows: ";
+int check_digest_rows(const std::string &w, const void *table, int32_t kind, int64_t table_rows, int32_t dim, int64_t row0, int64_t row_step,
+                      const void *row_ids, int64_t n, const void *out, const void *workspace, std::string *why) {
   if (n < 0) return refuse(why, w + "`n` is negative");
   if (n >= kRowLimit) return refuse(why, w + "`n` must stay below 2^32 - 3");
   if (table_rows < 0 || table_rows >= kRowLimit) return refuse(why, w + "`table_rows` must lie in [0, 2^32 - 3), a plan's row limit");
@@ -70,6 +68,16 @@ int check_digest_rows(const void *table, int32_t kind, int64_t table_rows, int32
   if ((rc = check_aligned(w, "row_ids", row_ids, 8, "", why))) return rc;
   if ((rc = check_aligned(w, "out", out, 8, "", why))) return rc;
   return check_aligned(w, "workspace", workspace, 8, "", why);
+}
+
+int check_digest(const void *first_row, int32_t kind, int64_t rows, int32_t dim, int64_t row0, int64_t row_step, const void *out,
+                 const void *workspace, std::string *why) {
+  return check_digest("fcp_table_digest: ", first_row, kind, rows, dim, row0, row_step, out, workspace, why);
+}
+
+int check_digest_rows(const void *table, int32_t kind, int64_t table_rows, int32_t dim, int64_t row0, int64_t row_step, const void *row_ids,
+                      int64_t n, const void *out, const void *workspace, std::string *why) {
+  return check_digest_rows("fcp_table_digest_rows: ", table, kind, table_rows, dim, row0, row_step, row_ids, n, out, workspace, why);
 }
 
 } // namespace fcpd

@@ -28,6 +28,7 @@
 
 #include "fcp_table_walk.h"
 #include "fcp_table_rows_bodies.h"
+#include "fcp_find_piece.h" // find_piece: the search of a block for its entry
 #include "fcp_tables_rows_plan.h"
 
 static_assert(FCP_TAB_BF16 == FCP_OUT_BF16 && FCP_TAB_F16 == FCP_OUT_F16, "st_out_narrow takes the table kind as its output kind");
@@ -37,28 +38,6 @@ static_assert(sizeof(fcp_table_rows_t) == 64, "fcp_table_rows_t is 64 bytes");
 namespace {
 
 using fcpr::Rec;
-constexpr int kSearchSteps = 17; // ceil(log2(65536 + 1)): the most records of one launch
-
-// The piece block b of this launch belongs to, and b's index inside it.  prefix: n_recs + 1 ascending values, prefix[0] == 0,
-// prefix[n_recs] == gridDim.x; no two equal (a piece has rows, so blocks).  Scalar throughout: b is blockIdx.x.
-__device__ __forceinline__ Rec find_piece(const Rec *recs, const uint32_t *prefix, uint32_t n_recs, uint32_t b, uint32_t *local) {
-  const FCP_CONST uint32_t *p = as_const(prefix);
-  uint32_t lo = 0, hi = n_recs, first = 0; // prefix[lo] == first <= b < prefix[hi]
-#pragma unroll 1
-  for (int step = 0; step < kSearchSteps && hi - lo > 1; ++step) {
-    const uint32_t mid = (lo + hi) >> 1;
-    const uint32_t v = p[mid];
-    if (v <= b) {
-      lo = mid;
-      first = v;
-    } else {
-      hi = mid;
-    }
-  }
-  *local = b - first;
-  return ld_rec(as_const(recs) + lo);
-}
-
 template <int V, int G>
 __global__ void __launch_bounds__(FCP_BLOCK_THREADS) fcp_tables_update_q8_kernel(const Rec *recs, const uint32_t *prefix, uint32_t n_recs) {
   uint32_t block;

@@ -164,6 +164,12 @@ class TableRows(C.Structure):
                 ("kind", C.c_int32), ("dim", C.c_int32), ("reserved", C.c_int64 * 2)]
 
 
+class TableDigestEntry(C.Structure):
+    """fcp_table_digest_entry_t: one entry of fcp_tables_digest"""
+    _fields_ = [("table", C.c_void_p), ("row_ids", C.c_void_p), ("rows", C.c_int64), ("n", C.c_int64), ("row0", C.c_int64),
+                ("row_step", C.c_int64), ("kind", C.c_int32), ("dim", C.c_int32), ("reserved", C.c_int64)]
+
+
 class PrivateStreamsStats(C.Structure):
     """fcp_private_streams_stats_t"""
     _fields_ = [("supervised_stream", C.c_void_p), ("requests", C.c_int64), ("lane_requests", C.c_int64), ("evaluations", C.c_int64),
@@ -219,6 +225,7 @@ EXPORTS = [
     "fcp_table_diff_workspace_bytes", "fcp_table_diff",
     "fcp_outputs_compare_workspace_bytes", "fcp_outputs_compare",
     "fcp_tables_rows_workspace_bytes", "fcp_tables_rows_launches", "fcp_tables_update_rows", "fcp_tables_read_rows",
+    "fcp_tables_digest_workspace_bytes", "fcp_tables_digest_launches", "fcp_tables_digest",
 ]
 
 _lib = None
@@ -423,6 +430,12 @@ def load() -> C.CDLL:
         L.fcp_tables_rows_launches.argtypes = [C.POINTER(TableRows), C.c_int32]
         L.fcp_tables_update_rows.argtypes = [C.POINTER(TableRows), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.fcp_tables_read_rows.argtypes = [C.POINTER(TableRows), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    if hasattr(L, "fcp_tables_digest"):
+        L.fcp_tables_digest_workspace_bytes.restype = C.c_int64
+        L.fcp_tables_digest_workspace_bytes.argtypes = [C.c_int32]
+        L.fcp_tables_digest_launches.restype = C.c_int32
+        L.fcp_tables_digest_launches.argtypes = [C.POINTER(TableDigestEntry), C.c_int32, C.POINTER(C.c_int32)]
+        L.fcp_tables_digest.argtypes = [C.POINTER(TableDigestEntry), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     if L.fcp_abi_version() != FCP_ABI_VERSION:
         raise ImportError("libfcp_hip.so ABI version mismatch; rebuild")
     _lib = L

@@ -8,7 +8,9 @@ by which the audit weighs its sums (``fcp_table_audit_weighted``); ``new_plan_co
 which ``Plan.traffic_bind`` / ``Plan.traffic_count`` (recom_amd/ops.py) fill from requests through the plan's own id path;
 and the digest of a table of any format — an order-free 64-bit sum of row hashes, on the device (``fcp_table_digest`` /
 ``fcp_table_digest_rows``, recom_amd/csrc/fcp_table_digest.hip) and from host memory (``fcp_table_digest_host``) — by which a
-deployment checks that a served table is, byte for byte, the table it should be, and keeps that check across ``update_rows``;
+deployment checks that a served table is, byte for byte, the table it should be, and keeps that check across ``update_rows``
+— for a whole model's tables in one call (``fcp_tables_digest``, recom_amd/csrc/fcp_tables_digest.hip: ``digests_grouped``,
+``digest_rows_grouped``, ``update_rows_grouped_tracked``, ``digest_tables``);
 and, for deltas that name a row more than once, the ids made distinct on the device with the last occurrence winning
 (``fcp_table_delta_distinct``, recom_amd/csrc/fcp_table_delta.hip), in front of ``update_rows`` and the digest bookkeeping, which
 both ask for distinct ids and do not check (``apply_delta``);
@@ -593,10 +595,121 @@ def digest_host(array, dtype: str, dim: Optional[int] = None, row0: int = 0, row
 def digest_tables(spec: PlanSpec, tables: Sequence, stream: Optional[int] = None) -> list:
     """One ``digest`` per device input of ``spec`` that a lookup column reads (a shared table once), ``None`` for the others.
     The tables are the rank's own — any format — and ``row0 = spec.shard_rank, row_step = spec.shard_world``: the lists of the
-    ranks of a row-sharded plan add up, entry by entry modulo 2^64, to the unsharded plan's."""
-    read = set(spec.read_inputs())
-    return [digest(t, row0=spec.shard_rank, row_step=spec.shard_world, stream=stream) if i in read else None
-            for i, t in enumerate(tables)]
+    ranks of a row-sharded plan add up, entry by entry modulo 2^64, to the unsharded plan's.  One ``fcp_tables_digest`` call
+    and one synchronise for the whole plan (``digests_grouped``)."""
+    read = [i for i in sorted(set(spec.read_inputs())) if i < len(tables)]
+    sums = digests_grouped([tables[i] for i in read], row0=spec.shard_rank, row_step=spec.shard_world, stream=stream)
+    out = [None] * len(tables)
+    for i, s in zip(read, sums):
+        out[i] = s
+    return out
+
+
+# ---- digest, many tables in one call (fcp_tables_digest) --------------------------------------------------------------------------
+def _per_table(value, n: int, what: str) -> list:
+    """``value`` for each of n entries: a scalar for all of them, or a sequence of n"""
+    if hasattr(value, "__len__"):
+        if len(value) != n:
+            raise ValueError(f"tables names {n} entries, {what} {len(value)}")
+        return [int(v) for v in value]
+    return [int(value)] * n
+
+
+def _digest_entries(torch, tables_, row_ids, row0, row_step):
+    """The ``fcp_table_digest_entry_t`` array of ``tables_`` — with ``row_ids`` (a sequence as long) the by-id entries, without
+    the rows of each table back to back — each entry validated as ``digest`` / ``digest_rows`` validate theirs, and the one
+    device all of it lives on (``None`` for no entries)."""
+    n_tables = len(tables_)
+    if row_ids is not None and len(row_ids) != n_tables:
+        raise ValueError(f"tables names {n_tables} entries, row_ids {len(row_ids)}")
+    row0s, steps = _per_table(row0, n_tables, "row0"), _per_table(row_step, n_tables, "row_step")
+    entries = (_lib.TableDigestEntry * max(n_tables, 1))()
+    device = None
+    for k, t in enumerate(tables_):
+        try:
+            name, dim = _kind_and_dim(t, "table")
+            n = _ids_of(torch, t, row_ids[k]) if row_ids is not None else 0
+        except ValueError as e:
+            raise ValueError(f"entry {k}: {e}") from None
+        if device is None:
+            device = t.device
+        elif t.device != device:
+            raise ValueError(f"entry {k}: table is on {t.device}, entry 0's on {device}")
+        # (an empty id tensor may have no address: the entry then reads as "no rows back to back", which sums the same nothing)
+        ids_ptr = row_ids[k].data_ptr() if n else None
+        entries[k] = _lib.TableDigestEntry(t.data_ptr(), ids_ptr, int(t.shape[0]) if n or row_ids is None else 0, n, row0s[k], steps[k],
+                                           _lib.TABLE_KINDS[name], dim, 0)
+    return entries, device
+
+
+def _grouped_digest_buffers(torch, L, device, stream: int, n_tables: int, n_out: int = 1):
+    """``n_out`` result arrays of ``n_tables`` records and one workspace (calls on one stream run one after the other and may
+    share it), allocated as that stream's (``_digest_buffers`` says why)"""
+    words = C.sizeof(_lib.TableDigest) // 8
+    with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device)):
+        outs = torch.empty((n_out, n_tables, words), dtype=torch.int64, device=device)
+        workspace = torch.empty((int(L.fcp_tables_digest_workspace_bytes(n_tables)) // 8,), dtype=torch.int64, device=device)
+    return outs, workspace
+
+
+def _enqueue_digests(L, entries, n_tables: int, out, workspace, device, stream: int) -> None:
+    status = L.fcp_tables_digest(entries, n_tables, C.c_void_p(out.data_ptr()), C.c_void_p(workspace.data_ptr()), device.index or 0,
+                                 C.c_void_p(stream))
+    _lib.check(status, "fcp_tables_digest")
+
+
+def _grouped_digests(tables_, row_ids, row0, row_step, stream: Optional[int]) -> list:
+    """the ``TableDigest`` records of one ``fcp_tables_digest`` call, read after one synchronise"""
+    import torch
+    entries, device = _digest_entries(torch, tables_, row_ids, row0, row_step)
+    if device is None:
+        return []
+    L = _lib.load()
+    stream = _stream_of(torch, device, stream)
+    outs, workspace = _grouped_digest_buffers(torch, L, device, stream, len(tables_))
+    _enqueue_digests(L, entries, len(tables_), outs[0], workspace, device, stream)
+    torch.cuda.ExternalStream(stream, device=device).synchronize()
+    return _digests_of(outs[0])
+
+
+def digests_grouped(tables, row0=0, row_step=1, stream: Optional[int] = None) -> list:
+    """``fcp_tables_digest``: ``digest`` of many tables in ONE call and one synchronise — entry k is what
+    ``digest(tables[k], row0[k], row_step[k])`` returns, in any mix of formats and dims on one device; the number of launches
+    does not grow with their number.  ``row0`` / ``row_step``: a scalar for every table, or one value per table.  Tables may
+    be row ranges ``t[a:b]`` (with ``row0=a``) and may name the same memory more than once."""
+    return [int(d.sum) for d in _grouped_digests(tables, None, row0, row_step, stream)]
+
+
+def digest_rows_grouped(tables, row_ids, row0=0, row_step=1, stream: Optional[int] = None) -> list:
+    """``fcp_tables_digest`` by id: ``digest_rows`` of many tables in ONE call and one synchronise — entry k is the
+    ``(sum, rows, skipped)`` that ``digest_rows(tables[k], row_ids[k], row0[k], row_step[k])`` returns."""
+    if row_ids is None:
+        raise ValueError("row_ids is a sequence of int64 [n] tensors, one per table")
+    return [(int(d.sum), int(d.rows), int(d.skipped)) for d in _grouped_digests(tables, row_ids, row0, row_step, stream)]
+
+
+def update_rows_grouped_tracked(tables, row_ids, rows, digests, row0=0, row_step=1, skipped=None, stream: Optional[int] = None) -> list:
+    """``update_rows_grouped`` with every table's digest kept up to date from the touched rows alone: one grouped digest of
+    ``row_ids`` before, the grouped update, one grouped digest after — all on ``stream``, one synchronise at the end — and
+    ``(digests[k] - before[k] + after[k]) mod 2^64`` is returned per table: the ``digest`` of the updated table when
+    ``digests[k]`` was that of the table before and its ids are pairwise distinct (not checked)."""
+    import torch
+    if len(digests) != len(tables):
+        raise ValueError(f"tables names {len(tables)} entries, digests {len(digests)}")
+    entries, device = _digest_entries(torch, tables, row_ids, row0, row_step)
+    if device is None:
+        update_rows_grouped(tables, row_ids, rows, skipped=skipped, stream=stream)
+        return []
+    L = _lib.load()
+    n_tables = len(tables)
+    stream = _stream_of(torch, device, stream)
+    outs, workspace = _grouped_digest_buffers(torch, L, device, stream, n_tables, n_out=2)
+    _enqueue_digests(L, entries, n_tables, outs[0], workspace, device, stream)
+    update_rows_grouped(tables, row_ids, rows, skipped=skipped, stream=stream)
+    _enqueue_digests(L, entries, n_tables, outs[1], workspace, device, stream)
+    torch.cuda.ExternalStream(stream, device=device).synchronize()
+    before, after = _digests_of(outs[0]), _digests_of(outs[1])
+    return [(int(d) - int(b.sum) + int(a.sum)) % (1 << 64) for d, b, a in zip(digests, before, after)]
 
 
 def update_rows_tracked(table, row_ids, rows, digest: int, row0: int = 0, row_step: int = 1, skipped=None,
