@@ -382,6 +382,28 @@ struct StageRings {
   }
 };
 
+bool stream_is_capturing(hipStream_t stream); // (fcp_process.hip)
+
+// A host-built descriptor image into the caller's workspace, for the kernels the entry enqueues behind it on `stream`: the one
+// place that orders the slot's hand-over.  The caller has entered the device.  In this order: a capturing stream is refused
+// (FCP_ERR_UNSUPPORTED, "<who>: " + capture_refusal; null where the caller has refused it already); *d_image is the workspace's
+// first 16-byte boundary; a slot of `rings` is leased; fill(char *slot) writes all image_bytes on the host, the padding of its
+// sections as zeros (the slot holds an earlier call's bytes; zeroing it whole here cost fcp_outputs_compare a microsecond in
+// a thousand columns); a fence; the upload kernel slot -> *d_image; the slot's read event (the slot is free once that has run).
+template <class F> int upload_image(const char *who, StageRings &rings, int32_t device, hipStream_t stream, void *workspace, size_t image_bytes,
+                                    const char *capture_refusal, F fill, char **d_image) {
+  if (capture_refusal && stream_is_capturing(stream)) return fail(FCP_ERR_UNSUPPORTED, std::string(who) + ": " + capture_refusal);
+  *d_image = reinterpret_cast<char *>(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
+  StageRings::Lease sl;
+  int rc = rings.acquire(device, image_bytes, &sl);
+  if (rc) return rc;
+  fill(sl.buf);
+  __atomic_thread_fence(__ATOMIC_SEQ_CST); // the image is in memory before the launch that reads it is queued
+  const int e = fcp_launch_upload(sl.buf_dev, *d_image, image_bytes, stream);
+  if (e) return hip_fail((std::string(who) + ": descriptor upload launch").c_str(), (hipError_t)e);
+  return sl.record(stream);
+}
+
 // ---- functions that cross translation units -----------------------------------------------------------------------
 // fcp_plan.hip
 // bytes of one descriptor slot: the FcpColDyn records and, in plans with weighted columns, the weights' offsets behind them
@@ -395,8 +417,7 @@ inline const int64_t *slot_weights(const fcp_plan *p, const FcpColDyn *dyn) {
   return p->has_weights ? reinterpret_cast<const int64_t *>(dyn + p->cols.size()) : nullptr;
 }
 void build_plain_template(fcp_plan *p); // the gate and the image template of plain dense plans (plan creation)
-// fcp_process.hip
-bool stream_is_capturing(hipStream_t stream);
+// fcp_process.hip (and stream_is_capturing, above)
 int bind_tables(fcp_plan *p, const void *const *input_ptrs, bool capturing);
 void build_key(const fcp_plan *p, const fcp_process_args_t *a, std::vector<int32_t> &key);
 int find_or_reserve(fcp_plan *p, const std::vector<int32_t> &key, DynSlot **out, bool *install, bool capturing);

@@ -362,32 +362,30 @@ extern "C" int fcp_outputs_compare(const void *const *ptrs_a, const int64_t *row
 
   const int T = tiles_of(n_columns);
   const size_t image_bytes = (size_t)n_columns * sizeof(CmpColumn);
-  CmpColumn *d_cols = reinterpret_cast<CmpColumn *>(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
-  CmpPartial *d_partials = reinterpret_cast<CmpPartial *>(reinterpret_cast<char *>(d_cols) + image_bytes);
-
-  // the descriptor image goes through a slot of this entry's pinned ring (StageRings, fcp_host.h)
+  // the descriptor image goes through a slot of this entry's pinned ring, filled in place (upload_image, fcp_host.h; the capture
+  // was refused above, in front of the waits)
   static StageRings rings;
-  StageRings::Lease sl;
-  if ((rc = rings.acquire(device, image_bytes, &sl))) return rc;
   const int ea = elem_bytes(out_kind_a), eb = elem_bytes(out_kind_b);
-  CmpColumn *h = reinterpret_cast<CmpColumn *>(sl.buf);
-  for (int32_t k = 0; k < n_columns; ++k) {
-    CmpColumn c;
-    c.a = static_cast<const char *>(ptrs_a[k]);
-    c.b = static_cast<const char *>(ptrs_b[k]);
-    c.stride_a = row_strides_a[k];
-    c.stride_b = row_strides_b[k];
-    c.rows = shapes[2 * k];
-    c.dim = shapes[2 * k + 1];
-    c.vec = vec_of_column(c, ea, eb);
-    const int slots = c.dim / c.vec;
-    c.tile_rows = slots <= FCP_BLOCK_THREADS ? FCP_BLOCK_THREADS / slots : 1;
-    h[k] = c;
-  }
-  __atomic_thread_fence(__ATOMIC_SEQ_CST); // the image is in memory before the launch that reads it is queued
-  const int e = fcp_launch_upload(sl.buf_dev, d_cols, image_bytes, stream);
-  if (e) return hip_fail("fcp_outputs_compare: descriptor upload launch", (hipError_t)e);
-  if ((rc = sl.record(stream))) return rc; // the slot is free once the upload has run
+  char *d_image;
+  rc = upload_image("fcp_outputs_compare", rings, device, stream, workspace, image_bytes, nullptr, [&](char *buf) {
+    CmpColumn *h = reinterpret_cast<CmpColumn *>(buf);
+    for (int32_t k = 0; k < n_columns; ++k) {
+      CmpColumn c;
+      c.a = static_cast<const char *>(ptrs_a[k]);
+      c.b = static_cast<const char *>(ptrs_b[k]);
+      c.stride_a = row_strides_a[k];
+      c.stride_b = row_strides_b[k];
+      c.rows = shapes[2 * k];
+      c.dim = shapes[2 * k + 1];
+      c.vec = vec_of_column(c, ea, eb);
+      const int slots = c.dim / c.vec;
+      c.tile_rows = slots <= FCP_BLOCK_THREADS ? FCP_BLOCK_THREADS / slots : 1;
+      h[k] = c;
+    }
+  }, &d_image);
+  if (rc) return rc;
+  CmpColumn *d_cols = reinterpret_cast<CmpColumn *>(d_image);
+  CmpPartial *d_partials = reinterpret_cast<CmpPartial *>(d_image + image_bytes);
   launch_compare(out_kind_a, out_kind_b, dim3((unsigned)((int64_t)n_columns * T)), stream, d_cols, (int32_t)T, d_partials);
   hipLaunchKernelGGL(fcp_outputs_compare_fold_kernel, dim3((unsigned)((n_columns + 63) / 64)), dim3(64), 0, stream, d_cols, d_partials,
                      n_columns, (int32_t)T, out);

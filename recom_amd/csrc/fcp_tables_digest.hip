@@ -34,7 +34,7 @@
 #include "fcp_table_walk.h"          // with_group, with_one_of: the host's dispatch
 #include "fcp_table_digest_bodies.h" // digest_body, DigestPartial
 #include "fcp_block_fold.h"          // wave_fold, block_fold
-#include "fcp_find_piece.h"          // find_piece: the search of a block for its entry
+#include "fcp_grouped_front.h"       // find_piece: the search of a block for its entry, asserted against the launch list's bounds
 #include "fcp_tables_digest_plan.h"
 
 static_assert(fcpg::kBlockThreads == FCP_BLOCK_THREADS, "the deal of blocks is made for these kernels");
@@ -45,7 +45,6 @@ namespace {
 using fcpg::Rec;
 using fcpg::Run;
 static_assert(fcpg::kPartialBytes == sizeof(DigestPartial), "the workspace formula counts these records");
-static_assert(fcpg::kMaxTables + 1 <= (1 << kSearchSteps), "find_piece's steps reach every record of a launch");
 
 constexpr int kFoldWaves = FCP_BLOCK_THREADS / 64; // entries per block of the fold kernel
 
@@ -118,25 +117,16 @@ extern "C" int fcp_tables_digest(const fcp_table_digest_entry_t *entries, int32_
   DeviceGuard guard;
   if ((rc = guard.enter(device))) return rc;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (stream_is_capturing(stream))
-    return fail(FCP_ERR_UNSUPPORTED, w + "stream capture of a call with entries: their records are installed from the host by every "
-                                         "call, which a replay would not repeat");
-  char *d_image = reinterpret_cast<char *>(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
+  char *d_image;
+  rc = upload_image("fcp_tables_digest", rings, device, stream, workspace, image_bytes,
+                    "stream capture of a call with entries: their records are installed from the host by every call, which a replay would "
+                    "not repeat",
+                    [&](char *buf) { L.write_image(buf); }, &d_image);
+  if (rc) return rc;
   const Rec *d_recs = reinterpret_cast<const Rec *>(d_image);
   const uint32_t *d_prefix = reinterpret_cast<const uint32_t *>(d_image + recs_bytes);
   const Run *d_runs = reinterpret_cast<const Run *>(d_image + recs_bytes + prefix_bytes);
   DigestPartial *d_partials = reinterpret_cast<DigestPartial *>(d_image + partials_off);
-
-  StageRings::Lease sl;
-  if ((rc = rings.acquire(device, image_bytes, &sl))) return rc;
-  std::memset(sl.buf, 0, image_bytes); // (the padding behind the prefixes and the runs)
-  if (recs_bytes) std::memcpy(sl.buf, L.recs.data(), recs_bytes);
-  if (!L.prefix.empty()) std::memcpy(sl.buf + recs_bytes, L.prefix.data(), L.prefix.size() * sizeof(uint32_t));
-  std::memcpy(sl.buf + recs_bytes + prefix_bytes, L.runs.data(), L.runs.size() * sizeof(Run));
-  __atomic_thread_fence(__ATOMIC_SEQ_CST); // the image is in memory before the launch that reads it is queued
-  const int e = fcp_launch_upload(sl.buf_dev, d_image, image_bytes, stream);
-  if (e) return hip_fail((w + "descriptor upload launch").c_str(), (hipError_t)e);
-  if ((rc = sl.record(stream))) return rc; // the slot is free once the upload has run
   for (const fcpg::Launch &l : L.launches) launch(l, d_recs + l.first_rec, d_prefix + l.prefix_off, d_partials + l.partial_first, stream);
   hipLaunchKernelGGL(fcp_tables_digest_fold_kernel, dim3((n_tables + kFoldWaves - 1) / kFoldWaves), dim3(FCP_BLOCK_THREADS), 0, stream, d_runs,
                      d_partials, n_tables, out);

@@ -14,14 +14,13 @@
 #include <string>
 #include <vector>
 
-#include "../../include/fcp_hip.h"
-#include "fcp_formats.h"
+#include "fcp_grouped_plan.h" // what the grouped entries share: constants, refusals, class sort, launch list
 
 namespace fcpg {
 
-constexpr int32_t kMaxTables = 65536;  // n_tables lies in [0, kMaxTables]
-constexpr int kBlockThreads = 256;     // FCP_BLOCK_THREADS (fcp_tables_digest.hip asserts it)
-constexpr int kLoneBlocks = 2048;      // the most blocks of one table: 8 blocks of 256 threads on each of 256 CUs
+using fcpgp::kBlockThreads;
+using fcpgp::kMaxTables;
+constexpr int kLoneBlocks = 2048;     // the most blocks of one table: 8 blocks of 256 threads on each of 256 CUs
 constexpr int64_t kDealBlocks = 8192;  // the blocks of one call sum to at most kDealBlocks + n_tables
 constexpr int kClasses = 4 * 7 * 2;    // A 8, 4, 2, 1 x G 1 .. 64 x by-id
 constexpr int kMaxLaunches = kClasses + 2;
@@ -65,23 +64,22 @@ struct Run {
 };
 static_assert(sizeof(Run) == 8, "one run per entry, 8 bytes");
 
-// One kernel launch: the entries recs[first_rec .. first_rec + n_recs) of ONE class and prefix[prefix_off .. prefix_off +
-// n_recs]: the first block of each entry in this launch's grid, ascending from 0, and the grid itself as the last value.  Block b
-// writes partial record partial_first + b.
+// One kernel launch (fcpgp::LaunchList): entries of ONE class.  Block b writes partial record partial_first + b.
 struct Launch {
   int32_t align, group, by_id;
   uint32_t first_rec, n_recs, prefix_off, blocks, partial_first;
 };
 
-struct LaunchList {
-  std::vector<Rec> recs;        // grouped by launch
-  std::vector<uint32_t> prefix; // n_recs + 1 values per launch
-  std::vector<Run> runs;        // one per entry of the call, in entry order
-  std::vector<Launch> launches;
-  // bytes of the image: the records, the prefixes, the runs (each a 16-byte multiple)
-  size_t recs_bytes() const { return recs.size() * sizeof(Rec); }
-  size_t prefix_bytes() const { return (prefix.size() * sizeof(uint32_t) + 15) / 16 * 16; }
+// The image: the records, the prefixes, the runs (each a 16-byte multiple)
+struct LaunchList : fcpgp::LaunchList<Rec, Launch> {
+  std::vector<Run> runs; // one per entry of the call, in entry order
   size_t runs_bytes() const { return (runs.size() * sizeof(Run) + 15) / 16 * 16; }
+  void write_image(char *buf) const { // all three sections, their padding zeroed
+    fcpgp::LaunchList<Rec, Launch>::write_image(buf);
+    const size_t used = runs.size() * sizeof(Run);
+    if (used) std::memcpy(buf + recs_bytes() + prefix_bytes(), runs.data(), used);
+    std::memset(buf + recs_bytes() + prefix_bytes() + used, 0, runs_bytes() - used);
+  }
   size_t image_bytes() const { return recs_bytes() + prefix_bytes() + runs_bytes(); }
 };
 

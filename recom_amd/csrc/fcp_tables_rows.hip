@@ -28,7 +28,7 @@
 
 #include "fcp_table_walk.h"
 #include "fcp_table_rows_bodies.h"
-#include "fcp_find_piece.h" // find_piece: the search of a block for its entry
+#include "fcp_grouped_front.h" // find_piece: the search of a block for its entry, asserted against the launch list's bounds
 #include "fcp_tables_rows_plan.h"
 
 static_assert(FCP_TAB_BF16 == FCP_OUT_BF16 && FCP_TAB_F16 == FCP_OUT_F16, "st_out_narrow takes the table kind as its output kind");
@@ -93,22 +93,14 @@ int run(const char *who, bool update, StageRings &rings, const fcp_table_rows_t 
   DeviceGuard guard;
   if ((rc = guard.enter(device))) return rc;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (stream_is_capturing(stream))
-    return fail(FCP_ERR_UNSUPPORTED, w + "stream capture of a call with rows: the entries' records are installed from the host by "
-                                         "every call, which a replay would not repeat");
-  char *d_image = reinterpret_cast<char *>(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
+  char *d_image;
+  rc = upload_image(who, rings, device, stream, workspace, image_bytes,
+                    "stream capture of a call with rows: the entries' records are installed from the host by every call, which a replay "
+                    "would not repeat",
+                    [&](char *buf) { L.write_image(buf); }, &d_image);
+  if (rc) return rc;
   const Rec *d_recs = reinterpret_cast<const Rec *>(d_image);
   const uint32_t *d_prefix = reinterpret_cast<const uint32_t *>(d_image + recs_bytes);
-
-  StageRings::Lease sl;
-  if ((rc = rings.acquire(device, image_bytes, &sl))) return rc;
-  std::memcpy(sl.buf, L.recs.data(), recs_bytes);
-  std::memset(sl.buf + recs_bytes, 0, image_bytes - recs_bytes);
-  std::memcpy(sl.buf + recs_bytes, L.prefix.data(), L.prefix.size() * sizeof(uint32_t));
-  __atomic_thread_fence(__ATOMIC_SEQ_CST); // the image is in memory before the launch that reads it is queued
-  const int e = fcp_launch_upload(sl.buf_dev, d_image, image_bytes, stream);
-  if (e) return hip_fail((w + "descriptor upload launch").c_str(), (hipError_t)e);
-  if ((rc = sl.record(stream))) return rc; // the slot is free once the upload has run
   for (const fcpr::Launch &l : L.launches) launch(l, update, d_recs + l.first_rec, d_prefix + l.prefix_off, stream);
   const hipError_t le = hipGetLastError();
   return le == hipSuccess ? FCP_OK : hip_fail((w + "kernel launch").c_str(), le);

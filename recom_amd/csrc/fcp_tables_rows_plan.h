@@ -8,13 +8,12 @@
 #include <string>
 #include <vector>
 
-#include "../../include/fcp_hip.h"
-#include "fcp_formats.h"
+#include "fcp_grouped_plan.h" // what the grouped entries share: constants, refusals, class sort, launch list
 
 namespace fcpr {
 
-constexpr int32_t kMaxTables = 65536;            // n_tables lies in [0, kMaxTables]
-constexpr int kBlockThreads = 256;               // FCP_BLOCK_THREADS (fcp_tables_rows.hip asserts it)
+using fcpgp::kBlockThreads;
+using fcpgp::kMaxTables;
 constexpr int64_t kMaxLaunchThreads = 1ll << 30; // per launch, as the single-table hosts chunk (fcp_table_walk.h)
 constexpr int64_t kMaxLaunchBlocks = kMaxLaunchThreads / kBlockThreads;
 // One call names at most 2^40 elements — 4 TiB of float32 rows, beyond any device.  The bound is what makes the workspace a
@@ -41,22 +40,13 @@ struct Rec {
 };
 static_assert(sizeof(Rec) == 64, "the descriptor image's records are 64 bytes");
 
-// One kernel launch: the pieces recs[first_rec .. first_rec + n_recs) of ONE class — (vec, group) for a q8 update, (vec, 0)
-// for every other update and for every read — and prefix[prefix_off .. prefix_off + n_recs]: the first block of each piece in
-// this launch's grid, ascending from 0, and the grid itself as the last value.  n_recs <= kMaxTables + 1: 17 search steps.
+// One kernel launch (fcpgp::LaunchList): pieces of ONE class — (vec, group) for a q8 update, (vec, 0) for every other update
+// and for every read.  n_recs <= kMaxTables + 1.  The image: the records, then the prefixes.
 struct Launch {
   int32_t vec, group;
   uint32_t first_rec, n_recs, prefix_off, blocks;
 };
-
-struct LaunchList {
-  std::vector<Rec> recs;        // grouped by launch
-  std::vector<uint32_t> prefix; // n_recs + 1 values per launch
-  std::vector<Launch> launches;
-  // bytes of the image: the records, then the prefixes (both 16-byte multiples)
-  size_t recs_bytes() const { return recs.size() * sizeof(Rec); }
-  size_t prefix_bytes() const { return (prefix.size() * sizeof(uint32_t) + 15) / 16 * 16; }
-};
+using LaunchList = fcpgp::LaunchList<Rec, Launch>;
 
 // The checks of fcp_table_update_rows / fcp_table_read_rows up to `skipped`, in their stated order; `w` goes in front of the
 // message, which names the argument between backquotes.  FCP_OK, or FCP_ERR_INVALID_ARGUMENT with *why.

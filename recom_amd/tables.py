@@ -195,32 +195,48 @@ def read_rows(table, row_ids, out=None, stream: Optional[int] = None):
 
 
 # ---- rows by id, many tables in one call (fcp_tables_update_rows / fcp_tables_read_rows) --------------------------------------
-def _grouped_entries(torch, tables_, row_ids, rows, what: str):
-    """The ``fcp_table_rows_t`` array of equally long sequences, each entry validated as ``update_rows`` / ``read_rows``
-    validate theirs, and the one device all of it lives on (``None`` for no entries)."""
-    if len(row_ids) != len(tables_) or len(rows) != len(tables_):
-        raise ValueError(f"tables names {len(tables_)} entries, row_ids {len(row_ids)}, {what} {len(rows)}")
-    entries = (_lib.TableRows * max(len(tables_), 1))()
+def _entries_of(struct, tables_, entry_of):
+    """The ``struct`` array of a grouped call and the one device all of it lives on (``None`` for no entries):
+    ``entry_of(k, table)`` validates entry k and returns the arguments of its struct; what it refuses goes behind "entry k: "."""
+    entries = (struct * max(len(tables_), 1))()
     device = None
-    for k, (t, ids, r) in enumerate(zip(tables_, row_ids, rows)):
+    for k, t in enumerate(tables_):
         try:
-            name, dim = _kind_and_dim(t, "table")
-            n = _ids_of(torch, t, ids)
-            _rows_of(torch, t, dim, n, r, what)
+            args = entry_of(k, t)
         except ValueError as e:
             raise ValueError(f"entry {k}: {e}") from None
         if device is None:
             device = t.device
         elif t.device != device:
             raise ValueError(f"entry {k}: table is on {t.device}, entry 0's on {device}")
-        entries[k] = _lib.TableRows(t.data_ptr(), ids.data_ptr(), r.data_ptr(), int(t.shape[0]), n, _lib.TABLE_KINDS[name], dim)
+        entries[k] = struct(*args)
     return entries, device
 
 
-def _grouped_workspace(torch, L, device, stream: int, n_tables: int):
-    """the call's workspace, allocated as that stream's (``_digest_buffers`` says why)"""
+def _as_streams(torch, device, stream: int, *shapes) -> list:
+    """int64 device tensors of ``shapes``, in that order, allocated as that stream's: a block the caching allocator hands out
+    may still have work pending on the stream it was freed on.  A workspace of N bytes is ``(N // 8,)``."""
     with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device)):
-        return torch.empty((int(L.fcp_tables_rows_workspace_bytes(n_tables)) // 8,), dtype=torch.int64, device=device)
+        return [torch.empty(shape, dtype=torch.int64, device=device) for shape in shapes]
+
+
+def _grouped_entries(torch, tables_, row_ids, rows, what: str):
+    """The ``fcp_table_rows_t`` array of equally long sequences, each entry validated as ``update_rows`` / ``read_rows``
+    validate theirs, and the one device all of it lives on (``None`` for no entries)."""
+    if len(row_ids) != len(tables_) or len(rows) != len(tables_):
+        raise ValueError(f"tables names {len(tables_)} entries, row_ids {len(row_ids)}, {what} {len(rows)}")
+
+    def entry_of(k, t):
+        name, dim = _kind_and_dim(t, "table")
+        n = _ids_of(torch, t, row_ids[k])
+        _rows_of(torch, t, dim, n, rows[k], what)
+        return t.data_ptr(), row_ids[k].data_ptr(), rows[k].data_ptr(), int(t.shape[0]), n, _lib.TABLE_KINDS[name], dim
+    return _entries_of(_lib.TableRows, tables_, entry_of)
+
+
+def _grouped_workspace(torch, L, device, stream: int, n_tables: int):
+    """the call's workspace, allocated as that stream's"""
+    return _as_streams(torch, device, stream, (int(L.fcp_tables_rows_workspace_bytes(n_tables)) // 8,))[0]
 
 
 def update_rows_grouped(tables, row_ids, rows, skipped=None, stream: Optional[int] = None):
@@ -240,8 +256,7 @@ def update_rows_grouped(tables, row_ids, rows, skipped=None, stream: Optional[in
     if device is None:
         return tables
     L = _lib.load()
-    if stream is None:
-        stream = torch.cuda.current_stream(device).cuda_stream
+    stream = _stream_of(torch, device, stream)
     workspace = _grouped_workspace(torch, L, device, stream, n_tables)
     status = L.fcp_tables_update_rows(entries, n_tables, C.c_void_p(skipped.data_ptr()) if skipped is not None else None,
                                       C.c_void_p(workspace.data_ptr()), device.index or 0, C.c_void_p(stream))
@@ -257,8 +272,8 @@ def read_rows_grouped(tables, row_ids, out=None, stream: Optional[int] = None) -
     import torch
     if len(row_ids) != len(tables):
         raise ValueError(f"tables names {len(tables)} entries, row_ids {len(row_ids)}")
-    if stream is None and len(tables) and getattr(tables[0], "is_cuda", False):
-        stream = torch.cuda.current_stream(tables[0].device).cuda_stream
+    if len(tables) and getattr(tables[0], "is_cuda", False):
+        stream = _stream_of(torch, tables[0].device, stream)
     if out is None:
         out = []
         for k, (t, ids) in enumerate(zip(tables, row_ids)):
@@ -496,12 +511,8 @@ def choose_dtypes(spec: PlanSpec, audits: Sequence, budget_bytes: int, allowed: 
 # ---- digest (fcp_table_digest / fcp_table_digest_rows / fcp_table_digest_host) -------------------------------------------------
 def _digest_buffers(torch, L, device, stream: int, n_out: int = 1):
     """``n_out`` result records and one workspace (calls on one stream run one after the other and may share it), allocated as
-    that stream's: a block the caching allocator hands out may still have work pending on the stream it was freed on"""
-    words = C.sizeof(_lib.TableDigest) // 8
-    with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device)):
-        outs = torch.empty((n_out, words), dtype=torch.int64, device=device)
-        workspace = torch.empty((int(L.fcp_table_digest_workspace_bytes()) // 8,), dtype=torch.int64, device=device)
-    return outs, workspace
+    that stream's (``_as_streams`` says why)"""
+    return _as_streams(torch, device, stream, (n_out, C.sizeof(_lib.TableDigest) // 8), (int(L.fcp_table_digest_workspace_bytes()) // 8,))
 
 
 def _digests_of(outs) -> list:
@@ -623,33 +634,21 @@ def _digest_entries(torch, tables_, row_ids, row0, row_step):
     if row_ids is not None and len(row_ids) != n_tables:
         raise ValueError(f"tables names {n_tables} entries, row_ids {len(row_ids)}")
     row0s, steps = _per_table(row0, n_tables, "row0"), _per_table(row_step, n_tables, "row_step")
-    entries = (_lib.TableDigestEntry * max(n_tables, 1))()
-    device = None
-    for k, t in enumerate(tables_):
-        try:
-            name, dim = _kind_and_dim(t, "table")
-            n = _ids_of(torch, t, row_ids[k]) if row_ids is not None else 0
-        except ValueError as e:
-            raise ValueError(f"entry {k}: {e}") from None
-        if device is None:
-            device = t.device
-        elif t.device != device:
-            raise ValueError(f"entry {k}: table is on {t.device}, entry 0's on {device}")
+
+    def entry_of(k, t):
+        name, dim = _kind_and_dim(t, "table")
+        n = _ids_of(torch, t, row_ids[k]) if row_ids is not None else 0
         # (an empty id tensor may have no address: the entry then reads as "no rows back to back", which sums the same nothing)
         ids_ptr = row_ids[k].data_ptr() if n else None
-        entries[k] = _lib.TableDigestEntry(t.data_ptr(), ids_ptr, int(t.shape[0]) if n or row_ids is None else 0, n, row0s[k], steps[k],
-                                           _lib.TABLE_KINDS[name], dim, 0)
-    return entries, device
+        return t.data_ptr(), ids_ptr, int(t.shape[0]) if n or row_ids is None else 0, n, row0s[k], steps[k], _lib.TABLE_KINDS[name], dim, 0
+    return _entries_of(_lib.TableDigestEntry, tables_, entry_of)
 
 
 def _grouped_digest_buffers(torch, L, device, stream: int, n_tables: int, n_out: int = 1):
     """``n_out`` result arrays of ``n_tables`` records and one workspace (calls on one stream run one after the other and may
-    share it), allocated as that stream's (``_digest_buffers`` says why)"""
-    words = C.sizeof(_lib.TableDigest) // 8
-    with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device)):
-        outs = torch.empty((n_out, n_tables, words), dtype=torch.int64, device=device)
-        workspace = torch.empty((int(L.fcp_tables_digest_workspace_bytes(n_tables)) // 8,), dtype=torch.int64, device=device)
-    return outs, workspace
+    share it), allocated as that stream's"""
+    return _as_streams(torch, device, stream, (n_out, n_tables, C.sizeof(_lib.TableDigest) // 8),
+                       (int(L.fcp_tables_digest_workspace_bytes(n_tables)) // 8,))
 
 
 def _enqueue_digests(L, entries, n_tables: int, out, workspace, device, stream: int) -> None:

@@ -4,8 +4,8 @@
 //   tables_digest_plan_san SEED SETS
 // Drives the launch-list builder over SETS random entry lists — every kind, dims of every G, every alignment the kind allows,
 // both modes, empty entries, entries beyond the fixed grid (their pointers are numbers: nothing is dereferenced) — and checks,
-// per list, what the kernels rely on: every launch's first-block table starts at 0, ascends strictly and ends at the grid; a
-// launch holds entries of ONE class, in ascending order; the records say what the entries say; the launches' partial records lie
+// per list, what the kernels rely on: the launch list's own promises (grouped_image_check.h: first-block tables from 0, strictly
+// ascending, ending at the grid); a launch holds entries of ONE class, in ascending order; the records say what the entries say; the launches' partial records lie
 // back to back, every entry's run is exactly its blocks inside its launch's, no two runs meet, and all of them lie inside the
 // partial area of the workspace of n_tables; the image ends in front of that area.  Then the deal's promises and the
 // refusals, in order.  Prints `<n> sets` and `<n> failures`.
@@ -30,6 +30,7 @@ static int failures = 0;
       std::printf("\n");             \
     }                                \
   } while (0)
+#include "grouped_image_check.h" // check_launch_list: what both grouped entries' kernels rely on (needs EXPECT)
 
 static const uintptr_t A = uintptr_t(1) << 40; // aligned for everything
 
@@ -75,45 +76,41 @@ static void check_set(const std::vector<fcp_table_digest_entry_t> &es, int set) 
   EXPECT(16 + partials_off + (fcpg::kDealBlocks + n_tables) * (int64_t)fcpg::kPartialBytes == fcpg::workspace_bytes(n_tables), "set %d: workspace", set);
   EXPECT((int)L.launches.size() <= fcpg::kClasses && (int64_t)L.runs.size() == n_tables, "set %d: %zu launches", set, L.launches.size());
   std::vector<int> seen((size_t)n_tables, 0);
-  size_t rec = 0, pre = 0;
-  uint32_t partial = 0;
-  int last_class = -1;
-  for (const fcpg::Launch &l : L.launches) {
-    EXPECT(l.first_rec == rec && l.prefix_off == pre && l.partial_first == partial, "set %d: launches are not back to back", set);
-    EXPECT(l.n_recs >= 1 && l.n_recs <= (uint32_t)fcpg::kMaxTables, "set %d: %u entries in a launch", set, l.n_recs);
-    const int cls = (l.by_id * 4 + (l.align == 8 ? 0 : l.align == 4 ? 1 : l.align == 2 ? 2 : 3)) * 128 + l.group;
-    EXPECT(cls > last_class, "set %d: classes out of order", set);
-    last_class = cls;
-    uint32_t first = 0;
-    int last_k = -1;
-    for (uint32_t j = 0; j < l.n_recs; ++j) {
-      const fcpg::Rec &r = L.recs[rec + j];
-      EXPECT(L.prefix[pre + j] == first, "set %d: prefix[%u] = %u, want %u", set, j, L.prefix[pre + j], first);
-      // which entry: the one whose run starts here
-      int k = -1;
-      for (int c = last_k + 1; c < n_tables && k < 0; ++c)
-        if (L.runs[c].n && L.runs[c].first == partial + first) k = c;
-      EXPECT(k >= 0, "set %d: a record without an entry", set);
-      if (k < 0) break;
-      last_k = k;
-      ++seen[k];
-      const fcp_table_digest_entry_t &e = es[k];
-      const int64_t rb = fcpf::row_bytes(e.kind, e.dim);
-      EXPECT(l.align == fcpg::align_of(e.table, rb) && l.group == fcpg::group_of_words((rb + 7) / 8) && (l.by_id != 0) == (e.row_ids != nullptr),
-             "set %d: entry %d in a launch of class (%d, %d, %d)", set, k, l.align, l.group, l.by_id);
-      EXPECT((uintptr_t)e.table % l.align == 0 && rb % l.align == 0, "set %d: entry %d: loads of %d bytes", set, k, l.align);
-      EXPECT(r.base == e.table && r.ids == e.row_ids && r.count == (uint64_t)count_of(e) && r.table_rows == (e.row_ids ? (uint64_t)e.rows : 0) &&
-                 r.salt == fcpd::salt_of(e.kind, e.dim) && r.row0 == (uint64_t)e.row0 && r.row_step == (uint64_t)e.row_step && r.rb == rb &&
-                 r.blocks == blocks[k] && L.runs[k].n == blocks[k],
-             "set %d: entry %d: record", set, k);
-      first += r.blocks;
-    }
-    EXPECT(L.prefix[pre + l.n_recs] == first && l.blocks == first, "set %d: grid %u, entries sum to %u", set, l.blocks, first);
-    rec += l.n_recs;
-    pre += l.n_recs + 1;
-    partial += l.blocks;
-  }
-  EXPECT(rec == L.recs.size() && pre == L.prefix.size(), "set %d: records left over", set);
+  uint32_t partial = 0, next_partial = 0; // the launch's first partial record, the next launch's
+  int last_class = -1, last_k = -1;
+  check_launch_list(
+      L, (int64_t)L.image_bytes(), fcpg::workspace_bytes(n_tables), set,
+      [&](const fcpg::Launch &l) {
+        partial = next_partial;
+        next_partial += l.blocks;
+        last_k = -1;
+        EXPECT(l.partial_first == partial, "set %d: partial records are not back to back", set);
+        EXPECT(l.n_recs <= (uint32_t)fcpg::kMaxTables, "set %d: %u entries in a launch", set, l.n_recs);
+        const int cls = (l.by_id * 4 + (l.align == 8 ? 0 : l.align == 4 ? 1 : l.align == 2 ? 2 : 3)) * 128 + l.group;
+        EXPECT(cls > last_class, "set %d: classes out of order", set);
+        last_class = cls;
+      },
+      [&](const fcpg::Launch &l, const fcpg::Rec &r, uint32_t first) {
+        // which entry: the one whose run starts here
+        int k = -1;
+        for (int c = last_k + 1; c < n_tables && k < 0; ++c)
+          if (L.runs[c].n && L.runs[c].first == partial + first) k = c;
+        EXPECT(k >= 0, "set %d: a record without an entry", set);
+        if (k < 0) return r.blocks;
+        last_k = k;
+        ++seen[k];
+        const fcp_table_digest_entry_t &e = es[k];
+        const int64_t rb = fcpf::row_bytes(e.kind, e.dim);
+        EXPECT(l.align == fcpg::align_of(e.table, rb) && l.group == fcpg::group_of_words((rb + 7) / 8) && (l.by_id != 0) == (e.row_ids != nullptr),
+               "set %d: entry %d in a launch of class (%d, %d, %d)", set, k, l.align, l.group, l.by_id);
+        EXPECT((uintptr_t)e.table % l.align == 0 && rb % l.align == 0, "set %d: entry %d: loads of %d bytes", set, k, l.align);
+        EXPECT(r.base == e.table && r.ids == e.row_ids && r.count == (uint64_t)count_of(e) && r.table_rows == (e.row_ids ? (uint64_t)e.rows : 0) &&
+                   r.salt == fcpd::salt_of(e.kind, e.dim) && r.row0 == (uint64_t)e.row0 && r.row_step == (uint64_t)e.row_step && r.rb == rb &&
+                   r.blocks == blocks[k] && L.runs[k].n == blocks[k],
+               "set %d: entry %d: record", set, k);
+        return r.blocks;
+      });
+  partial = next_partial;
   EXPECT((int64_t)partial == sum && (int64_t)partial <= fcpg::kDealBlocks + n_tables, "set %d: %u partial records", set, partial);
   // runs: disjoint, inside the area
   std::vector<std::pair<uint32_t, uint32_t>> runs;
@@ -129,6 +126,14 @@ static void check_set(const std::vector<fcp_table_digest_entry_t> &es, int set) 
     end = r.first + r.second;
   }
   EXPECT(end <= partial, "set %d: a run leaves the partial records", set);
+  // the image as the upload moves it: the three sections, the padding of the last two zeros, not a byte behind it
+  std::vector<unsigned char> image(L.image_bytes() + 1, 0x5a), want(L.image_bytes() + 1, 0);
+  want.back() = 0x5a;
+  if (!L.recs.empty()) std::memcpy(want.data(), L.recs.data(), L.recs_bytes());
+  if (!L.prefix.empty()) std::memcpy(want.data() + L.recs_bytes(), L.prefix.data(), L.prefix.size() * 4);
+  if (!L.runs.empty()) std::memcpy(want.data() + L.recs_bytes() + L.prefix_bytes(), L.runs.data(), L.runs.size() * sizeof(fcpg::Run));
+  L.write_image(reinterpret_cast<char *>(image.data()));
+  EXPECT(image == want, "set %d: the image's bytes", set);
 }
 
 int main(int argc, char **argv) {

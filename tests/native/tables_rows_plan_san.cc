@@ -3,8 +3,9 @@
 //   tables_rows_plan_san SEED SETS
 // Drives the launch-list builder over SETS random entry sets — every kind, dims of every V and G, empty entries, entries of
 // more than 2^30 threads (their pointers are numbers: nothing is dereferenced) — and checks, per set, what the kernels rely on:
-// every launch's first-block table starts at 0, ascends strictly and ends at the grid; the grid is the sum of its pieces'
-// blocks and stays within 2^22 unless the launch is one piece; a launch holds at most 65537 pieces of ONE class; the pieces of
+// the launch list's own promises (grouped_image_check.h: first-block tables from 0, strictly ascending, ending at the grid; at
+// most 65537 pieces in a launch); the grid is the sum of its pieces' blocks and stays within 2^22 unless the launch is one
+// piece; a launch holds pieces of ONE class; the pieces of
 // an entry tile its rows exactly, in order, with ids / rows / skipped pointing where the single-table host would point; the
 // image fits the workspace of n_tables.  Then the refusals, in order.  Prints `<n> sets` and `<n> failures`.
 #include <algorithm>
@@ -28,6 +29,7 @@ static int failures = 0;
       std::printf("\n");             \
     }                                \
   } while (0)
+#include "grouped_image_check.h" // check_launch_list: what both grouped entries' kernels rely on (needs EXPECT)
 
 static const uintptr_t A = uintptr_t(1) << 40; // aligned for everything
 
@@ -53,44 +55,33 @@ static void check_set(const std::vector<fcp_table_rows_t> &es, bool update, int 
   if (rc) return;
   fcpr::LaunchList L;
   fcpr::build_launches(es.data(), n_tables, update, skipped, &L);
-  EXPECT((int64_t)(16 + L.recs_bytes() + L.prefix_bytes()) <= fcpr::workspace_bytes(n_tables), "set %d: the image outgrows the workspace", set);
   EXPECT((int64_t)L.recs.size() <= n_tables + fcpr::kExtraRecs && (int64_t)L.launches.size() <= fcpr::kMaxLaunches, "set %d: bounds", set);
   std::map<const void *, int64_t> next_row; // by ids base of the entry -> rows seen so far
   std::map<uintptr_t, int> by_ids;
   for (int k = 0; k < n_tables; ++k) by_ids[(uintptr_t)es[k].row_ids] = k;
-  size_t rec = 0, pre = 0;
-  for (const fcpr::Launch &l : L.launches) {
-    EXPECT(l.first_rec == rec && l.prefix_off == pre, "set %d: launches are not back to back", set);
-    EXPECT(l.n_recs >= 1 && l.n_recs <= (uint32_t)fcpr::kMaxTables + 1, "set %d: %u pieces in a launch", set, l.n_recs);
-    EXPECT(l.blocks <= fcpr::kMaxLaunchBlocks || l.n_recs == 1, "set %d: a launch of %u blocks and %u pieces", set, l.blocks, l.n_recs);
-    uint32_t first = 0;
-    for (uint32_t j = 0; j < l.n_recs; ++j) {
-      const fcpr::Rec &r = L.recs[rec + j];
-      EXPECT(L.prefix[pre + j] == first, "set %d: prefix[%u] = %u, want %u", set, j, L.prefix[pre + j], first);
-      // which entry: the one whose ids the piece points into
-      auto it = by_ids.upper_bound((uintptr_t)r.ids);
-      --it;
-      const fcp_table_rows_t &e = es[it->second];
-      const int vec = fcpf::vec_of(e.dim);
-      const int group = update && e.kind == FCP_TAB_Q8 ? fcpf::group_of(e.dim, vec) : 0;
-      EXPECT(l.vec == vec && l.group == group, "set %d: entry %d in a launch of class (%d, %d)", set, it->second, l.vec, l.group);
-      const int64_t spr = e.dim / vec, r0 = r.ids - e.row_ids;
-      const int64_t rows = group ? (int64_t)r.n : (int64_t)r.n / spr;
-      const int64_t threads = group ? rows * group : (int64_t)r.n;
-      EXPECT(rows >= 1 && (group || (int64_t)r.n == rows * spr), "set %d: a piece of %u units", set, r.n);
-      EXPECT(r0 == next_row[e.row_ids] && r.rows == e.rows + r0 * e.dim, "set %d: entry %d: piece at row %" PRId64, set, it->second, r0);
-      EXPECT(threads <= fcpr::kMaxLaunchThreads || rows == 1, "set %d: a piece of %" PRId64 " threads", set, threads);
-      next_row[e.row_ids] = r0 + rows;
-      EXPECT(r.table == e.table && r.table_rows == (uint64_t)e.table_rows && r.dim == e.dim && r.kind == e.kind && r.spr == (uint32_t)spr && r.pad == 0,
-             "set %d: entry %d: record", set, it->second);
-      EXPECT(r.skipped == (skipped ? skipped + it->second : nullptr), "set %d: entry %d: skipped", set, it->second);
-      first += (uint32_t)((threads + fcpr::kBlockThreads - 1) / fcpr::kBlockThreads);
-    }
-    EXPECT(L.prefix[pre + l.n_recs] == first && l.blocks == first, "set %d: grid %u, pieces sum to %u", set, l.blocks, first);
-    rec += l.n_recs;
-    pre += l.n_recs + 1;
-  }
-  EXPECT(rec == L.recs.size() && pre == L.prefix.size(), "set %d: records left over", set);
+  check_launch_list(
+      L, (int64_t)(L.recs_bytes() + L.prefix_bytes()), fcpr::workspace_bytes(n_tables), set,
+      [&](const fcpr::Launch &l) { EXPECT(l.blocks <= fcpr::kMaxLaunchBlocks || l.n_recs == 1, "set %d: a launch of %u blocks and %u pieces", set, l.blocks, l.n_recs); },
+      [&](const fcpr::Launch &l, const fcpr::Rec &r, uint32_t) {
+        // which entry: the one whose ids the piece points into
+        auto it = by_ids.upper_bound((uintptr_t)r.ids);
+        --it;
+        const fcp_table_rows_t &e = es[it->second];
+        const int vec = fcpf::vec_of(e.dim);
+        const int group = update && e.kind == FCP_TAB_Q8 ? fcpf::group_of(e.dim, vec) : 0;
+        EXPECT(l.vec == vec && l.group == group, "set %d: entry %d in a launch of class (%d, %d)", set, it->second, l.vec, l.group);
+        const int64_t spr = e.dim / vec, r0 = r.ids - e.row_ids;
+        const int64_t rows = group ? (int64_t)r.n : (int64_t)r.n / spr;
+        const int64_t threads = group ? rows * group : (int64_t)r.n;
+        EXPECT(rows >= 1 && (group || (int64_t)r.n == rows * spr), "set %d: a piece of %u units", set, r.n);
+        EXPECT(r0 == next_row[e.row_ids] && r.rows == e.rows + r0 * e.dim, "set %d: entry %d: piece at row %" PRId64, set, it->second, r0);
+        EXPECT(threads <= fcpr::kMaxLaunchThreads || rows == 1, "set %d: a piece of %" PRId64 " threads", set, threads);
+        next_row[e.row_ids] = r0 + rows;
+        EXPECT(r.table == e.table && r.table_rows == (uint64_t)e.table_rows && r.dim == e.dim && r.kind == e.kind && r.spr == (uint32_t)spr && r.pad == 0,
+               "set %d: entry %d: record", set, it->second);
+        EXPECT(r.skipped == (skipped ? skipped + it->second : nullptr), "set %d: entry %d: skipped", set, it->second);
+        return (uint32_t)((threads + fcpr::kBlockThreads - 1) / fcpr::kBlockThreads);
+      });
   for (int k = 0; k < n_tables; ++k)
     EXPECT(next_row[es[k].row_ids] == std::max<int64_t>(es[k].n, 0), "set %d: entry %d: %" PRId64 " of %" PRId64 " rows", set, k, next_row[es[k].row_ids], es[k].n);
 }

@@ -113,6 +113,15 @@ def test_status_codes_arrive_in_the_stated_order():
         status, msg = _compare(**bad)
         assert status == INV and word in msg, (name, msg)
         bad[name] = fixed
+    # the sentences around the shared staging routine (upload_image, fcp_host.h), whole: the workspace's two, and — no device
+    # here, so from the unit's text with its adjacent string literals joined — the refusal of a capturing stream
+    assert _compare(workspace=0) == (INV, "fcp_outputs_compare: `workspace` is null")
+    assert _compare(workspace=A + 4) == (INV, "fcp_outputs_compare: `workspace` is not 8-byte aligned")
+    with open(os.path.join(ROOT, "recom_amd", "csrc", "fcp_outputs_compare.hip")) as f:
+        unit = re.sub(r'"\s*\n\s*"', "", f.read())
+    assert ('fail(FCP_ERR_UNSUPPORTED, "fcp_outputs_compare: stream capture of a call with columns: their descriptors are installed from '
+            'the host by every call, which a replay would not repeat")') in unit
+    assert unit.index("stream_is_capturing(stream)") < unit.index("wait_for_inputs(ptrs_a")     # refused in front of the waits
     if not torch.cuda.is_available():
         assert _compare(**bad)[0] == NODEV
         # what IS valid gets as far as the device: rows 0 with null pointers, n_columns 0 with null arrays (the zero record is

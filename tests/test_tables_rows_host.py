@@ -374,3 +374,21 @@ def test_the_launch_list_builder_alone_under_address_and_undefined_sanitizers(tm
     run = subprocess.run([exe, "20261020", "400"], capture_output=True, text=True, timeout=300)
     assert run.returncode == 0 and run.stderr == "", run.stdout[-2000:] + run.stderr[-4000:]
     assert run.stdout.splitlines()[-2:] == ["400 sets", "0 failures"], run.stdout[-2000:]
+
+
+def test_the_shared_grouped_plan_header_alone_under_address_and_undefined_sanitizers(tmp_path):
+    """recom_amd/csrc/fcp_grouped_plan.h — the class sort, the launch-list builder and the refusals that the grouped rows and the
+    grouped digest entries share — needs no unit of the library; a stand-alone program (tests/native/grouped_plan_san.cc) built
+    with -fsanitize=address,undefined drives the sort against std::stable_sort, the builder with and without a block cap,
+    log2_of and the refusals' whole texts, and prints `0 failures` with no sanitizer report.  Nothing is loaded into python."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "grouped_plan_san")
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I", CSRC,
+                            os.path.join(ROOT, "tests", "native", "grouped_plan_san.cc"), "-o", exe], capture_output=True, text=True)
+    if build.returncode != 0 and ("asan" in build.stderr.lower() or "ubsan" in build.stderr.lower()):
+        pytest.skip("libasan / libubsan not installed")
+    assert build.returncode == 0, build.stderr
+    run = subprocess.run([exe, "20261021", "600"], capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0 and run.stderr == "", run.stdout[-2000:] + run.stderr[-4000:]
+    assert run.stdout.splitlines()[-2:] == ["600 sets", "0 failures"], run.stdout[-2000:]
