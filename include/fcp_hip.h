@@ -1125,13 +1125,14 @@ enum {
   /* the per-input-format instantiations of the three (FCP_FLAG_TABLES_PER_INPUT plans whose tables really differ) */
   FCP_LAUNCH_DENSE_TABMIX = 14, FCP_LAUNCH_RAGGED_TABMIX = 15, FCP_LAUNCH_HYBRID_TABMIX = 16
 };
-enum { FCP_LAUNCH_STORE_NT = 0, FCP_LAUNCH_STORE_SC1_NT = 1, FCP_LAUNCH_STORE_PLAIN = 4 };
+/* (FCP_LAUNCH_STORE_SC1: write-through without the streaming hint, a form of the plain dense kernel alone) */
+enum { FCP_LAUNCH_STORE_NT = 0, FCP_LAUNCH_STORE_SC1_NT = 1, FCP_LAUNCH_STORE_PLAIN = 4, FCP_LAUNCH_STORE_SC1 = 8 };
 enum { FCP_LAUNCH_SEG_NONE = 0, FCP_LAUNCH_SEG_PREPASS = 1, FCP_LAUNCH_SEG_SEARCH = 2 };
 typedef struct fcp_launch_info {
   int32_t kernel;           /* FCP_LAUNCH_*: no kernel (empty request), dense, ragged, the hybrid of the two, or the weighted ragged kernel */
   int32_t vec;              /* floats per slot (V of the instantiation): the gcd of the plan's column dims, 1 | 2 | 4 */
   int32_t rows_per_wave;    /* dense body (R of the instantiation): 1 | 2 | 4 */
-  int32_t store_policy;     /* FCP_LAUNCH_STORE_*: output stores `nt`, write-through `sc1 nt`, or plain */
+  int32_t store_policy;     /* FCP_LAUNCH_STORE_*: output stores `nt`, write-through `sc1 nt`, plain, or `sc1` */
   int32_t wide_rows;        /* 1: 64-bit row arithmetic in the dense body (a table shard of >= 2^32 - 3 slots) */
   int32_t shard_world;      /* > 1: the SHARDED instantiation (row-sharded plan) */
   int32_t dense_blocks;     /* blocks of the dense body (0: none) */

@@ -24,7 +24,7 @@
 #include <vector>
 
 #include "../../include/fcp_hip.h"
-#include "fcp_fused_bodies.h" // (--mix-probe: the product's table loads and its three output stores)
+#include "fcp_fused_bodies.h" // (--mix-probe: the product's table loads and st_out's three output stores)
 #include "fcp_env.h"
 #include "fcp_plain_map.h"    // (--mix-probe: the product's block mapping)
 #include "numa_util.h"
@@ -82,6 +82,14 @@ __global__ void fill_table(float *t, uint32_t seed, uint64_t vocab, uint32_t dim
 // depend on nothing: tptr[q] per 16-byte slot of the concat row, roff[row][q] per output slot.  That is 4 bytes of coalesced
 // reads per output slot (S2: 15.4 MB against the 3.9 MB of ids the product reads).  --mix-probe 2 (col_of != null) reads
 // the offsets per (row, column) instead — fewer bytes than the ids, but behind one dependent hop (slot -> column).
+// Four store policies: st_out's three and the bare `sc1` form (write-through, no streaming hint; policy bit 3), which the
+// probe keeps as a copy of its own so that it can be measured whether or not a kernel of the library has it.
+__device__ __forceinline__ void probe_st_sc1(float *p, const VF<4> &v) {
+  VecType<4>::T t;
+  __builtin_memcpy(&t, &v, sizeof(t));
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(as_global(reinterpret_cast<VecType<4>::T *>(p))), "v"(t) : "memory");
+}
+constexpr int kProbeStSc1 = 8;
 __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
 mix_probe_kernel(const float *const *tptr, const uint32_t *roff, const int32_t *col_of, int roff_stride, float *out, int rows, int nslots,
                  int nsp8, int nlist, int deal_tiles, int out_stride, int policy) {
@@ -105,7 +113,13 @@ mix_probe_kernel(const float *const *tptr, const uint32_t *roff, const int32_t *
   float *outp = out + q * V;
 #pragma unroll
   for (int r = 0; r < R; ++r)
-    if (row0 + r < rows) st_out<V>(outp + (int64_t)(row0 + r) * out_stride, v[r], policy);
+    if (row0 + r < rows) {
+      float *p = outp + (int64_t)(row0 + r) * out_stride;
+      if (policy & kProbeStSc1)
+        probe_st_sc1(p, v[r]);
+      else
+        st_out<V>(p, v[r], policy);
+    }
 }
 
 static uint64_t splitmix(uint64_t &s) {
@@ -490,11 +504,11 @@ int main(int argc, char **argv) {
     std::printf("mix probe %d: grid %d x %d, %d slots, %d rows; per launch %.1f MB of table lines + %.1f MB of output + %.1f MB of offsets\n",
                 mix_probe, grid, FCP_BLOCK_THREADS, nslots, batch, line_bytes / 1e6, (double)batch * width * 4 / 1e6,
                 (double)batch * roff_stride * 4 / 1e6);
-    const char *names[3] = {"nt", "sc1 nt", "plain"};
-    const int policies[3] = {0, FCP_ST_THROUGH, FCP_ST_PLAIN};
+    const char *names[4] = {"nt", "sc1 nt", "plain", "sc1"};
+    const int policies[4] = {0, FCP_ST_THROUGH, FCP_ST_PLAIN, kProbeStSc1};
     for (int pass = 0; pass < 2; ++pass) // (every cell twice: the second pass shows the run-to-run spread)
       for (int nring : {1, 6})
-        for (int k = 0; k < 3; ++k) {
+        for (int k = 0; k < 4; ++k) {
           auto run = [&](int n) {
             for (int i = 0; i < n; ++i)
               hipLaunchKernelGGL(mix_probe_kernel, dim3(grid), dim3(FCP_BLOCK_THREADS), 0, st, d_tptr, d_roff[i % requests],

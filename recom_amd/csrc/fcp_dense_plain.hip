@@ -19,6 +19,8 @@
 //     id loads; a loop of as many passes as the span has pairs;
 //   * the conversion for the three id kinds only: a range check on the whole 64-bit id, bucketize_arith, pre-scaled
 //     32-bit slot offsets parked in LDS.
+// Phase 2 has one store form more than st_out's three: write-through without the streaming hint (st_through_alloc below),
+// which store_policy_for hands to this kernel for large outputs into a reused arena (S2 25.57 -> 24.35 us).
 // Same bits out as the generic kernel, same bad-id counts (a column that straddles two spans is counted by the block that
 // holds its first slot).
 #include "fcp_fused_bodies.h"
@@ -43,6 +45,23 @@ static_assert(PlainLds<4>::REC / 16 <= FCP_BLOCK_THREADS, "one 16-byte piece of 
 // an int64 id of the blob: 4-byte aligned only (ConcatInputs packs tensors back to back), read with one 8-byte load
 typedef uint32_t __attribute__((ext_vector_type(2))) U2;
 typedef U2 __attribute__((aligned(4))) Id64;
+
+// Fourth output-store form, this kernel's alone: write-through WITHOUT the streaming hint (`sc1`: the line leaves the XCD's
+// L2 at once, as under `sc1 nt`, and allocates as a plain store does).  FcpPlainLaunch::store_policy bit 3
+// (FCP_ST_THROUGH_ALLOC); the other three forms are st_out's (fcp_fused_bodies.h), untouched.  Inline asm ending in
+// s_nop 1, for st_through's reasons.  Measured in profiles/dense_plain_store_sc1_ab.txt.
+__device__ __forceinline__ void st_through_alloc(FCP_GLOBAL VecType<4>::T *p, VecType<4>::T t) {
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(t) : "memory");
+}
+__device__ __forceinline__ void st_out_plain(float *p, const VF<4> &v, int policy) {
+  if (policy & FCP_ST_THROUGH_ALLOC) {
+    VecType<4>::T t;
+    __builtin_memcpy(&t, &v, sizeof(t));
+    st_through_alloc(as_global(reinterpret_cast<VecType<4>::T *>(p)), t);
+    return;
+  }
+  st_out<4>(p, v, policy);
+}
 
 template <int R>
 __global__ void __launch_bounds__(FCP_BLOCK_THREADS)
@@ -129,7 +148,7 @@ fcp_dense_kernel_plain(const char *img, const char *blob, float *out, int rows, 
   const int q = q0 + lane;
   if (q >= nslots) return;
 
-  // ---- phase 2: R table reads in flight per lane, then R coalesced stores (dense_body's) ------------------------------
+  // ---- phase 2: R table reads in flight per lane, then R coalesced stores (dense_body's, and a fourth store form) -----
   const int j = H.lane_col[lane];
   const float *tb = cols[j].table + (q * V - cols[j].out_off);
   float *outp = out + q * V;
@@ -146,7 +165,7 @@ fcp_dense_kernel_plain(const char *img, const char *blob, float *out, int rows, 
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const int b = row_blk + r0 + r;
-    if (b < rows) st_out<V>(outp + (int64_t)b * out_stride, v[r], policy);
+    if (b < rows) st_out_plain(outp + (int64_t)b * out_stride, v[r], policy);
   }
 }
 

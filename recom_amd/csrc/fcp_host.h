@@ -206,6 +206,9 @@ struct fcp_plan : fcph::HostPlan {
   // The plain kernel's block mapping (fcp_plain_map.h): the partial last group of eight spans dealt evenly over the XCDs,
   // or the generic kernel's.  FCP_DIAG=plain_even_deal=0|1 at plan creation; the default is FCP_PLAIN_EVEN_DEAL_DEFAULT.
   bool plain_even_deal = false;
+  // FCP_DIAG=store_policy=sc1 at plan creation: every launch of the plain dense kernel stores `sc1`, whatever the output
+  // size or the arena (the A/B's and the tests' seam; store_policy_for).  No other kernel has the form or reads the key.
+  bool plain_store_sc1 = false;
   int32_t plain_stride = 0, plain_spans = 0, plain_cols_off = 0; // (plain_cols_off: FcpPlainSpan::cols_off of every record)
   std::vector<char> plain_tmpl;
   std::vector<std::pair<uint32_t, int32_t>> plain_entries;

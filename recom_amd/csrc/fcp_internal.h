@@ -171,8 +171,11 @@ struct FcpPlainLaunch {
   int32_t deal_tiles;      // the grid's row tiles: the partial last group of eight spans is dealt evenly to the XCDs
                            // (fcp_plain_map.h); 0: the generic kernel's block mapping
   int32_t out_stride;      // row stride of the output in elements
-  int32_t store_policy;    // FcpLaunch::store_through bits 0 and 2
+  int32_t store_policy;    // FcpLaunch::store_through bits 0 and 2, or FCP_ST_THROUGH_ALLOC alone
 };
+// bit 3 of FcpPlainLaunch::store_policy: write-through stores without the streaming hint (`sc1`), a form only the plain
+// dense kernel has (FCP_LAUNCH_STORE_SC1 of fcp_plan_last_launch)
+constexpr int FCP_ST_THROUGH_ALLOC = 8;
 
 // Segment-offset pre-pass (ComputeSegmentOffsets, cuda_emitter.cc:768-818)
 struct FcpSegLaunch {

@@ -76,6 +76,8 @@ void build_plain_template(fcp_plan *p) {
   if (fcp::diag_ll("dense_generic", 0) != 0) return;
   // FCP_DIAG=plain_even_deal=0|1: the block mapping of the plain kernel's partial last group (the A/B's seam)
   p->plain_even_deal = fcp::diag_ll("plain_even_deal", FCP_PLAIN_EVEN_DEAL_DEFAULT) != 0;
+  // FCP_DIAG=store_policy=sc1: the plain kernel's launches store `sc1` whatever the rule says (store_policy_for)
+  if (const char *v = fcp::diag("store_policy")) p->plain_store_sc1 = !std::strcmp(v, "sc1");
   const fcp_plan_desc_t &d = p->desc;
   if (p->out_elem != 4 || p->tab_elem != 4 || d.layout != FCP_LAYOUT_CONCAT || d.n_groups != 1 || d.shard_world > 1 || p->vec != 4 || p->wide_rows ||
       p->weighted_kernel || !p->dense_only || p->cols.empty())

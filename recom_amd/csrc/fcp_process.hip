@@ -228,7 +228,17 @@ void publish_slot(fcp_plan *p, DynSlot &s, const std::vector<int32_t> &key, void
 //   * larger outputs into any other arena (a ring of three or more, fresh memory): plain stores lose 3 us of 28 there —
 //     write-through `sc1 nt`
 //   (profiles/r06_arena_reuse_store_policy.txt).  A performance hint only: read and updated without the plan's mutex.
-int store_policy_for(fcp_plan *p, const void *arena, int64_t out_bytes) {
+// A launch of the plain dense kernel (plain_launch) has a fourth form, `sc1` (FCP_ST_THROUGH_ALLOC: write-through without the
+// streaming hint — the line leaves the XCD's L2 at once and still allocates as a plain store does).  It is considered only
+// for outputs of at least kSc1MinBytes, the capacity of the eight L2s — a constant, whatever FCP_STORE_THROUGH_BYTES says —
+// and was decided in two cells, each on its own A/B (profiles/dense_plain_store_sc1_ab.txt):
+//   (A) where the rule above says plain (arena reused, at most 160 MiB): `sc1` — S2 with one arena 25.55 -> 24.44 us, every
+//       run faster than every run with plain stores in both visits; batch 1024 47.93 -> 46.28; two arenas 26.55 -> 25.48;
+//   (B) where it says `sc1 nt`: stays `sc1 nt` — `sc1` LOSES there (ring of three 30.2 against 27.3 us, ring of six 30.3
+//       against 27.4, batch 2048 111 against 101; why was not measured).
+// FCP_DIAG=store_policy=sc1 (fcp_plan::plain_store_sc1) forces the form on every launch of that kernel, whatever the size.
+// Every other kernel, and every smaller output, gets the rule above.
+int store_policy_for(fcp_plan *p, const void *arena, int64_t out_bytes, bool plain_launch) {
   const int64_t through_bytes = p->env.store_through_bytes;
   const uintptr_t ar = reinterpret_cast<uintptr_t>(arena);
   const uintptr_t a0 = p->recent_arena[0].load(std::memory_order_relaxed), a1 = p->recent_arena[1].load(std::memory_order_relaxed);
@@ -238,8 +248,11 @@ int store_policy_for(fcp_plan *p, const void *arena, int64_t out_bytes) {
     p->recent_arena[0].store(ar, std::memory_order_relaxed);
   }
   constexpr int64_t kPlainMaxBytes = (int64_t)160 << 20;
+  constexpr int64_t kSc1MinBytes = (int64_t)32 << 20;
+  if (plain_launch && p->plain_store_sc1) return FCP_ST_THROUGH_ALLOC;
   if (out_bytes < through_bytes) return 0;
-  return (reused && out_bytes <= kPlainMaxBytes) ? 4 : 1;
+  if (!(reused && out_bytes <= kPlainMaxBytes)) return 1;                            // cell B
+  return plain_launch && out_bytes >= kSc1MinBytes ? FCP_ST_THROUGH_ALLOC : 4;       // cell A
 }
 
 void fill_launch(const fcp_plan *p, const DynSlot &s, int kind, const void *blob, void *arena, int store_policy, FcpLaunch *L) {
@@ -368,7 +381,8 @@ int fcp_internal_process(fcp_plan_t *p, const fcp_process_args_t *a, fcp_process
   }
 
   FcpLaunch L;
-  const int store_policy = store_policy_for(p, arena, m.csr_arena_off);
+  const bool plain_launch = p->variant != FCP_VAR_WEIGHTED && m.geo[0].grid_blocks > 0 && m.plain; // (the dispatch below)
+  const int store_policy = store_policy_for(p, arena, m.csr_arena_off, plain_launch);
   fill_launch(p, *slot, 1, a->concated_inputs, arena, store_policy, &L);
   { // fcp_plan_last_launch (diagnostics): the dispatch below, as it will be made
     fcp_plan::LastLaunch &ll = p->last_launch;

@@ -43,7 +43,7 @@ LAUNCH_KERNELS = {0: "none", 1: "dense", 2: "ragged", 3: "hybrid", 4: "ragged_we
                   11: "dense_tabq8", 12: "ragged_tabq8", 13: "hybrid_tabq8",
                   14: "dense_tabmix", 15: "ragged_tabmix", 16: "hybrid_tabmix"}
 DENSE_FRONTS = {0: "none", 1: "generic", 2: "plain"}   # fcp_plan_last_dense_front
-LAUNCH_STORES = {0: "nt", 1: "sc1_nt", 4: "plain"}
+LAUNCH_STORES = {0: "nt", 1: "sc1_nt", 4: "plain", 8: "sc1"}
 LAUNCH_SEGMENT_OFFSETS = {0: "none", 1: "prepass", 2: "search"}
 # fcp_aux_launch_counts: the kernels outside the fused matrix, one counter per instantiation (FCP_AUX_* order)
 AUX_KERNELS = ("segment_offsets", "shard_finalize_v4", "shard_finalize_v2", "shard_finalize_v1",
