@@ -644,6 +644,72 @@ int64_t fcp_table_delta_workspace_bytes(int64_t n);
 int fcp_table_delta_distinct(const void *row_ids, int32_t id_bytes, const float *rows, int32_t dim, int64_t n, int64_t table_rows,
                              int64_t *ids_out, float *rows_out, int64_t *pos_out, fcp_table_delta_report_t *report, void *workspace,
                              int32_t device, void *stream);
+/* ---- a model's delta made distinct: many tables in one call -------------------------------------------------------------------- */
+/* fcp_tables_update_rows, fcp_tables_read_rows and fcp_tables_digest take a model's delta in one call and ask that the ids of
+ * each entry be pairwise distinct; fcp_table_delta_distinct guarantees that for one table with five launches.
+ * fcp_tables_delta_distinct is that entry for MANY tables: one fcp_table_delta_entry_t per table (an ENTRY), int32 and int64
+ * ids, ids only and rows of any dim mixed, and a number of launches that does not grow with n_tables.
+ *
+ * `entries` is a HOST array of n_tables records; it is read before the call returns and may then be freed.  Everything an entry
+ * points at is on the device.  Once the stream has run, for every entry k, `ids_out`, `pos_out`, the rows < m_k of `rows_out`
+ * and reports[k] (`reports`: device, n_tables records) hold exactly the bytes ONE fcp_table_delta_distinct call with entry k's
+ * arguments leaves; rows >= m_k of `rows_out` are not touched; an entry with n == 0 gets reports[k] = {0, 0, 0, 0} and nothing
+ * else.  Entries are INDEPENDENT: each has a hash table of its own, two entries may carry the same ids, for the same table or
+ * not, and an id that repeats ACROSS two entries is not seen — entries that name one table must be merged into one entry first
+ * (concatenated in the order they are to be applied) if the result is to be distinct for that table.  Every output byte is a
+ * function of the arguments alone: two calls leave the same bytes, whatever the workspace held.  Per entry, asynchrony on
+ * `stream`, "no allocation, no synchronisation", the alignment rules, the row limit and "outputs must not overlap the inputs
+ * or each other" are inherited unchanged from fcp_table_delta_distinct.
+ *
+ * Limits: n_tables lies in [0, 65536], and the ids of one call, n summed over its entries, stay below 2^32 - 3 (the
+ * single-table limit, applied to the sum).
+ *
+ * `workspace`: fcp_tables_delta_workspace_bytes of the entries' n values (a host array, in entry order) bytes on the device,
+ * 8-byte aligned, the call's own until its kernels have run (calls on one stream may share one); its content before and after
+ * the call means nothing.  The size is a function of the n values alone: a multiple of 8, non-decreasing in every n[k], at
+ * most 40 * N + 1024 * n_tables + 2^10 with N the sum of the n[k]; -1 for an invalid argument (n_tables outside its range, a
+ * null n with n_tables > 0, an n[k] that is negative or beyond the limit, a sum beyond the limit).
+ *
+ * Launches.  One launch installs the entries' records in the workspace; then ONE clear (the entries' hash tables lie back to
+ * back), ONE insert, ONE classify and ONE fold (a wave per entry) follow, whatever n_tables is, each block finding its entry
+ * by a search over a first-block table; then one compact launch per CLASS present: ids only, or the (V, G) of the entry's rows
+ * — V the largest of 4 | 2 | 1 that divides dim, G the lanes that share a row — 1 + 21 classes, so a call enqueues at most 27
+ * launches (of the 21, the dims that exist reach 18: 24).  fcp_tables_delta_launches (host only, no device is touched) returns
+ * the number for these entries, computed by the function the entry builds its launch list with: 0 for n_tables == 0, 1 when
+ * every n == 0 (only the reports are written, nothing is installed), the negative of the status for invalid entries.
+ * Alone, an entry takes the classify / compact grid of fcp_table_delta_distinct, B blocks (at most 1024, a block at least 1024
+ * positions).  Grouped it takes that grid while the Bs of a call sum to fcp_tables_delta_deal_blocks() = 8192 or less; else
+ * the grid of at most max(1, floor(B * 8192 / sum)) blocks: a call's blocks sum to at most 8192 + n_tables and no block is
+ * idle.  fcp_tables_delta_grid (host only) returns the call's classify grid and, `blocks` not NULL, every entry's share (0
+ * without ids).  The deal plays no part in the result.
+ *
+ * Status, decided in this order (the first needs no device and dereferences no device pointer):
+ *   FCP_ERR_INVALID_ARGUMENT  n_tables outside [0, 65536]; a null `entries` with n_tables > 0; then, over the entries in
+ *                             ascending order, what fcp_table_delta_distinct refuses for the entry's fields, in its order and
+ *                             by its text (`report` and `workspace` are the call's: checked behind the entries), behind
+ *                             "fcp_tables_delta_distinct: entry k: "; then 2^32 - 3 ids or more together; then a null
+ *                             (n_tables > 0) or misaligned `reports`; then a null (n_tables > 0) or misaligned `workspace`;
+ *   FCP_OK                    n_tables == 0: no device is touched;
+ *   FCP_ERR_NO_DEVICE         no usable gfx950 device;
+ *   FCP_ERR_UNSUPPORTED       `stream` is capturing and an entry has ids: the records are installed from the host by every
+ *                             call, which a replay would not repeat (the only such case);
+ *   FCP_ERR_HIP               a runtime call or a kernel launch failed. */
+typedef struct fcp_table_delta_entry {
+  const void *row_ids;   /* device int64 [n] (id_bytes 8) or int32 [n] (id_bytes 4) */
+  const float *rows;     /* device float32 [n, dim], or NULL: ids only */
+  int64_t *ids_out;      /* device int64 [n] */
+  float *rows_out;       /* device float32 [n, dim]; NULL exactly when rows is NULL */
+  int64_t *pos_out;      /* device int64 [n], or NULL */
+  int64_t table_rows, n;
+  int32_t id_bytes, dim;
+} fcp_table_delta_entry_t;   /* 64 bytes */
+int64_t fcp_tables_delta_workspace_bytes(const int64_t *n /* host [n_tables] */, int32_t n_tables);
+int32_t fcp_tables_delta_launches(const fcp_table_delta_entry_t *entries, int32_t n_tables);  /* host only */
+int32_t fcp_tables_delta_deal_blocks(void);                                                   /* host only */
+int32_t fcp_tables_delta_grid(const fcp_table_delta_entry_t *entries, int32_t n_tables, int32_t *blocks /* host [n_tables] or NULL */);  /* host only */
+int fcp_tables_delta_distinct(const fcp_table_delta_entry_t *entries, int32_t n_tables,
+                              fcp_table_delta_report_t *reports /* device [n_tables] */,
+                              void *workspace, int32_t device, void *stream);
 /* ---- a new master against a served table: the rows whose stored bytes would change ------------------------------------------ */
 /* Every entry above takes a delta somebody already has.  A trainer often ships a whole new float32 checkpoint instead, and a
  * digest says THAT two replicas differ, not WHERE.  fcp_table_diff turns "new rows + served table" into the delta

@@ -51,6 +51,19 @@ template <class R, class P> __device__ __forceinline__ void block_fold(R p, P *p
   }
 }
 
+// ... and with the record's place given: a block of a grouped launch owns a record of its ENTRY's run, not number blockIdx.x
+template <class R, class P> __device__ __forceinline__ void block_fold_to(R p, P *mine) {
+  wave_fold(p);
+  __shared__ R s_wave[FCP_BLOCK_THREADS / 64];
+  const int tid = threadIdx.x;
+  if ((tid & 63) == 0) s_wave[tid / 64] = p;
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < FCP_BLOCK_THREADS / 64; ++w) fold(p, s_wave[w]);
+    *mine = p;
+  }
+}
+
 // ---- a block's LDS table of SLOTS {row, value} cells, SLOTS a power of two, for a block of THREADS threads.  The kernel owns
 // the two __shared__ arrays.  A row's home is row mod SLOTS; it looks at kLdsRowProbes cells from there on.  A cell is claimed
 // by an LDS compare-and-swap on its key; the key of a claimed cell never changes while the block runs, so a key that is read as

@@ -55,6 +55,24 @@ template <int Blocks, class P> __device__ __forceinline__ void select_offsets(P 
   }
 }
 
+// The run-time form, for a fold whose wave serves an entry of a grouped call (fcp_tables_delta.hip): `per` records per lane, any
+// per with 64 * per >= nblocks, where the template form takes Blocks / 64.
+template <class P> __device__ __forceinline__ void select_offsets_n(P *partials, int nblocks, int per, int64_t mine) {
+  const int lane = threadIdx.x & 63;
+  const int b0 = lane * per < nblocks ? lane * per : nblocks, b1 = b0 + per < nblocks ? b0 + per : nblocks;
+  int64_t before = mine; // inclusive scan of the lanes' counts, then made exclusive
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int64_t up = __shfl_up(before, d, 64);
+    if (lane >= d) before += up;
+  }
+  before -= mine;
+  for (int b = b0; b < b1; ++b) {
+    partials[b].offset = before;
+    before += selected_of(partials[b]);
+  }
+}
+
 // V 32-bit words as one load / store at the rows' alignment 4 * V
 template <int V> struct Words;
 template <> struct Words<4> { typedef uint32_t __attribute__((ext_vector_type(4))) T; };
@@ -78,6 +96,57 @@ __device__ __forceinline__ void select_compact(const uint8_t *flags, const P *pa
   const int64_t c1 = c0 + chunk < n ? c0 + chunk : n;
   const int64_t m = selected_of(partials[Blocks]);
   int64_t k0 = partials[blockIdx.x].offset; // the output index of the tile's first selected position
+  for (int64_t t0 = c0; t0 < c1; t0 += kSelectTile) {
+    const int64_t i = t0 + tid;
+    const bool have = i < c1;
+    const bool hit = have && *as_global(flags + i) != 0;
+    const auto brought = h.prepare(i, have);
+    const unsigned long long ballot = __ballot(hit);
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+    if ((tid & 63) == 0) s_count[wave] = (uint32_t)__popcll(ballot);
+    __syncthreads();
+    uint32_t rank = below, total = 0;
+#pragma unroll
+    for (int w = 0; w < kSelectTile / 64; ++w) {
+      const uint32_t c = s_count[w];
+      if (w < wave) rank += c;
+      total += c;
+    }
+    if (hit) {
+      h.emit(k0 + rank, i, brought);
+      if constexpr (V > 0) s_list[rank] = (uint32_t)tid;
+    }
+    if (have && i >= m) h.tail(i);
+    __syncthreads(); // s_list is whole; s_count may be written again
+    if constexpr (V > 0) {
+      typedef typename Words<V>::T W;
+      const int lane = tid & (G - 1);
+      const int nslots = dim / V;
+      for (uint32_t j = (uint32_t)(tid / G); j < total; j += kSelectTile / G) {
+        const FCP_GLOBAL W *src = as_global(reinterpret_cast<const W *>(rows + (t0 + (int64_t)s_list[j]) * dim));
+        FCP_GLOBAL W *dst = as_global(reinterpret_cast<W *>(rows_out + (k0 + (int64_t)j) * dim));
+        for (int slot = lane; slot < nslots; slot += G) dst[slot] = src[slot];
+      }
+      __syncthreads(); // the copies have read s_list
+    }
+    k0 += total;
+  }
+}
+
+// The run-time form, for a block that serves an entry of a grouped call (fcp_tables_delta.hip): `block` of the entry's own
+// `nblocks`, its records partials[0 .. nblocks) and its totals partials[nblocks], where the template form takes blockIdx.x and
+// Blocks.  The same steps, barriers and LDS.
+template <int V, int G, class P, class H>
+__device__ __forceinline__ void select_compact_at(const uint8_t *flags, const P *partials, uint32_t block, uint32_t nblocks, int64_t n, int64_t chunk,
+                                                  const float *rows, float *rows_out, int32_t dim, const H &h) {
+  __shared__ uint32_t s_list[kSelectTile]; // the tile's selected positions, by rank: their thread
+  __shared__ uint32_t s_count[kSelectTile / 64];
+  const int tid = threadIdx.x;
+  const int wave = tid / 64;
+  const int64_t c0 = (int64_t)block * chunk;
+  const int64_t c1 = c0 + chunk < n ? c0 + chunk : n;
+  const int64_t m = selected_of(partials[nblocks]);
+  int64_t k0 = partials[block].offset; // the output index of the tile's first selected position
   for (int64_t t0 = c0; t0 < c1; t0 += kSelectTile) {
     const int64_t i = t0 + tid;
     const bool have = i < c1;

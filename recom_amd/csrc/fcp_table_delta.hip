@@ -43,81 +43,12 @@
 #include "fcp_table_walk.h" // vec_of, group_of, with_vec, with_group: the rows' V and G, the host's dispatch
 #include "fcp_block_fold.h" // wave_fold, block_fold; the block's LDS row table, kEmptyCell
 #include "fcp_select_compact.h" // select_grid, select_offsets, select_compact, with_compact_shape: the selection's shared tail
+#include "fcp_delta_table.h" // the records, the hash table, ld_id, the geometry's constants: shared with fcp_tables_delta.hip
+#include "fcp_tables_delta_plan.h" // check_delta_args, cells_for: the host-only level, shared with the grouped entry
+
+static_assert(fcptd::kMinCells == kDeltaMinCells, "one rule for the cells of a hash table");
 
 namespace {
-
-constexpr int kDeltaThreads = FCP_BLOCK_THREADS;
-constexpr int kDeltaTile = kSelectTile;             // positions of one step of a classify / compact block
-constexpr int kDeltaBlocks = 1024;                  // the fixed grid of classify / compact; also the partial records
-constexpr int kDeltaMinChunkTiles = 4;              // a block's chunk is at least this many tiles
-constexpr int kDeltaInsertIdsPerThread = 4;
-constexpr int kDeltaInsertTile = kDeltaThreads * kDeltaInsertIdsPerThread;
-constexpr int kDeltaInsertMaxBlocks = 65535;        // longer deltas: the stride loop
-constexpr int kDeltaClearBlocks = 4096;
-constexpr int kDeltaSlots = 2048;                   // cells of a block's LDS table: 2 x 8 KiB, for a tile of 1024 positions
-constexpr int64_t kDeltaMinCells = 64;
-constexpr uint64_t kDeltaHashMul = 0x9E3779B97F4A7C15ull;
-
-// What a block of the classify phase counted, and, once the fold has run, where its winners go.  32 bytes.
-struct DeltaPartial {
-  int64_t winners, duplicates, skipped;
-  int64_t offset; // winners of the blocks before this one (the totals record: unused)
-};
-static_assert(sizeof(DeltaPartial) == 32 && sizeof(fcp_table_delta_report_t) == 32, "records of 32 bytes");
-
-// What a lane, a wave and a block of the classify phase count (uint32_t: a chunk stays below 2^23 positions), and what the
-// lanes of the fold sum (int64_t)
-template <class T> struct DeltaCounts {
-  T winners, duplicates, skipped;
-  __device__ operator DeltaPartial() const { return DeltaPartial{(int64_t)winners, (int64_t)duplicates, (int64_t)skipped, 0}; }
-};
-template <class T> __device__ __forceinline__ void fold(DeltaCounts<T> &a, const DeltaCounts<T> &b) {
-  a.winners += b.winners;
-  a.duplicates += b.duplicates;
-  a.skipped += b.skipped;
-}
-
-struct DeltaTable {
-  uint32_t *cells; // cell c: key at cells[2 c], pos1 at cells[2 c + 1]
-  uint64_t mask;   // cells - 1
-  int32_t shift;   // 64 - log2(cells)
-};
-
-__device__ __forceinline__ uint64_t ld_id(const void *ids, int64_t i, bool is64) {
-  return is64 ? (uint64_t)*as_global(static_cast<const int64_t *>(ids) + i)
-              : (uint64_t)(int64_t)*as_global(static_cast<const int32_t *>(ids) + i);
-}
-
-__device__ __forceinline__ uint64_t home_of(const DeltaTable &T, uint32_t row) { return ((uint64_t)row * kDeltaHashMul) >> T.shift; }
-
-// pos1 into the cell of `row`, claiming one if the row has none yet.  At most `cells` steps; the load is at or below 0.5.
-__device__ __forceinline__ void insert_global(const DeltaTable &T, uint32_t row, uint32_t pos1) {
-  uint64_t c = home_of(T, row);
-  for (uint64_t step = 0; step <= T.mask; ++step, c = (c + 1) & T.mask) {
-    uint32_t *key = T.cells + 2 * c;
-    uint32_t k = __hip_atomic_load(as_global(key), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (k == kEmptyCell) {
-      uint32_t seen = kEmptyCell; // what the cell held: still empty = claimed for row
-      __hip_atomic_compare_exchange_strong(as_global(key), &seen, row, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      k = seen == kEmptyCell ? row : seen;
-    }
-    if (k == row) {
-      (void)__hip_atomic_fetch_max(as_global(key + 1), pos1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return;
-    }
-  }
-}
-
-// the pos1 of `row`'s cell; 0 if the row has none (the insert phase gave every row inside the table one)
-__device__ __forceinline__ uint32_t lookup_global(const DeltaTable &T, uint32_t row) {
-  uint64_t c = home_of(T, row);
-  for (uint64_t step = 0; step <= T.mask; ++step, c = (c + 1) & T.mask) {
-    const uint64_t cell = *as_global(reinterpret_cast<const uint64_t *>(T.cells + 2 * c)); // key in the low half, pos1 in the high
-    if ((uint32_t)cell == row) return (uint32_t)(cell >> 32);
-    if ((uint32_t)cell == kEmptyCell) return 0;
-  }
-  return 0;
-}
 
 // one cell per 8-byte store (the workspace is 8-byte aligned, no more)
 __global__ void __launch_bounds__(kDeltaThreads) fcp_delta_clear_kernel(uint32_t *cells, uint64_t n_cells) {
@@ -231,11 +162,7 @@ template <int V, int G> __global__ void __launch_bounds__(kDeltaThreads) fcp_del
   select_compact<V, G, kDeltaBlocks>(A.flags, A.partials, A.n, A.chunk, A.rows, A.rows_out, A.dim, DeltaEmit{A});
 }
 
-int64_t cells_for(int64_t n) {
-  int64_t cells = kDeltaMinCells;
-  while (cells < 2 * n) cells <<= 1;
-  return cells;
-}
+using fcptd::cells_for;
 int64_t partial_bytes() { return (int64_t)(kDeltaBlocks + 1) * (int64_t)sizeof(DeltaPartial); }
 
 } // namespace
@@ -248,25 +175,11 @@ extern "C" int64_t fcp_table_delta_workspace_bytes(int64_t n) {
 extern "C" int fcp_table_delta_distinct(const void *row_ids, int32_t id_bytes, const float *rows, int32_t dim, int64_t n, int64_t table_rows,
                                         int64_t *ids_out, float *rows_out, int64_t *pos_out, fcp_table_delta_report_t *report,
                                         void *workspace, int32_t device, void *stream) {
-  const std::string w = "fcp_table_delta_distinct: ";
-  if (n < 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`n` is negative");
-  if (const std::string why = fcpf::row_limit_refusal("n", n, table_rows); !why.empty()) return fail(FCP_ERR_INVALID_ARGUMENT, w + why);
-  if (id_bytes != 4 && id_bytes != 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`id_bytes` is 4 (int32 ids) or 8 (int64 ids)");
-  if (rows && dim <= 0) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`dim` must be positive");
-  if (rows_out && !rows) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`rows_out` without `rows`: ids only takes both null");
-  if (rows && !rows_out) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`rows_out` is null and `rows` is not");
-  if (!report) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`report` is null");
-  if (!workspace) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`workspace` is null");
-  if (n > 0 && !row_ids) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`row_ids` is null");
-  if (n > 0 && !ids_out) return fail(FCP_ERR_INVALID_ARGUMENT, w + "`ids_out` is null");
+  std::string why;
+  if (const int rc = fcptd::check_delta_args("fcp_table_delta_distinct: ", row_ids, id_bytes, rows, dim, n, table_rows, ids_out, rows_out, pos_out,
+                                             report, workspace, &why))
+    return fail(rc, why);
   const int vec = rows ? vec_of(dim) : 1;
-  if ((uintptr_t)row_ids % (uintptr_t)id_bytes) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("row_ids", id_bytes));
-  if ((uintptr_t)rows % (4 * vec)) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("rows", 4 * vec, " (float32 rows of this dim)"));
-  if ((uintptr_t)ids_out % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("ids_out", 8));
-  if ((uintptr_t)rows_out % (4 * vec)) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("rows_out", 4 * vec, " (float32 rows of this dim)"));
-  if ((uintptr_t)pos_out % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("pos_out", 8));
-  if ((uintptr_t)report % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("report", 8));
-  if ((uintptr_t)workspace % 8) return fail(FCP_ERR_INVALID_ARGUMENT, w + fcpf::not_aligned("workspace", 8));
 
   DeltaPartial *partials = static_cast<DeltaPartial *>(workspace);
   const int64_t cells = cells_for(n);

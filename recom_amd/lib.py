@@ -170,6 +170,12 @@ class TableDigestEntry(C.Structure):
                 ("row_step", C.c_int64), ("kind", C.c_int32), ("dim", C.c_int32), ("reserved", C.c_int64)]
 
 
+class TableDeltaEntry(C.Structure):
+    """fcp_table_delta_entry_t: one entry of fcp_tables_delta_distinct"""
+    _fields_ = [("row_ids", C.c_void_p), ("rows", C.c_void_p), ("ids_out", C.c_void_p), ("rows_out", C.c_void_p), ("pos_out", C.c_void_p),
+                ("table_rows", C.c_int64), ("n", C.c_int64), ("id_bytes", C.c_int32), ("dim", C.c_int32)]
+
+
 class PrivateStreamsStats(C.Structure):
     """fcp_private_streams_stats_t"""
     _fields_ = [("supervised_stream", C.c_void_p), ("requests", C.c_int64), ("lane_requests", C.c_int64), ("evaluations", C.c_int64),
@@ -226,6 +232,8 @@ EXPORTS = [
     "fcp_outputs_compare_workspace_bytes", "fcp_outputs_compare",
     "fcp_tables_rows_workspace_bytes", "fcp_tables_rows_launches", "fcp_tables_update_rows", "fcp_tables_read_rows",
     "fcp_tables_digest_workspace_bytes", "fcp_tables_digest_launches", "fcp_tables_digest",
+    "fcp_tables_delta_workspace_bytes", "fcp_tables_delta_launches", "fcp_tables_delta_deal_blocks", "fcp_tables_delta_grid",
+    "fcp_tables_delta_distinct",
 ]
 
 _lib = None
@@ -430,6 +438,16 @@ def load() -> C.CDLL:
         L.fcp_tables_rows_launches.argtypes = [C.POINTER(TableRows), C.c_int32]
         L.fcp_tables_update_rows.argtypes = [C.POINTER(TableRows), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.fcp_tables_read_rows.argtypes = [C.POINTER(TableRows), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    if hasattr(L, "fcp_tables_delta_distinct"):
+        L.fcp_tables_delta_workspace_bytes.restype = C.c_int64
+        L.fcp_tables_delta_workspace_bytes.argtypes = [C.POINTER(C.c_int64), C.c_int32]
+        L.fcp_tables_delta_launches.restype = C.c_int32
+        L.fcp_tables_delta_launches.argtypes = [C.POINTER(TableDeltaEntry), C.c_int32]
+        L.fcp_tables_delta_deal_blocks.restype = C.c_int32
+        L.fcp_tables_delta_deal_blocks.argtypes = []
+        L.fcp_tables_delta_grid.restype = C.c_int32
+        L.fcp_tables_delta_grid.argtypes = [C.POINTER(TableDeltaEntry), C.c_int32, C.POINTER(C.c_int32)]
+        L.fcp_tables_delta_distinct.argtypes = [C.POINTER(TableDeltaEntry), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     if hasattr(L, "fcp_tables_digest"):
         L.fcp_tables_digest_workspace_bytes.restype = C.c_int64
         L.fcp_tables_digest_workspace_bytes.argtypes = [C.c_int32]

@@ -862,6 +862,173 @@ def apply_delta(table, row_ids, rows, digest: Optional[int] = None, row0: int = 
     return report, (int(digest) - int(before.sum) + int(after.sum)) % (1 << 64)
 
 
+# ---- a model's delta made distinct, many tables in one call (fcp_tables_delta_distinct) -----------------------------------------
+def _delta_entries(torch, row_ids, rows, table_rows, pos: bool, stream: Optional[int]):
+    """What one ``fcp_tables_delta_distinct`` call takes: every entry validated as ``delta_distinct_async`` validates its own,
+    the outputs carved out of ONE tensor per kind (int64 ids, int64 positions, float32 rows, each entry's rows at a 16-byte
+    boundary, int64 reports) and the workspace, all allocated as that stream's.  Returns ``(entries, device, stream, ids_out,
+    rows_out, pos_out, reports, workspace)`` — the per-entry outputs as lists of views — or ``device`` ``None`` without entries."""
+    n_tables = len(row_ids)
+    if rows is not None and len(rows) != n_tables:
+        raise ValueError(f"row_ids names {n_tables} entries, rows {len(rows)}")
+    if not hasattr(table_rows, "__len__") or len(table_rows) != n_tables:
+        raise ValueError(f"row_ids names {n_tables} entries; table_rows is a sequence as long: the rows of each entry's table")
+    if n_tables == 0:
+        return None, None, stream, [], [], [], None, None
+    device = None
+    ns, dims = [], []
+    for k in range(n_tables):
+        try:
+            n = _delta_ids_of(torch, row_ids[k])
+            if device is None:
+                device = row_ids[k].device
+            elif row_ids[k].device != device:
+                raise ValueError(f"row_ids is on {row_ids[k].device}, entry 0's on {device}")
+            dim = None
+            if rows is not None and rows[k] is not None:
+                r = rows[k]
+                if r.dtype != torch.float32 or r.dim() != 2 or not r.is_contiguous():
+                    raise ValueError("rows is a contiguous float32 [n, dim] tensor")
+                if r.device != device:
+                    raise ValueError(f"row_ids is on {device}, rows on {r.device}")
+                if r.shape[0] != n:
+                    raise ValueError(f"rows has {r.shape[0]} rows, row_ids names {n}")
+                dim = int(r.shape[1])
+        except ValueError as e:
+            raise ValueError(f"entry {k}: {e}") from None
+        ns.append(n)
+        dims.append(dim)
+    L = _lib.load()
+    need = int(L.fcp_tables_delta_workspace_bytes((C.c_int64 * n_tables)(*ns), n_tables))
+    if need < 0:
+        raise ValueError(f"row_ids names {n_tables} entries of {sum(ns)} ids together; a call takes at most 65536 entries and stays below 2^32 - 3 ids")
+    stream = _stream_of(torch, device, stream)
+    row_at, floats = [], 0
+    for n, dim in zip(ns, dims):
+        row_at.append(floats)
+        floats += (n * (dim or 0) + 3) // 4 * 4
+    total = sum(ns)
+    with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device)):
+        ids_all = torch.empty((total,), dtype=torch.int64, device=device)
+        pos_all = torch.empty((total,), dtype=torch.int64, device=device) if pos else None
+        rows_all = torch.empty((floats,), dtype=torch.float32, device=device)
+        reports = torch.empty((n_tables, C.sizeof(_lib.TableDeltaReport) // 8), dtype=torch.int64, device=device)
+        workspace = torch.empty((need // 8,), dtype=torch.int64, device=device)
+    entries = (_lib.TableDeltaEntry * n_tables)()
+    ids_out, rows_out, pos_out = [], [], []
+    at = 0
+    for k, (n, dim) in enumerate(zip(ns, dims)):
+        ids_out.append(ids_all[at:at + n])
+        pos_out.append(pos_all[at:at + n] if pos else None)
+        rows_out.append(rows_all[row_at[k]:row_at[k] + n * dim].view(n, dim) if dim is not None else None)
+        # (an empty tensor may have no address; the entry reads none of its pointers at n == 0)
+        with_rows = dim is not None and n > 0
+        entries[k] = _lib.TableDeltaEntry(row_ids[k].data_ptr() if n else None, rows[k].data_ptr() if with_rows else None,
+                                          ids_out[k].data_ptr() if n else None, rows_out[k].data_ptr() if with_rows else None,
+                                          pos_out[k].data_ptr() if pos and n else None, int(table_rows[k]), n,
+                                          int(row_ids[k].element_size()), dim or 0)
+        at += n
+    return entries, device, stream, ids_out, rows_out, pos_out, reports, workspace
+
+
+def delta_distinct_grouped_async(row_ids, rows, table_rows, pos: bool = False, stream: Optional[int] = None):
+    """``fcp_tables_delta_distinct`` enqueued on ``stream`` (torch's current stream of the device by default), nothing
+    synchronised: ``delta_distinct_async`` for a whole model's delta in ONE call.  ``row_ids`` and ``table_rows`` are equally
+    long sequences, ``rows`` a sequence as long (an entry ``None``: ids only) or ``None`` for ids only throughout; entry k is
+    what ``delta_distinct_async(row_ids[k], rows[k], table_rows=table_rows[k])`` takes, int32 and int64 ids and any dims mixed,
+    on one device; the number of launches does not grow with their number.  Returns one tuple per entry, ``(ids, rows,
+    report)`` — plus ``pos`` when asked — byte for byte what the single-table function leaves, each at its full length n_k.
+    Entries are independent: an id that repeats ACROSS two entries is not seen."""
+    import torch
+    entries, device, stream, ids_out, rows_out, pos_out, reports, workspace = _delta_entries(torch, row_ids, rows, table_rows, pos, stream)
+    if device is None:
+        return []
+    status = _lib.load().fcp_tables_delta_distinct(entries, len(row_ids), _ptr(reports), _ptr(workspace), device.index or 0, C.c_void_p(stream))
+    _lib.check(status, "fcp_tables_delta_distinct")
+    return [(ids_out[k], rows_out[k], reports[k], pos_out[k]) if pos else (ids_out[k], rows_out[k], reports[k]) for k in range(len(row_ids))]
+
+
+def _reports_of(reports) -> list:
+    return [DeltaReport(*(int(v) for v in r)) for r in reports.cpu().tolist()]
+
+
+def delta_distinct_grouped(row_ids, rows, table_rows, pos: bool = False, stream: Optional[int] = None):
+    """``fcp_tables_delta_distinct``: ``delta_distinct`` for a whole model's delta in ONE call and one synchronise — one tuple
+    ``(ids[:m], rows[:m] or None, report)`` per entry, plus ``pos[:m]`` when ``pos``, with ``report`` a ``DeltaReport``."""
+    import torch
+    out = delta_distinct_grouped_async(row_ids, rows, table_rows, pos=pos, stream=stream)
+    if not out:
+        return []
+    device = row_ids[0].device
+    torch.cuda.ExternalStream(_stream_of(torch, device, stream), device=device).synchronize()
+    reports = _reports_of(torch.stack([o[2] for o in out]))
+    result = []
+    for o, report in zip(out, reports):
+        m = report.distinct
+        head = (o[0][:m], o[1][:m] if o[1] is not None else None, report)
+        result.append(head + (o[3][:m],) if pos else head)
+    return result
+
+
+def apply_delta_grouped(tables, row_ids, rows, digests=None, row0=0, row_step=1, skipped=None, stream: Optional[int] = None):
+    """``apply_delta`` for a whole model in FOUR library calls: the grouped distinct, (``fcp_tables_digest`` of the winners'
+    rows,) ``update_rows_grouped`` of the padded outputs, (the same digest again) — every table ends up, byte for byte, as one
+    ``apply_delta`` per entry leaves it.  ``tables``, ``row_ids`` (int64) and ``rows`` are equally long sequences; ``digests``, if
+    given, every table's digest before (``row0`` / ``row_step``: a scalar or one per table, as in ``digests_grouped``).
+    ``skipped``: one int64 ``[len(tables)]`` device tensor; element k grows by entry k's own ids outside its table (not by the
+    ``-1`` padding).  An id that repeats across two entries is not seen: entries that name one table are merged first.  All on
+    ``stream``, one synchronise at the end.  Returns the list of ``DeltaReport``s, or ``(reports, new digests)``."""
+    import torch
+    n_tables = len(tables)
+    if len(row_ids) != n_tables or len(rows) != n_tables:
+        raise ValueError(f"tables names {n_tables} entries, row_ids {len(row_ids)}, rows {len(rows)}")
+    if digests is not None and len(digests) != n_tables:
+        raise ValueError(f"tables names {n_tables} entries, digests {len(digests)}")
+    device = None
+    for k, t in enumerate(tables):
+        try:
+            _name, dim = _kind_and_dim(t, "table")
+            n = _delta_ids_of(torch, row_ids[k])
+            if row_ids[k].device != t.device:
+                raise ValueError(f"table is on {t.device}, row_ids on {row_ids[k].device}")
+            _rows_of(torch, t, dim, n, rows[k], "rows")
+            if device is None:
+                device = t.device
+            elif t.device != device:
+                raise ValueError(f"table is on {t.device}, entry 0's on {device}")
+        except ValueError as e:
+            raise ValueError(f"entry {k}: {e}") from None
+    if skipped is not None:
+        if skipped.dtype != torch.int64 or skipped.dim() != 1 or skipped.shape[0] != n_tables or not skipped.is_contiguous() or \
+                (device is not None and skipped.device != device):
+            raise ValueError("skipped is a contiguous int64 [len(tables)] tensor on the tables' device")
+    if device is None:
+        return [] if digests is None else ([], [])
+    L = _lib.load()
+    stream = _stream_of(torch, device, stream)
+    entries, _device, _stream, ids_d, rows_d, _pos, reports_t, workspace = _delta_entries(torch, row_ids, rows, [int(t.shape[0]) for t in tables],
+                                                                                         False, stream)
+    status = L.fcp_tables_delta_distinct(entries, n_tables, _ptr(reports_t), _ptr(workspace), device.index or 0, C.c_void_p(stream))
+    _lib.check(status, "fcp_tables_delta_distinct")
+    if digests is not None:
+        d_entries, _d = _digest_entries(torch, tables, ids_d, row0, row_step)
+        outs, d_workspace = _grouped_digest_buffers(torch, L, device, stream, n_tables, n_out=2)
+        _enqueue_digests(L, d_entries, n_tables, outs[0], d_workspace, device, stream)
+    update_rows_grouped(tables, ids_d, rows_d, stream=stream)      # (its own skipped counters would count the padding too)
+    if digests is not None:
+        _enqueue_digests(L, d_entries, n_tables, outs[1], d_workspace, device, stream)
+    ext = torch.cuda.ExternalStream(stream, device=device)
+    if skipped is not None:
+        with torch.cuda.stream(ext):
+            skipped.add_(reports_t[:, 3])
+    ext.synchronize()
+    reports = _reports_of(reports_t)
+    if digests is None:
+        return reports
+    before, after = _digests_of(outs[0]), _digests_of(outs[1])
+    return reports, [(int(d) - int(b.sum) + int(a.sum)) % (1 << 64) for d, b, a in zip(digests, before, after)]
+
+
 # ---- a new master against a served table (fcp_table_diff) ----------------------------------------------------------------------
 @dataclasses.dataclass(frozen=True)
 class DiffReport:
